@@ -5,6 +5,11 @@
 torch.distributed.run, one rank per GPU).  A step = one OTPose forward (HRNet-W48 + temporal encoders +
 RSB heads + 5x modulated DCN, fp32, eval) over 16 synthetic clips = 80 frames per rank, inputs resident
 in HBM.  Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+
+A plain run sets up, warms up, times the K steps and prints the line (`ms_per_step` = one timed step).  ``--full`` adds
+everything measured beside the headline (input-copy loop, exact-fp32 kernels, eager PyTorch-ROCm and CPU baselines, the
+7-frame fp16 configuration, the training step, per-kernel rooflines, parity against the reference golden).
+``--dump-outputs DIR`` writes the outputs of the last timed step as DIR/<name>.npy (float32).
 """
 from __future__ import annotations
 
@@ -17,6 +22,10 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+OUTPUT_NAMES = ("output", "rough", "intersection", "prev_b", "context", "squeezed", "total_b")   # OTPose.forward's tuple
+DUMP_MAX_ELEMS = 2 * 1024 * 1024      # float32 elements per dumped output (8 MB): the 7 files stay under 64 MB at any batch
+DUMP_SAMPLE_SEED = 20240917           # the fixed sample of an output larger than that
+
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
@@ -24,12 +33,18 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=16, help="clips per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train-step", action="store_true", help="skip the training-step probe (extra field of the line)")
-    ap.add_argument("--train-f32", action="store_true", help="also time the fp32 training step (1 GPU)")
-    ap.add_argument("--no-exact-fp32", action="store_true", help="skip the exact-fp32-kernel forward reported beside the headline")
-    ap.add_argument("--no-eager-baseline", action="store_true", help="skip the eager PyTorch-ROCm forward timed beside the headline")
-    ap.add_argument("--no-config5", action="store_true", help="skip the 7-frame-window forward (BASELINE configs[4]) reported beside the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything reported beside the headline (baselines, other precisions and configurations, "
+                         "training step, rooflines, golden parity); off: only set-up, warm-up, the timed steps and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the 7 outputs of the last timed step as DIR/<name>.npy (float32; an output over %d elements is "
+                         "a fixed seeded sample of its flattened elements)" % DUMP_MAX_ELEMS)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-train-step", action="store_true", help="with --full: skip the training-step probe (extra field of the line)")
+    ap.add_argument("--train-f32", action="store_true", help="with --full: also time the fp32 training step (1 GPU)")
+    ap.add_argument("--no-exact-fp32", action="store_true", help="with --full: skip the exact-fp32-kernel forward reported beside the headline")
+    ap.add_argument("--no-eager-baseline", action="store_true", help="with --full: skip the eager PyTorch-ROCm forward timed beside the headline")
+    ap.add_argument("--no-config5", action="store_true", help="with --full: skip the 7-frame-window forward (BASELINE configs[4]) reported beside the headline")
     return ap.parse_args(argv)
 
 
@@ -643,6 +658,22 @@ def config5_probe(dev, batch, steps):
             "roofline": roof}
 
 
+def dump_outputs(outs, path):
+    """The 7 outputs a caller of the timed forward receives, as ``path/<name>.npy`` (float32).  An output of more than
+    DUMP_MAX_ELEMS elements (`rough`: 5 frames per clip) is written as the elements at a fixed seeded set of flat indices, in
+    index order, so that the same arguments give the same sample on every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in zip(OUTPUT_NAMES, outs):
+        a = t.detach().float().cpu()
+        if a.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+            idx = torch.randperm(a.numel(), generator=g)[:DUMP_MAX_ELEMS].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
+    log("outputs of the last timed step written to %s" % path)
+
+
 def main():
     a = parse_args()
 
@@ -696,24 +727,28 @@ def main():
             outs = model(xb, margin=mb)
         barrier()
         dt = time.perf_counter() - t0
-        # the same loop fed from a tensor of the CALLER's (what script/Common.py:116-118 does every iteration): the engine copies the
-        # 106 MB clip tensor into its input buffer first - a device-to-device copy that `ms_per_step` (inputs resident in the
-        # engine's own buffers, OTPose.input_buffers) does not contain; reported beside it, never part of `value`
-        t1 = time.perf_counter()
-        for _ in range(a.steps):
-            outs = model(x, margin=margin)
-        torch.cuda.synchronize(dev)
-        dt_copy = time.perf_counter() - t1
+        finite = bool(torch.isfinite(outs[0]).all())
+        if a.dump_outputs and rank == 0:
+            dump_outputs(outs, a.dump_outputs)
+        dt_copy = None
+        if a.full:
+            # the same loop fed from a tensor of the CALLER's (what script/Common.py:116-118 does every iteration): the engine copies
+            # the 106 MB clip tensor into its input buffer first - a device-to-device copy that `ms_per_step` (inputs resident in the
+            # engine's own buffers, OTPose.input_buffers) does not contain; reported beside it, never part of `value`
+            t1 = time.perf_counter()
+            for _ in range(a.steps):
+                outs = model(x, margin=margin)
+            torch.cuda.synchronize(dev)
+            dt_copy = time.perf_counter() - t1
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if dist is not None:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
-    finite = bool(torch.isfinite(outs[0]).all())
     # the same forward on the exact-fp32 MFMA kernels of round 1 (OTPOSE_CONV_MATH=f32), reported beside the headline so that
     # both arithmetic choices are on one line; 1 GPU only, never part of `value`
     exact = None
     math = os.environ.get("OTPOSE_CONV_MATH", "x3")
-    if world == 1 and math != "f32" and not a.no_exact_fp32:
+    if a.full and world == 1 and math != "f32" and not a.no_exact_fp32:
         os.environ["OTPOSE_CONV_MATH"] = "f32"
         hip.lib().otp_chan_attn_set_split(0)                    # the library-wide switch is read once at load time
         try:
@@ -737,7 +772,7 @@ def main():
             model.invalidate_engine()
     # the eager PyTorch-ROCm forward of the same graph, timed here (1 GPU, rank 0): the denominator of the 5x target
     eager = None
-    if world == 1 and not a.no_eager_baseline:
+    if a.full and world == 1 and not a.no_eager_baseline:
         try:
             eager = eager_baseline(model, cfg, x, margin, dev)
             log("eager PyTorch-ROCm baseline: %.1f ms per forward (warm-up incl. MIOpen search %.1f s)"
@@ -748,10 +783,10 @@ def main():
     # BASELINE configs[4] (extension: the reference has no 7-frame model): the same forward with a 7-frame window, batch 16 x 7 x
     # 384 x 288 - 12 x 17 = 204 stacked maps per temporal encoder; 1 GPU only, never part of `value`
     config5 = None
-    if world == 1 and not a.no_config5 and a.batch == 16:
+    if a.full and world == 1 and not a.no_config5 and a.batch == 16:
         config5 = config5_probe(dev, a.batch, a.steps)
     train = None
-    if not a.no_train_step:
+    if a.full and not a.no_train_step:
         del outs
         model._engine = None                                    # free the inference engine's buffers before the training probe
         torch.cuda.empty_cache()
@@ -766,7 +801,6 @@ def main():
             "metric": "frames/sec at 384x288, 5-frame window, batch 16; heatmap max-abs delta vs ref",
             "value": frames / dt, "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "ms_per_step_incl_input_copy": 1e3 * dt_copy / a.steps,
             # the arithmetic that was timed: every tensor, accumulator, normalisation and activation is fp32; the products of the
             # convolutions / projections / MLPs / attention are three f16 MFMA products of two-piece fp32 operands (IEEE-half pieces, 22 significand
             # bits per operand; the reference's fp32 is 24, its default TF32 convolutions on NVIDIA hardware 11).  Measured on the
@@ -788,38 +822,40 @@ def main():
             "roofline_forward": forward_roofline(FLOP_PER_CLIP * a.batch * fwd_per_s, math),
         }
         log("timed region done: %.2f ms/step" % (1e3 * dt / a.steps))
-        conv, dcn, mlp, attn, head = kernel_rooflines(dev, a.batch)
-        log("kernel rooflines done")
-        line["roofline"] = conv
-        line["roofline_dcn"] = dcn
-        if mlp is not None:
-            line["roofline_mlp"] = mlp
-        line["roofline_attn"] = attn
-        if head is not None:
-            line["roofline_warp_head"] = head
-        if exact is not None:
-            line["exact_fp32_kernels"] = exact
-        if config5 is not None:
-            line["config5"] = config5
-        if eager is None:
-            eager = eager_ratio_committed(a.batch)
-        if eager is not None:
-            ms = 1e3 * dt / a.steps
-            eager = dict(eager)
-            eager["target"] = 5.0
-            eager["speedup"] = eager["eager_forward_ms"] / ms                  # the headline arithmetic (`dtype` of this line)
-            eager["speedup_arithmetic"] = line["dtype"]
+        if a.full:
+            line["ms_per_step_incl_input_copy"] = 1e3 * dt_copy / a.steps
+            conv, dcn, mlp, attn, head = kernel_rooflines(dev, a.batch)
+            log("kernel rooflines done")
+            line["roofline"] = conv
+            line["roofline_dcn"] = dcn
+            if mlp is not None:
+                line["roofline_mlp"] = mlp
+            line["roofline_attn"] = attn
+            if head is not None:
+                line["roofline_warp_head"] = head
             if exact is not None:
-                eager["speedup_exact_fp32_kernels"] = eager["eager_forward_ms"] / exact["ms_per_step"]
-            line["vs_eager_rocm"] = eager
-        line["parity"] = golden_parity(model, cfg, dev)     # the "heatmap max-abs delta vs ref" half of the metric
-        log("golden parity done")
-        if train is not None:
-            line["train_step"] = train
-        if world == 1 and a.train_f32:
-            line["train_step_f32"] = train_step_probe(cfg, dev, a.batch, "f32")
-        if world == 1 and not a.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(a.batch)
+                line["exact_fp32_kernels"] = exact
+            if config5 is not None:
+                line["config5"] = config5
+            if eager is None:
+                eager = eager_ratio_committed(a.batch)
+            if eager is not None:
+                ms = 1e3 * dt / a.steps
+                eager = dict(eager)
+                eager["target"] = 5.0
+                eager["speedup"] = eager["eager_forward_ms"] / ms                  # the headline arithmetic (`dtype` of this line)
+                eager["speedup_arithmetic"] = line["dtype"]
+                if exact is not None:
+                    eager["speedup_exact_fp32_kernels"] = eager["eager_forward_ms"] / exact["ms_per_step"]
+                line["vs_eager_rocm"] = eager
+            line["parity"] = golden_parity(model, cfg, dev)     # the "heatmap max-abs delta vs ref" half of the metric
+            log("golden parity done")
+            if train is not None:
+                line["train_step"] = train
+            if world == 1 and a.train_f32:
+                line["train_step_f32"] = train_step_probe(cfg, dev, a.batch, "f32")
+            if world == 1 and not a.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(a.batch)
         print(json.dumps(line), file=json_out, flush=True)
     if dist is not None:
         dist.barrier()

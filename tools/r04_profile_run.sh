@@ -14,7 +14,7 @@ python tools/pmc_fold.py convs_kernel gpurun_out/${TAG}_convs_pmc1.csv gpurun_ou
 python tools/pmc_fold.py convs_kernel gpurun_out/${TAG}_convs_conv2_pmc1.csv gpurun_out/${TAG}_convs_conv2_pmc2.csv >> gpurun_out/${TAG}_convs_pmc_fold.txt
 python tools/pmc_fold.py convs2_kernel gpurun_out/${TAG}_convs2_pmc1.csv gpurun_out/${TAG}_convs2_pmc2.csv gpurun_out/${TAG}_convs2_pmc3.csv gpurun_out/${TAG}_convs2_pmc4.csv > gpurun_out/${TAG}_convs2_pmc_fold.txt
 bash tools/convs_timing.sh 80 48 48 96 72 > gpurun_out/${TAG}_convs_phase_stamps.txt 2>&1
-PROF_TIMELINE="glue_total" bash tools/prof.sh ${TAG}_bench bench.py --steps 10 --warmup 3 --no-exact-fp32 --no-train-step --no-cpu-baseline --no-config5 --no-eager-baseline
+PROF_TIMELINE="glue_total" bash tools/prof.sh ${TAG}_bench bench.py --full --steps 10 --warmup 3 --no-exact-fp32 --no-train-step --no-cpu-baseline --no-config5 --no-eager-baseline
 MIN_GAP=10 bash tools/trace_gaps.sh glue_total bench.py --steps 6 --warmup 3 --no-exact-fp32 --no-train-step --no-cpu-baseline --no-config5 --no-eager-baseline > gpurun_out/${TAG}_bench_gaps.txt 2>&1
 TAG=$TAG python3 - <<'PY'
 import csv, json, os

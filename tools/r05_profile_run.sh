@@ -14,5 +14,5 @@ for k in mlpx_kernel qkvx_front_kernel densex_cc_kernel; do
 done > gpurun_out/${TAG}_enc_pmc_fold.txt
 bash tools/pmc.sh ${TAG}_dcnf "$SQ1" "$SQ2" "$SQ3" "FETCH_SIZE" "WRITE_SIZE" -- tools/dcn_fused_bench.py
 python tools/pmc_fold.py dcn_fused_kernel gpurun_out/${TAG}_dcnf_pmc1.csv gpurun_out/${TAG}_dcnf_pmc2.csv gpurun_out/${TAG}_dcnf_pmc3.csv gpurun_out/${TAG}_dcnf_pmc4.csv gpurun_out/${TAG}_dcnf_pmc5.csv > gpurun_out/${TAG}_dcnf_pmc_fold.txt
-PROF_TIMELINE="glue_total" bash tools/prof.sh ${TAG}_bench bench.py --steps 10 --warmup 3 --no-exact-fp32 --no-train-step --no-cpu-baseline --no-config5 --no-eager-baseline
+PROF_TIMELINE="glue_total" bash tools/prof.sh ${TAG}_bench bench.py --full --steps 10 --warmup 3 --no-exact-fp32 --no-train-step --no-cpu-baseline --no-config5 --no-eager-baseline
 PROF_TIMELINE="adamw_kernel" bash tools/prof.sh ${TAG}_train tools/train_bench.py --dtype bf16 --steps 1 --free-run 6

@@ -596,6 +596,25 @@ int otp_adamw_step(void* param, const void* grad, void* exp_avg, void* exp_avg_s
 int otp_frames_u8_to_clip(const void* frames_u8, void* out, int B, int F, int H, int W, float mean_r, float mean_g,
                           float mean_b, float std_r, float std_g, float std_b, void* stream);
 
+/* ---- person crops from whole video frames (dataset/PoseTrackDataset.py:389-399 + the input assembly above) ----------
+ * pool_u8 (S, Hp, Wp, 3) uint8 RGB frames; frame_idx (B, F) int32 pool frame of window slot f of sample b; M (B, 2, 3)
+ * float64 forward crop matrix (image -> crop); flip (B) uint8 or NULL: read frame[:, ::-1] (mirrored over the pool width
+ * Wp).  out (B, 3F, H, W) float32: plane 3f + c = Normalize(ToTensor(cv2.warpAffine(frame, M, (W, H), INTER_LINEAR,
+ * BORDER_CONSTANT 0))) with the fixed-point arithmetic of OpenCV <= 4.10 (M inverted in double, 1/1024 px row origin +
+ * column delta rounded half-even, 1/32 px bilinear weights summing to 32768, (sum + 16384) >> 15) and the float32
+ * normalisation of otp_frames_u8_to_clip.  A frame_idx outside [0, S) reads as an all-border frame.  Hp, Wp <= 32767;
+ * OTP_ERR_UNSUPPORTED also for a zero std.  No allocation, no synchronisation. */
+int otp_crop_clips_u8(const void* pool_u8, int S, int Hp, int Wp, const void* frame_idx, const void* M, const void* flip,
+                      void* out, int B, int F, int H, int W, float mean_r, float mean_g, float mean_b, float std_r,
+                      float std_g, float std_b, void* stream);
+/* Training targets (PoseTrackDataset.py:403-420, utils/heatmap.py:48-105): joints (B, J, 2) float64 image coordinates,
+ * vis (B, J) float32 (joints_3d_vis[:, 0]), M (B, 2, 3) float64 as above, gauss the (2 sigma3 + 1)^2 float32 Gaussian
+ * patch (built on the host) -> target (B, J, h, w) float32, target_weight (B, J, 1) float32.  Joints with vis > 0 are
+ * moved by M; vis drops to 0 outside [0, W] x [0, H] or when the patch misses the heat-map; the patch is drawn where the
+ * weight is > 0.5. */
+int otp_pose_targets(const void* joints, const void* vis, const void* M, const void* gauss, void* target,
+                     void* target_weight, int B, int J, int W, int H, int w, int h, int sigma3, void* stream);
+
 /* ---- heatmap losses (model/loss.py) ------------------------------------------------------------- */
 /* ST_OHKW_MSELoss.forward (loss.py:25-92): s,t,g (B,J,HW), w (B,J); flags (J) int32 in/out: when
  * flags_given == 0 the kernel computes flags[j] = (max_b,p g[b,j,p] == 1) itself; result[0..2] =

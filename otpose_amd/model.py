@@ -86,6 +86,11 @@ class DeformableCONV(nn.Module):
         return self.deform_conv(x, offsets, mask)
 
 
+def _host(x):
+    """A tensor's values as a host numpy array (other array-likes pass through): the crop matrices are built on the host."""
+    return x.detach().cpu().numpy() if torch.is_tensor(x) else x
+
+
 def _plain_conv(cin, cout, dilation):
     return nn.Conv2d(cin, cout, 3, 1, padding=dilation, dilation=dilation, bias=False)
 
@@ -213,6 +218,40 @@ class OTPose(nn.Module):
         if self._engine is None or not self._engine.matches_shape(b, 3 * f, h, w, frames_u8.device):
             self._engine = self._engine_class()(self, b, frames_u8.device)
         return self._engine.run(frames_u8, margin, self.alias_outputs)
+
+    def forward_video(self, pool, frame_idx, center, scale, margin, rotation=None, flip=None):
+        """Forward from whole video frames: ``pool`` (S, Hp, Wp, 3) uint8 RGB frames on the GPU, ``frame_idx`` (B, F) the
+        pool frame of every window slot (F = ``window_frames``, slots in the order cur, prev, next, pprev, nnext - see
+        otpose_amd.crop.window), ``center`` / ``scale`` (B, 2) of each person (otpose_amd.crop.box_to_center_scale),
+        ``margin`` (B, F - 1), optional ``rotation`` degrees (scalar or (B,)) and ``flip`` (B) (the caller mirrors
+        ``center`` to ``Wp - 1 - x`` itself, as the reference's training flip does).  The crops (dataset/PoseTrackDataset.py:
+        386-406) are cut on the GPU: in eval straight into the engine's input buffer (no copy), in ``model.train()`` into a
+        fresh tensor for the training forward."""
+        from . import crop
+        w_img, h_img = self.cfg.MODEL.IMAGE_SIZE
+        fi = torch.as_tensor(frame_idx)
+        if fi.dim() != 2 or fi.shape[1] != self.window_frames:
+            raise ValueError(f"frame_idx must be (B, {self.window_frames})")
+        b = fi.shape[0]
+        M = crop.crop_matrix(_host(center), _host(scale), 0.0 if rotation is None else _host(rotation), (w_img, h_img))
+        margin = torch.as_tensor(margin, dtype=torch.float32).to(pool.device)
+        if self.training:
+            x = ops.crop_clips(pool, fi, M, flip, size=(w_img, h_img))
+            return self.forward(x, margin=margin)
+        x, _ = self.input_buffers(b, pool.device)
+        ops.crop_clips(pool, fi, M, flip, out=x)
+        return self.forward(x, margin=margin)
+
+    def predict(self, pool, frame_idx, center, scale, margin):
+        """Keypoints in source-image pixels for B persons: the eval :meth:`forward_video` (no rotation, no flip), then the
+        argmax + quarter-pixel refinement + inverse crop transform of ``ops.get_final_preds`` on the output heat-maps.
+        Returns ``(preds (B, J, 2), maxvals (B, J, 1))`` float32 device tensors."""
+        if self.training:
+            raise RuntimeError("OTPose.predict runs in eval mode (call model.eval())")
+        out = self.forward_video(pool, frame_idx, center, scale, margin)
+        c = torch.as_tensor(_host(center), dtype=torch.float32)
+        s = torch.as_tensor(_host(scale), dtype=torch.float32)
+        return ops.get_final_preds(out[0], c, s)
 
     def input_buffers(self, batch, device):
         """The eval engine's own input tensors for ``batch`` clips on ``device``: ``(x (B, 3 F, H, W) fp32, margin (B, F - 1)

@@ -1089,6 +1089,97 @@ def frames_to_clip(frames_u8, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
     return out
 
 
+def _host_or_device(x, dtype, device, name, shape):
+    """``x`` (numpy / list / tensor) as a contiguous ``dtype`` tensor on ``device`` of the given shape."""
+    t = torch.as_tensor(x)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if not t.is_cuda and dtype.is_floating_point and not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{name} has non-finite values")
+    return t.to(device=device, dtype=dtype).contiguous()
+
+
+def crop_clips(pool, frame_idx, M, flip=None, out=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, size=None):
+    """Person crops straight from whole frames: ``pool`` (S, Hp, Wp, 3) uint8 RGB on the GPU, ``frame_idx`` (B, F) pool
+    frame of each window slot, ``M`` (B, 2, 3) float64 forward crop matrices (otpose_amd.crop.crop_matrix), ``flip`` (B)
+    optional: mirror the frame first.  Returns the model input (B, 3F, H, W) float32: five cv2.warpAffine(INTER_LINEAR)
+    crops per sample (dataset/PoseTrackDataset.py:389-399, bit-identical fixed-point arithmetic) followed by the
+    ToTensor + Normalize + concat of :func:`frames_to_clip`, in one kernel.  ``out`` (written in place) or ``size`` =
+    (W, H) gives the crop size.  An index outside [0, S) reads as an empty frame (border value 0); host-side indices
+    must fit int32.  Frames of different sizes may share a pool zero-padded to (Hp, Wp): the crops are unchanged
+    (except under ``flip``, which mirrors the padded width)."""
+    _require_gpu(pool)
+    if pool.dtype != torch.uint8 or pool.dim() != 4 or pool.shape[-1] != 3:
+        raise TypeError("pool must be an (S, Hp, Wp, 3) uint8 tensor")
+    pool = pool.contiguous()
+    s, hp, wp, _ = pool.shape
+    dev = pool.device
+    fi = torch.as_tensor(frame_idx)
+    if fi.dim() != 2 or fi.dtype.is_floating_point or fi.dtype == torch.bool:
+        raise TypeError("frame_idx must be a (B, F) integer array")
+    b, f = fi.shape
+    if fi.dtype != torch.int32:
+        if not fi.is_cuda and fi.numel() and (int(fi.min()) < -2 ** 31 or int(fi.max()) >= 2 ** 31):
+            raise ValueError("frame_idx values must fit int32")
+        fi = fi.clamp(-1, s)                    # out-of-range stays out of range through the int32 cast
+    fi = fi.to(device=dev, dtype=torch.int32).contiguous()
+    M = _host_or_device(M, torch.float64, dev, "M", (b, 2, 3))
+    fl = None if flip is None else _host_or_device(flip, torch.bool, dev, "flip", (b,)).to(torch.uint8)
+    if out is None:
+        if size is None:
+            raise ValueError("crop_clips needs out= or size=(W, H)")
+        w, h = int(size[0]), int(size[1])
+        out = torch.empty((b, 3 * f, h, w), dtype=torch.float32, device=dev)
+    else:
+        if (out.dim() != 4 or out.shape[:2] != (b, 3 * f) or out.dtype != torch.float32 or not out.is_contiguous()
+                or out.device != dev):
+            raise ValueError("out must be a contiguous float32 (B, 3F, H, W) tensor on the pool's device")
+        h, w = out.shape[2:]
+        if size is not None and (int(size[0]), int(size[1])) != (w, h):
+            raise ValueError("size disagrees with out")
+    hip.check(hip.lib().otp_crop_clips_u8(hip.ptr(pool), s, hp, wp, hip.ptr(fi), hip.ptr(M), hip.ptr(fl), hip.ptr(out),
+                                          b, f, h, w, *[float(v) for v in mean], *[float(v) for v in std],
+                                          hip.stream_of(pool)), "otp_crop_clips_u8")
+    return out
+
+
+_GAUSS = {}            # (sigma, device) -> device copy of the host-built Gaussian patch
+
+
+def pose_targets(joints, vis, M, sigma, image_size, heatmap_size):
+    """Training targets of dataset/PoseTrackDataset.py:403-420 on the GPU: ``joints`` (B, J, 2 or 3) image coordinates,
+    ``vis`` (B, J) (or (B, J, 3): column 0 is used), ``M`` (B, 2, 3) the crop matrices of :func:`crop_clips`.  Visible
+    joints are moved into the crop, joints outside [0, W] x [0, H] lose their visibility, and generate_heatmaps
+    (utils/heatmap.py:48-105) draws the Gaussian patches.  Returns ``(target (B, J, h, w), target_weight (B, J, 1))``
+    float32; ``image_size`` = (W, H), ``heatmap_size`` = (w, h), ``sigma`` a whole number."""
+    from .crop import gaussian_table
+    j = torch.as_tensor(joints, dtype=torch.float64)
+    dev = j.device if j.is_cuda else torch.as_tensor(M).device
+    if dev.type != "cuda":
+        raise NotImplementedError("pose_targets runs on the GPU only: pass joints or M as a GPU tensor")
+    gaussian_table(sigma)                      # validates sigma
+    if j.dim() != 3 or j.shape[-1] not in (2, 3):
+        raise ValueError("joints must be (B, J, 2) or (B, J, 3)")
+    b, nj = j.shape[:2]
+    j = j[..., :2].to(dev).contiguous()
+    v = torch.as_tensor(vis)
+    v = (v[..., 0] if v.dim() == 3 else v).to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(v.shape) != (b, nj):
+        raise ValueError("vis must be (B, J) or (B, J, 3)")
+    M = _host_or_device(M, torch.float64, dev, "M", (b, 2, 3))
+    key = (int(sigma), dev)
+    if key not in _GAUSS:
+        _GAUSS[key] = torch.from_numpy(gaussian_table(sigma)).to(dev)
+    W, H = int(image_size[0]), int(image_size[1])
+    w, h = int(heatmap_size[0]), int(heatmap_size[1])
+    target = torch.empty((b, nj, h, w), dtype=torch.float32, device=dev)
+    weight = torch.empty((b, nj, 1), dtype=torch.float32, device=dev)
+    hip.check(hip.lib().otp_pose_targets(hip.ptr(j), hip.ptr(v), hip.ptr(M), hip.ptr(_GAUSS[key]), hip.ptr(target),
+                                         hip.ptr(weight), b, nj, W, H, w, h, 3 * int(sigma), hip.stream_of(target)),
+              "otp_pose_targets")
+    return target, weight
+
+
 def st_ohkw_loss(s, t, g, w, topk=8, flags=None, with_grad=False):
     """ST_OHKW_MSELoss forward (+ analytic gradients) on the GPU; returns dict like the reference
     (model/loss.py:89-91) plus ``flags`` and, when requested, ``grad_s`` / ``grad_t``."""

@@ -607,6 +607,19 @@ int otp_frames_u8_to_clip(const void* frames_u8, void* out, int B, int F, int H,
 int otp_crop_clips_u8(const void* pool_u8, int S, int Hp, int Wp, const void* frame_idx, const void* M, const void* flip,
                       void* out, int B, int F, int H, int W, float mean_r, float mean_g, float mean_b, float std_r,
                       float std_g, float std_b, void* stream);
+/* otp_crop_clips_u8 with the training blur (PoseTrackDataset.py:374-388) fused into the gather: blur (B, F, 9, 5) float32
+ * per-slot tables (torchvision 0.8 _get_gaussian_kernel2d((5, 9), [s, s]): row i weighs image column x + i - 4, column j
+ * the RGB channel c + j - 2), blur_on (B, F) uint8 or NULL (= every slot blurred).  A blurred slot reads every bilinear
+ * corner byte as the blurred value of that pixel: its row alone (rows never mix), 9 taps along the width reflected at the
+ * frame's left and right edges (-k -> k, Wp - 1 + k -> Wp - 1 - k) times 5 taps across the RGB axis reflected as
+ * [b,g,r,g,b,g,r]; acc = 0, for i in 0..8, for j in 0..4: acc = acc + w[i][j] * v in float32 with every product and sum
+ * rounded (no FMA), then round half to even and clamp to [0, 255].  Under flip the mirrored frame is blurred.  Every frame
+ * must have the pool's width Wp (the reflection is at column Wp - 1); Wp >= 5, else OTP_ERR_UNSUPPORTED.  Slots with
+ * blur_on 0 are bit-identical to otp_crop_clips_u8. */
+int otp_crop_clips_blur_u8(const void* pool_u8, int S, int Hp, int Wp, const void* frame_idx, const void* M,
+                           const void* flip, void* out, int B, int F, int H, int W, float mean_r, float mean_g,
+                           float mean_b, float std_r, float std_g, float std_b, const void* blur, const void* blur_on,
+                           void* stream);
 /* Training targets (PoseTrackDataset.py:403-420, utils/heatmap.py:48-105): joints (B, J, 2) float64 image coordinates,
  * vis (B, J) float32 (joints_3d_vis[:, 0]), M (B, 2, 3) float64 as above, gauss the (2 sigma3 + 1)^2 float32 Gaussian
  * patch (built on the host) -> target (B, J, h, w) float32, target_weight (B, J, 1) float32.  Joints with vis > 0 are

@@ -3,8 +3,10 @@
 //                       per person, with ToTensor + Normalize + the channel concat of frames_u8_kernel fused behind them;
 //   otp_pose_targets  - the joint transform, the visibility cut and generate_heatmaps of PoseTrackDataset.py:407-420 /
 //                       utils/heatmap.py:48-105.
-// Both restate integer / double arithmetic exactly (the contract is in include/otpose_hip.h), so their outputs are
-// bit-identical to the host restatement in tests/crop_ref.py.
+//   otp_crop_clips_blur_u8 - the same crops of frames first blurred per (sample, slot) as torchvision 0.8's
+//                       T.GaussianBlur((5, 9)) blurs an (H, W, 3) uint8 tensor (PoseTrackDataset.py:374-388).
+// They restate integer / double arithmetic exactly (the contract is in include/otpose_hip.h), so their outputs are
+// bit-identical to the host restatements in tests/crop_ref.py and tests/augment_ref.py.
 #include "common.h"
 
 namespace {
@@ -48,13 +50,100 @@ __device__ __forceinline__ uint64_t load_pair(const uint8_t* pool, size_t pool_b
     return v;
 }
 
+// The blurred bytes of the two pool columns cl, cl + 1 (memory order, as load_pair packs them) of one row that starts at
+// byte offset `row`, for a table `tab` (9 x 5 float32, row i = image column offset i - 4, column j = RGB offset j - 2).
+// torchvision 0.8 reads the (H, W, 3) frame as (C=H, H'=W, W'=3): every image row is blurred on its own, along the
+// width with reflection at the frame's left / right edges and across the RGB axis reflected as [b,g,r,g,b,g,r].  Under
+// `fl` the mirrored frame is blurred: the window is read right to left.  The 10 pixels (30 bytes) around the two
+// columns come from one dword-aligned 36-byte load where the window lies inside the row and the pool, else pixel by
+// pixel with the reflection (clamped for a corner outside the frame, whose value is dropped anyway).
+// Arithmetic (fixed, restated by tests/augment_ref.py): per output byte acc = 0; for i in 0..8, for j in 0..4:
+// acc = acc + tab[i][j] * px (float32, every product and sum rounded: no FMA); then rint (half to even), clamp [0, 255].
+__device__ __forceinline__ uint64_t blur_pair(const uint8_t* pool, size_t pool_bytes, long long row, int Wp, int cl,
+                                              bool fl, bool inL, bool inR, const float* __restrict__ tab) {
+#pragma clang fp contract(off)
+    if (!inL && !inR) return 0;
+    float px[10][3];
+    const uintptr_t base = reinterpret_cast<uintptr_t>(pool);
+    const long long off = row + (long long)(cl - 4) * 3;
+    const uintptr_t addr = base + (uintptr_t)off;
+    const uintptr_t a4 = addr & ~(uintptr_t)3;
+    if (cl - 4 >= 0 && cl + 5 <= Wp - 1 && a4 >= base && a4 + 36 <= base + pool_bytes) {
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(pool + (a4 - base));
+        uint32_t d[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) d[k] = q[k];
+        const uint32_t sh = (uint32_t)(addr - a4);
+        uint32_t e[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) e[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh);
+#pragma unroll
+        for (int t = 0; t < 10; ++t)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int n = 3 * t + c;
+                px[t][c] = (float)((e[n >> 2] >> (8 * (n & 3))) & 255u);
+            }
+    } else {
+#pragma unroll
+        for (int t = 0; t < 10; ++t) {
+            int col = cl - 4 + t;
+            col = col < 0 ? -col : col;
+            col = col > Wp - 1 ? 2 * (Wp - 1) - col : col;
+            col = col < 0 ? 0 : (col > Wp - 1 ? Wp - 1 : col);
+            const uint8_t* p = pool + row + (long long)col * 3;
+            px[t][0] = (float)p[0];
+            px[t][1] = (float)p[1];
+            px[t][2] = (float)p[2];
+        }
+    }
+    if (fl) {
+#pragma unroll
+        for (int t = 0; t < 5; ++t)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float v = px[t][c];
+                px[t][c] = px[9 - t][c];
+                px[9 - t][c] = v;
+            }
+    }
+    // a[c]: the column whose taps are px[i] (cl, or cl + 1 under flip); b[c]: px[i + 1]
+    float a[3] = {0.f, 0.f, 0.f}, bb[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 9; ++i)
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            const float w = tab[i * 5 + j];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int k = c + j - 2;
+                const int ch = k < 0 ? -k : (k > 2 ? 4 - k : k);
+                a[c] = a[c] + w * px[i][ch];
+                bb[c] = bb[c] + w * px[i + 1][ch];
+            }
+        }
+    uint64_t lo = 0, hi = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const uint64_t va = (uint32_t)fminf(fmaxf(__builtin_rintf(a[c]), 0.f), 255.f);
+        const uint64_t vb = (uint32_t)fminf(fmaxf(__builtin_rintf(bb[c]), 0.f), 255.f);
+        lo |= (fl ? vb : va) << (8 * c);
+        hi |= (fl ? va : vb) << (8 * c);
+    }
+    return (inL ? lo : 0) | (inR ? hi << 24 : 0);
+}
+
 // One thread per output pixel (b, y, x) of one sample: the fixed-point source position is the same for all F frames of
 // the sample, so it is computed once and the F gathers reuse it.  Writes: 3F coalesced float rows along x.
+// BLUR: slot (b, f) with blur_on[b, f] != 0 (or blur_on NULL) reads its corner bytes through blur_pair with the table
+// blur[b, f]; the other slots read the pool as the plain kernel does.
+template <bool BLUR>
 __global__ __launch_bounds__(256) void crop_clips_kernel(const uint8_t* __restrict__ pool, int S, int Hp, int Wp,
                                                          const int* __restrict__ frame_idx, const double* __restrict__ Ms,
                                                          const uint8_t* __restrict__ flip, float* __restrict__ out, int F,
                                                          int H, int W, float m0, float m1, float m2, float s0, float s1,
-                                                         float s2) {
+                                                         float s2, const float* __restrict__ blur,
+                                                         const uint8_t* __restrict__ blur_on) {
 #pragma clang fp contract(off)
     const int b = blockIdx.y;
     const int HW = H * W;
@@ -93,8 +182,16 @@ __global__ __launch_bounds__(256) void crop_clips_kernel(const uint8_t* __restri
         const int fi = frame_idx[(size_t)b * F + f];
         const bool fr = fi >= 0 && fi < S;
         const long long off0 = (((long long)fi * Hp + sy) * Wp + cl) * 3;
-        const uint64_t q0 = fr && in_r0 ? load_pair(pool, pool_bytes, off0, inL, inR) : 0;
-        const uint64_t q1 = fr && in_r1 ? load_pair(pool, pool_bytes, off0 + (long long)Wp * 3, inL, inR) : 0;
+        uint64_t q0, q1;
+        if (BLUR && (blur_on == nullptr || blur_on[(size_t)b * F + f] != 0)) {
+            const float* tab = blur + ((size_t)b * F + f) * 45;
+            const long long row0 = ((long long)fi * Hp + sy) * Wp * 3;
+            q0 = fr && in_r0 ? blur_pair(pool, pool_bytes, row0, Wp, cl, fl, inL, inR, tab) : 0;
+            q1 = fr && in_r1 ? blur_pair(pool, pool_bytes, row0 + (long long)Wp * 3, Wp, cl, fl, inL, inR, tab) : 0;
+        } else {
+            q0 = fr && in_r0 ? load_pair(pool, pool_bytes, off0, inL, inR) : 0;
+            q1 = fr && in_r1 ? load_pair(pool, pool_bytes, off0 + (long long)Wp * 3, inL, inR) : 0;
+        }
         float v[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -156,10 +253,28 @@ extern "C" int otp_crop_clips_u8(const void* pool_u8, int S, int Hp, int Wp, con
     if (Hp > 32767 || Wp > 32767 || std_r == 0.f || std_g == 0.f || std_b == 0.f) return OTP_ERR_UNSUPPORTED;
     if ((long long)H * W > INT32_MAX / 4 || B > 65535) return OTP_ERR_UNSUPPORTED;
     const unsigned blocks = (unsigned)otp_ceil_div(H * W, 256);
-    hipLaunchKernelGGL(crop_clips_kernel, dim3(blocks, B), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(crop_clips_kernel<false>, dim3(blocks, B), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint8_t*>(pool_u8), S, Hp, Wp, static_cast<const int*>(frame_idx),
                        static_cast<const double*>(M), static_cast<const uint8_t*>(flip), static_cast<float*>(out), F, H, W,
-                       mean_r, mean_g, mean_b, std_r, std_g, std_b);
+                       mean_r, mean_g, mean_b, std_r, std_g, std_b, nullptr, nullptr);
+    return otp_launch_status();
+}
+
+extern "C" int otp_crop_clips_blur_u8(const void* pool_u8, int S, int Hp, int Wp, const void* frame_idx, const void* M,
+                                      const void* flip, void* out, int B, int F, int H, int W, float mean_r, float mean_g,
+                                      float mean_b, float std_r, float std_g, float std_b, const void* blur,
+                                      const void* blur_on, void* stream) {
+    if (!pool_u8 || !frame_idx || !M || !out || !blur) return OTP_ERR_BAD_ARG;
+    if (S <= 0 || Hp <= 0 || Wp <= 0 || B <= 0 || F <= 0 || H <= 0 || W <= 0) return OTP_ERR_BAD_ARG;
+    if (Hp > 32767 || Wp > 32767 || std_r == 0.f || std_g == 0.f || std_b == 0.f) return OTP_ERR_UNSUPPORTED;
+    if ((long long)H * W > INT32_MAX / 4 || B > 65535) return OTP_ERR_UNSUPPORTED;
+    if (Wp < 5) return OTP_ERR_UNSUPPORTED;          // the width reflection by 4 needs 5 columns (as torch's reflect pad)
+    const unsigned blocks = (unsigned)otp_ceil_div(H * W, 256);
+    hipLaunchKernelGGL(crop_clips_kernel<true>, dim3(blocks, B), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint8_t*>(pool_u8), S, Hp, Wp, static_cast<const int*>(frame_idx),
+                       static_cast<const double*>(M), static_cast<const uint8_t*>(flip), static_cast<float*>(out), F, H, W,
+                       mean_r, mean_g, mean_b, std_r, std_g, std_b, static_cast<const float*>(blur),
+                       static_cast<const uint8_t*>(blur_on));
     return otp_launch_status();
 }
 

@@ -120,6 +120,8 @@ SIGNATURES = {
     "otp_pck_accuracy": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_float, c_void_p]),
     "otp_frames_u8_to_clip": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_float] * 6 + [c_void_p]),
     "otp_crop_clips_u8": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 4 + [c_int] * 4 + [c_float] * 6 + [c_void_p]),
+    "otp_crop_clips_blur_u8": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 4 + [c_int] * 4 + [c_float] * 6
+                               + [c_void_p] * 3),
     "otp_pose_targets": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),
     "otp_conv2d_wgrad_workspace": (c_size_t, [c_int] * 2),
     "otp_conv2d_wgrad": (c_int, [c_void_p] * 3 + [c_int] * 14 + [c_void_p, c_size_t, c_void_p]),

@@ -91,6 +91,17 @@ def _host(x):
     return x.detach().cpu().numpy() if torch.is_tensor(x) else x
 
 
+# TRAIN.* of the reference's PoseTrack18 config (configs/Base_PoseTrack18.yaml), for cfgs that do not set them
+_TRAIN_AUGMENT = {"SCALE_FACTOR": 0.35, "ROT_FACTOR": 45, "FLIP": True, "PROB_HALF_BODY": 0.3, "NUM_JOINTS_HALF_BODY": 8}
+
+
+def _train_augment_cfg(cfg):
+    """The keyword arguments of augment.sample_augmentation from ``cfg.TRAIN``."""
+    t = {k: cfg.get("TRAIN", {}).get(k, v) for k, v in _TRAIN_AUGMENT.items()}
+    return {"scale_factor": t["SCALE_FACTOR"], "rotation_factor": t["ROT_FACTOR"], "flip": bool(t["FLIP"]),
+            "prob_half_body": t["PROB_HALF_BODY"], "num_joints_half_body": t["NUM_JOINTS_HALF_BODY"]}
+
+
 def _plain_conv(cin, cout, dilation):
     return nn.Conv2d(cin, cout, 3, 1, padding=dilation, dilation=dilation, bias=False)
 
@@ -219,14 +230,15 @@ class OTPose(nn.Module):
             self._engine = self._engine_class()(self, b, frames_u8.device)
         return self._engine.run(frames_u8, margin, self.alias_outputs)
 
-    def forward_video(self, pool, frame_idx, center, scale, margin, rotation=None, flip=None):
+    def forward_video(self, pool, frame_idx, center, scale, margin, rotation=None, flip=None, blur=None):
         """Forward from whole video frames: ``pool`` (S, Hp, Wp, 3) uint8 RGB frames on the GPU, ``frame_idx`` (B, F) the
         pool frame of every window slot (F = ``window_frames``, slots in the order cur, prev, next, pprev, nnext - see
         otpose_amd.crop.window), ``center`` / ``scale`` (B, 2) of each person (otpose_amd.crop.box_to_center_scale),
         ``margin`` (B, F - 1), optional ``rotation`` degrees (scalar or (B,)) and ``flip`` (B) (the caller mirrors
-        ``center`` to ``Wp - 1 - x`` itself, as the reference's training flip does).  The crops (dataset/PoseTrackDataset.py:
-        386-406) are cut on the GPU: in eval straight into the engine's input buffer (no copy), in ``model.train()`` into a
-        fresh tensor for the training forward."""
+        ``center`` to ``Wp - 1 - x`` itself, as the reference's training flip does), optional ``blur``: the training blur as
+        (B, F, 9, 5) tables (every slot blurred) or a ``(tables, blur_on)`` pair (otpose_amd.augment.Augmentation.
+        blur_tables).  The crops (dataset/PoseTrackDataset.py:386-406) are cut on the GPU: in eval straight into the
+        engine's input buffer (no copy), in ``model.train()`` into a fresh tensor for the training forward."""
         from . import crop
         w_img, h_img = self.cfg.MODEL.IMAGE_SIZE
         fi = torch.as_tensor(frame_idx)
@@ -235,12 +247,50 @@ class OTPose(nn.Module):
         b = fi.shape[0]
         M = crop.crop_matrix(_host(center), _host(scale), 0.0 if rotation is None else _host(rotation), (w_img, h_img))
         margin = torch.as_tensor(margin, dtype=torch.float32).to(pool.device)
+        tab, on = blur if isinstance(blur, (tuple, list)) else (blur, None)
         if self.training:
-            x = ops.crop_clips(pool, fi, M, flip, size=(w_img, h_img))
+            x = ops.crop_clips(pool, fi, M, flip, size=(w_img, h_img), blur=tab, blur_on=on)
             return self.forward(x, margin=margin)
         x, _ = self.input_buffers(b, pool.device)
-        ops.crop_clips(pool, fi, M, flip, out=x)
+        ops.crop_clips(pool, fi, M, flip, out=x, blur=tab, blur_on=on)
         return self.forward(x, margin=margin)
+
+    def training_batch(self, pool, frame_idx, margin, joints, joints_vis, center, scale, augment=None):
+        """One augmented training batch from whole video frames - the training branch of the reference's
+        ``_get_spatio_temporal_window`` (dataset/PoseTrackDataset.py:343-420) for B persons at once.
+
+        ``pool`` (S, Hp, Wp, 3) uint8 RGB frames on the GPU, ``frame_idx`` (B, F) and ``margin`` (B, F - 1) as for
+        :meth:`forward_video`, ``joints`` / ``joints_vis`` (B, J, 3) and ``center`` / ``scale`` (B, 2) of the data items.
+        ``augment``: an :class:`otpose_amd.augment.Augmentation`, or None to draw one with
+        :func:`otpose_amd.augment.sample_augmentation` (the global ``np.random`` / ``random`` / ``torch`` generators, as
+        the reference) from ``cfg.TRAIN`` (SCALE_FACTOR, ROT_FACTOR, FLIP, PROB_HALF_BODY, NUM_JOINTS_HALF_BODY; the
+        PoseTrack18 values where absent).  The crops are cut with the flip and the blur on the GPU, and the targets drawn
+        from the flipped joints (``cfg.MODEL.SIGMA``, 3 where absent).  The flip and the blur mirror and reflect at the
+        pool's width, so every frame of the pool must be Wp wide (not a narrower frame zero-padded into it).
+
+        Returns ``(x (B, 3F, H, W), margin (B, F - 1), target (B, J, h, w), target_weight (B, J, 1))`` float32 on the
+        pool's device, the arguments of ``parallel.train_step_dp`` / ``train.forward_train`` + ``train.criterion``."""
+        from . import augment as A
+        from . import crop
+        m = self.cfg.MODEL
+        w_img, h_img = m.IMAGE_SIZE
+        fi = torch.as_tensor(frame_idx)
+        if fi.dim() != 2 or fi.shape[1] != self.window_frames:
+            raise ValueError(f"frame_idx must be (B, {self.window_frames})")
+        if augment is None:
+            t = _train_augment_cfg(self.cfg)
+            augment = A.sample_augmentation(_host(joints), _host(joints_vis), _host(center), _host(scale),
+                                            int(pool.shape[2]), aspect_ratio=w_img * 1.0 / h_img,
+                                            frames=self.window_frames, **t)
+        if augment.blur_sigma.shape != tuple(fi.shape):
+            raise ValueError(f"augment is for {augment.blur_sigma.shape} slots, frame_idx is {tuple(fi.shape)}")
+        M = crop.crop_matrix(augment.center, augment.scale, augment.rotation, (w_img, h_img))
+        tab, on = augment.blur_tables()
+        x = ops.crop_clips(pool, fi, M, augment.flip, size=(w_img, h_img), blur=tab, blur_on=on)
+        target, weight = ops.pose_targets(augment.joints, augment.joints_vis, torch.from_numpy(M).to(pool.device),
+                                          int(m.get("SIGMA", 3)), (w_img, h_img), m.HEATMAP_SIZE)
+        margin = torch.as_tensor(margin, dtype=torch.float32).to(pool.device)
+        return x, margin, target, weight
 
     def predict(self, pool, frame_idx, center, scale, margin):
         """Keypoints in source-image pixels for B persons: the eval :meth:`forward_video` (no rotation, no flip), then the

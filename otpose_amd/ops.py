@@ -1099,7 +1099,8 @@ def _host_or_device(x, dtype, device, name, shape):
     return t.to(device=device, dtype=dtype).contiguous()
 
 
-def crop_clips(pool, frame_idx, M, flip=None, out=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, size=None):
+def crop_clips(pool, frame_idx, M, flip=None, out=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, size=None, blur=None,
+               blur_on=None):
     """Person crops straight from whole frames: ``pool`` (S, Hp, Wp, 3) uint8 RGB on the GPU, ``frame_idx`` (B, F) pool
     frame of each window slot, ``M`` (B, 2, 3) float64 forward crop matrices (otpose_amd.crop.crop_matrix), ``flip`` (B)
     optional: mirror the frame first.  Returns the model input (B, 3F, H, W) float32: five cv2.warpAffine(INTER_LINEAR)
@@ -1107,7 +1108,13 @@ def crop_clips(pool, frame_idx, M, flip=None, out=None, mean=IMAGENET_MEAN, std=
     ToTensor + Normalize + concat of :func:`frames_to_clip`, in one kernel.  ``out`` (written in place) or ``size`` =
     (W, H) gives the crop size.  An index outside [0, S) reads as an empty frame (border value 0); host-side indices
     must fit int32.  Frames of different sizes may share a pool zero-padded to (Hp, Wp): the crops are unchanged
-    (except under ``flip``, which mirrors the padded width)."""
+    (except under ``flip``, which mirrors the padded width).
+
+    ``blur`` (B, F, 9, 5) float32 (otpose_amd.augment.blur_table per slot) blurs each slot's frame first, as the
+    reference's training T.GaussianBlur((5, 9)) does (9 taps along the width, 5 across RGB, rows never mixed; see
+    include/otpose_hip.h for the arithmetic); ``blur_on`` (B, F) optional selects the blurred slots (default: all).
+    The blur reflects at column Wp - 1, so every frame of the pool must have the pool's width (a zero-padded narrower
+    frame would be blurred with its padding), and Wp >= 5.  ``blur=None`` takes the plain kernel."""
     _require_gpu(pool)
     if pool.dtype != torch.uint8 or pool.dim() != 4 or pool.shape[-1] != 3:
         raise TypeError("pool must be an (S, Hp, Wp, 3) uint8 tensor")
@@ -1137,9 +1144,21 @@ def crop_clips(pool, frame_idx, M, flip=None, out=None, mean=IMAGENET_MEAN, std=
         h, w = out.shape[2:]
         if size is not None and (int(size[0]), int(size[1])) != (w, h):
             raise ValueError("size disagrees with out")
-    hip.check(hip.lib().otp_crop_clips_u8(hip.ptr(pool), s, hp, wp, hip.ptr(fi), hip.ptr(M), hip.ptr(fl), hip.ptr(out),
-                                          b, f, h, w, *[float(v) for v in mean], *[float(v) for v in std],
-                                          hip.stream_of(pool)), "otp_crop_clips_u8")
+    if blur is None:
+        if blur_on is not None:
+            raise ValueError("blur_on needs blur")
+        hip.check(hip.lib().otp_crop_clips_u8(hip.ptr(pool), s, hp, wp, hip.ptr(fi), hip.ptr(M), hip.ptr(fl),
+                                              hip.ptr(out), b, f, h, w, *[float(v) for v in mean],
+                                              *[float(v) for v in std], hip.stream_of(pool)), "otp_crop_clips_u8")
+        return out
+    if wp < 5:
+        raise ValueError(f"the blur needs frames at least 5 pixels wide, got {wp}")
+    bt = _host_or_device(blur, torch.float32, dev, "blur", (b, f, 9, 5))
+    on = None if blur_on is None else _host_or_device(blur_on, torch.bool, dev, "blur_on", (b, f)).to(torch.uint8)
+    hip.check(hip.lib().otp_crop_clips_blur_u8(hip.ptr(pool), s, hp, wp, hip.ptr(fi), hip.ptr(M), hip.ptr(fl),
+                                               hip.ptr(out), b, f, h, w, *[float(v) for v in mean],
+                                               *[float(v) for v in std], hip.ptr(bt), hip.ptr(on),
+                                               hip.stream_of(pool)), "otp_crop_clips_blur_u8")
     return out
 
 

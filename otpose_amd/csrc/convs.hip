@@ -359,6 +359,10 @@ template <int NM, int NR>
 __device__ __forceinline__ void sblock_sched() {
     if constexpr (NR == 0) {
         __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
+    } else if constexpr (NR == 1) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, NM - 2, 0);
     } else if constexpr (NR >= NM - 1) {
 #pragma unroll
         for (int g = 0; g < NM - 1; ++g) {
@@ -376,6 +380,18 @@ __device__ __forceinline__ void sblock_sched() {
     }
 }
 
+// the same for a read count known only after unrolling (the branches fold)
+template <int NM>
+__device__ __forceinline__ void sblock_sched_n(int nr) {
+    if (nr == 0) sblock_sched<NM, 0>();
+    else if (nr == 1) sblock_sched<NM, 1>();
+    else if (nr == 2) sblock_sched<NM, 2>();
+    else if (nr == 1 + 2 * 2) sblock_sched<NM, 1 + 2 * 2>();
+    else if (nr == 2 + 2 * 2) sblock_sched<NM, 2 + 2 * 2>();
+    else if (nr == 1 + 2 * 3) sblock_sched<NM, 1 + 2 * 3>();
+    else sblock_sched<NM, 2 + 2 * 3>();
+}
+
 // residual / fp32 output layouts of otp_conv3x3_s8
 enum { S_F32_NONE = 0, S_F32_C4 = 1, S_F32_NCHW = 2 };
 
@@ -388,7 +404,7 @@ __global__ __launch_bounds__(256, NCHW ? 2 : 3) void convs_kernel(const unsigned
     constexpr int BM = 64 * NPT;
     constexpr int WCH = swch(NTW);                                 // 1 KB pieces of a chunk's weights
     constexpr int WBYTES = WCH * 1024;
-    constexpr int NBLK = SKS * NPT;                                // (k-step, pixel tile) blocks of a chunk: 3 NTW MFMAs each
+    constexpr int NBLK = SKS * NPT;                                // (k-step, pixel tile) blocks of a chunk: 3 NTW MFMAs each, 2 NTW at s = 4
     constexpr int NM = 3 * NTW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int PL = P.pl;                                           // bytes between the planes of the window (no padding: three
@@ -484,6 +500,7 @@ __global__ __launch_bounds__(256, NCHW ? 2 : 3) void convs_kernel(const unsigned
             const int dy = tap / 3, dx = tap - dy * 3;
             toff[s] = (dy * P.W1 + dx - x0) * 16 + (q & 1) * (2 * PL);
         }
+        if (upper) toff[SKS - 1] += PL;                            // last k-step: lanes kl = 2, 3 read the lo part of k-slots 16, 17
         f32x4 sh[NTW];
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
@@ -565,9 +582,13 @@ __global__ __launch_bounds__(256, NCHW ? 2 : 3) void convs_kernel(const unsigned
         }
     }
 
-    // One chunk: NBLK blocks of 3 NTW MFMAs.  B fragments are read two blocks ahead (ring of three), the weight fragments of
+    // One chunk: NBLK blocks of 3 NTW MFMAs (2 NTW in the last k-step).  B fragments are read two blocks ahead (ring of three), the weight fragments of
     // the next k-step two blocks before it starts, the reads spread between the MFMAs (tools/micro/mfma_loop.hip: 16.8 cycles
     // per MFMA for one wave per SIMD, against 20.8 with reads one block ahead, clustered, and addresses computed in the loop).
+    // The last k-step holds k-slots 16, 17 only (tap 8; lanes kl = 0, 1).  Its three half products go into two MFMAs of full
+    // depth: lanes 0 .. 31 multiply lo weights by hi data and lanes 32 .. 63 hi weights by lo data (toff: the upper lanes' B
+    // read is the lo part of the same k-slots), then hi * hi on lanes 0 .. 31 against zero weights above.  One B read per pixel
+    // tile, 2 NTW MFMAs per block: 14 MFMAs per chunk and cout tile instead of 15.
     auto mfma_phase = [&]() __attribute__((always_inline)) {
         h16x8 ah[2][NTW], al[2][NTW], bh[3], bl[3];
         auto load_a = [&](int buf, int s) __attribute__((always_inline)) {
@@ -578,20 +599,20 @@ __global__ __launch_bounds__(256, NCHW ? 2 : 3) void convs_kernel(const unsigned
                     ah[buf][t] = *reinterpret_cast<const h16x8*>(a);
                     al[buf][t] = *reinterpret_cast<const h16x8*>(a + 1024);
                 } else {
-                    // last k-step: k-slots 16, 17 (tap 8) on the lanes kl = 0, 1; kl = 2, 3 (tap 9) multiply zeros - their half of
-                    // the fragment is not stored (512-byte half pieces behind the full ones)
-                    const unsigned char* a = wl + (SKS - 1) * NTW * 2048 + t * 1024 + (lane & 31) * 16;
-                    const h16x8 h = *reinterpret_cast<const h16x8*>(a), l = *reinterpret_cast<const h16x8*>(a + 512);
+                    // the 512-byte half pieces [hi, lo] of k-slots 16, 17: al = [lo | hi] (lanes 0 .. 31 | 32 .. 63) for the merged
+                    // MFMA - the 1 KB read with the halves swapped - and ah = [hi | 0] for the hi * hi one
+                    const unsigned char* a = wl + (SKS - 1) * NTW * 2048 + t * 1024;
+                    const h16x8 h = *reinterpret_cast<const h16x8*>(a + (lane & 31) * 16);
                     const h16x8 z = __builtin_bit_cast(h16x8, (u32x4){0u, 0u, 0u, 0u});
+                    al[buf][t] = *reinterpret_cast<const h16x8*>(a + (lane ^ 32) * 16);
                     ah[buf][t] = upper ? z : h;
-                    al[buf][t] = upper ? z : l;
                 }
             }
         };
         auto load_b = [&](int buf, int blk) __attribute__((always_inline)) {
             const unsigned char* b = win + (pb[blk % NPT] + toff[blk / NPT]);
             bh[buf] = *reinterpret_cast<const h16x8*>(b);
-            bl[buf] = *reinterpret_cast<const h16x8*>(b + PL);
+            if (blk / NPT < SKS - 1) bl[buf] = *reinterpret_cast<const h16x8*>(b + PL);
         };
         load_a(0, 0);
         load_b(0, 0);
@@ -602,15 +623,23 @@ __global__ __launch_bounds__(256, NCHW ? 2 : 3) void convs_kernel(const unsigned
             const bool nb = blk + 2 < NBLK, na = p == NPT - 2 && s + 1 < SKS;
             if (nb) load_b((blk + 2) % 3, blk + 2);
             if (na) load_a(sa ^ 1, s + 1);
+            const int nr = (nb ? ((blk + 2) / NPT < SKS - 1 ? 2 : 1) : 0) + (na ? 2 * NTW : 0);   // LDS reads of this block
+            if (s < SKS - 1) {
 #pragma unroll
-            for (int t = 0; t < NTW; ++t) {
-                acc[t][p] = OTP_X3_MFMA(al[sa][t], bh[cur], acc[t][p], 0, 0, 0);
-                acc[t][p] = OTP_X3_MFMA(ah[sa][t], bl[cur], acc[t][p], 0, 0, 0);
-                acc[t][p] = OTP_X3_MFMA(ah[sa][t], bh[cur], acc[t][p], 0, 0, 0);
+                for (int t = 0; t < NTW; ++t) {
+                    acc[t][p] = OTP_X3_MFMA(al[sa][t], bh[cur], acc[t][p], 0, 0, 0);
+                    acc[t][p] = OTP_X3_MFMA(ah[sa][t], bl[cur], acc[t][p], 0, 0, 0);
+                    acc[t][p] = OTP_X3_MFMA(ah[sa][t], bh[cur], acc[t][p], 0, 0, 0);
+                }
+                sblock_sched_n<NM>(nr);
+            } else {
+#pragma unroll
+                for (int t = 0; t < NTW; ++t) {
+                    acc[t][p] = OTP_X3_MFMA(al[sa][t], bh[cur], acc[t][p], 0, 0, 0);
+                    acc[t][p] = OTP_X3_MFMA(ah[sa][t], bh[cur], acc[t][p], 0, 0, 0);
+                }
+                sblock_sched_n<2 * NTW>(nr);
             }
-            if (!nb) sblock_sched<NM, 0>();
-            else if (na) sblock_sched<NM, 2 + 2 * NTW>();
-            else sblock_sched<NM, 2>();
             __builtin_amdgcn_sched_barrier(0);
         }
     };

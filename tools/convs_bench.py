@@ -1,5 +1,6 @@
 """S8 / LDS-DMA 3x3 convolution (csrc/convs.hip) next to the fp32-input split kernel (csrc/convx.hip): time per launch of the
-two BasicBlock convs (conv1: S8 -> S8; conv2: S8 + fp32 residual -> fp32 + S8, or fp32 only) and of the S8 converter.
+two BasicBlock convs (conv1: S8 -> S8; conv2: S8 + fp32 residual -> fp32 + S8, or fp32 only; the forward's conv2 form: S8 + S8
+residual -> S8) and of the S8 converter.
 usage: python tools/convs_bench.py [--reps 20]"""
 import sys
 import torch
@@ -30,7 +31,7 @@ def desc(n, ci, co, h, w):
 def main():
     reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 20
     torch.manual_seed(0)
-    print(f"{'shape':26s} {'convx':>7s} {'convx+r':>8s} | {'s8->s8':>7s} {'+r->nchw':>8s} {'+r->c4+s8':>10s} {'pack':>6s}  us;  block: convx / s8 (us)")
+    print(f"{'shape':26s} {'convx':>7s} {'convx+r':>8s} | {'s8->s8':>7s} {'+r->nchw':>8s} {'+r->c4+s8':>10s} {'+r8->s8':>8s} {'pack':>6s}  us;  block: convx / s8 (us)")
     for n, ci, co, h, w in SHAPES:
         x = torch.randn(n, ci, h, w, device="cuda")
         wt = torch.randn(co, ci, 3, 3, device="cuda") * (2.0 / (ci * 9)) ** 0.5
@@ -55,9 +56,12 @@ def main():
         ta = timed(lambda: ops.conv3x3_s8_launch(xs, ws, sh, ds, None, None, ops.S8_F32_C4, ys), reps)
         tb = timed(lambda: ops.conv3x3_s8_launch(xs, ws, sh, ds, rc4, y, ops.S8_F32_NCHW, None), reps)
         tc = timed(lambda: ops.conv3x3_s8_launch(xs, ws, sh, ds, rc4, oc4, ops.S8_F32_C4, ys), reps)
+        ds8 = desc(n, ci, co, h, w)
+        ds8.res_layout = 1                                           # residual = the block input's S8 records (ci == co)
+        td = timed(lambda: ops.conv3x3_s8_launch(xs, ws, sh, ds8, xs, None, ops.S8_F32_C4, ys), reps) if ci == co else float("nan")
         tp = timed(lambda: ops.s8_pack(x, xs, rc4), reps)
         fl = 2.0 * n * co * ci * 9 * h * w
-        print(f"{n:3d}x{ci:3d}->{co:3d} {h:3d}x{w:<3d}   {tx0:7.1f} {tx1:8.1f} | {ta:7.1f} {tb:8.1f} {tc:10.1f} {tp:6.1f}"
+        print(f"{n:3d}x{ci:3d}->{co:3d} {h:3d}x{w:<3d}   {tx0:7.1f} {tx1:8.1f} | {ta:7.1f} {tb:8.1f} {tc:10.1f} {td:8.1f} {tp:6.1f}"
               f"      {tx0 + tx1:6.1f} / {ta + tc:6.1f}   ({fl / tc * 1e-6:5.0f} TF algorithmic on s8+r->f+s)")
 
 

@@ -568,6 +568,22 @@ int otp_axpby(const void* x, void* y, float alpha, float beta, size_t n, void* s
 int otp_heatmap_decode(const void* heatmaps, void* preds, void* maxvals, const void* center, const void* scale,
                        int N, int J, int H, int W, int refine, void* stream);
 
+/* ---- flip test (HRNet's validate with TEST.FLIP_TEST / TEST.SHIFT_HEATMAP, configs/default.py:169-195) ---------------
+ * heatmaps (2B, J, H, W) float32: outputs[0] of one forward over [x_0 .. x_{B-1}, mirror(x_0) .. mirror(x_{B-1})]; perm a
+ * HOST int32 (J) array, the involution of the left/right flip pairs (unpaired joints map to themselves; J <= 256), checked
+ * on the host (OTP_ERR_BAD_ARG otherwise) and passed by value.  For b < B:
+ *   F[b, j, y, x]      = hm[B + b, perm[j], y, W - 1 - x]                               (flip_back)
+ *   S[b, j, y, x]      = shift && x >= 1 ? F[b, j, y, x - 1] : F[b, j, y, x]            (output_flipped[..., 1:] = [..., :-1])
+ *   merged[b, j, y, x] = (hm[b, j, y, x] + S[b, j, y, x]) * 0.5f                       (one float32 add, one multiply; no FMA)
+ * merged (B, J, H, W) must not overlap heatmaps.  preds (B, J, 2) / maxvals (B, J) are otp_heatmap_decode(merged, refine = 1)
+ * with the same rules (first maximum, first NaN, maxvals > 0 mask, strict refinement bounds, center / scale (B, 2) both or
+ * neither); the refinement's neighbours are recomputed from heatmaps.  One launch, one wave per (b, j) plane. */
+int otp_heatmap_flip_decode(const void* heatmaps, const int* perm, void* merged, void* preds, void* maxvals,
+                            const void* center, const void* scale, int B, int J, int H, int W, int shift, void* stream);
+/* out (2B, C, H, W) float32 = [x; x[..., ::-1]] for x (B, C, H, W) float32: the flip-test twin batch of clips that are
+ * already normalised (script/Common.py:348-354 mirrors the input tensor).  2 B C H W < 2^31, else OTP_ERR_UNSUPPORTED. */
+int otp_clip_mirror_pair(const void* x, void* out, int B, int C, int H, int W, void* stream);
+
 /* PCK accuracy of the training / validation loops (utils/evaluate.py:384-415 accuracy, :352-381 calc_dists / dist_acc;
  * called per iteration at script/Common.py:147-150) from the otp_heatmap_decode(refine = 0) coordinates (N,J,2) of the
  * predicted and target heat-maps of size H x W: acc (J+1) float32 = [mean over joints with a valid sample, per-joint
@@ -620,6 +636,11 @@ int otp_crop_clips_blur_u8(const void* pool_u8, int S, int Hp, int Wp, const voi
                            const void* flip, void* out, int B, int F, int H, int W, float mean_r, float mean_g,
                            float mean_b, float std_r, float std_g, float std_b, const void* blur, const void* blur_on,
                            void* stream);
+/* otp_crop_clips_u8 without flip, for the flip test: out (2B, 3F, H, W) float32, out[b] the crop of sample b and out[B + b]
+ * its exact column mirror (out[B + b][..., x] = out[b][..., W - 1 - x]); every value is computed once and stored twice. */
+int otp_crop_clips_pair_u8(const void* pool_u8, int S, int Hp, int Wp, const void* frame_idx, const void* M, void* out,
+                           int B, int F, int H, int W, float mean_r, float mean_g, float mean_b, float std_r, float std_g,
+                           float std_b, void* stream);
 /* Training targets (PoseTrackDataset.py:403-420, utils/heatmap.py:48-105): joints (B, J, 2) float64 image coordinates,
  * vis (B, J) float32 (joints_3d_vis[:, 0]), M (B, 2, 3) float64 as above, gauss the (2 sigma3 + 1)^2 float32 Gaussian
  * patch (built on the host) -> target (B, J, h, w) float32, target_weight (B, J, 1) float32.  Joints with vis > 0 are

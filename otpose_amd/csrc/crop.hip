@@ -5,6 +5,7 @@
 //                       utils/heatmap.py:48-105.
 //   otp_crop_clips_blur_u8 - the same crops of frames first blurred per (sample, slot) as torchvision 0.8's
 //                       T.GaussianBlur((5, 9)) blurs an (H, W, 3) uint8 tensor (PoseTrackDataset.py:374-388).
+//   otp_crop_clips_pair_u8 - the plain crops and their exact column mirrors (the flip-test twin batch) in one pass.
 // They restate integer / double arithmetic exactly (the contract is in include/otpose_hip.h), so their outputs are
 // bit-identical to the host restatements in tests/crop_ref.py and tests/augment_ref.py.
 #include "common.h"
@@ -137,7 +138,9 @@ __device__ __forceinline__ uint64_t blur_pair(const uint8_t* pool, size_t pool_b
 // the sample, so it is computed once and the F gathers reuse it.  Writes: 3F coalesced float rows along x.
 // BLUR: slot (b, f) with blur_on[b, f] != 0 (or blur_on NULL) reads its corner bytes through blur_pair with the table
 // blur[b, f]; the other slots read the pool as the plain kernel does.
-template <bool BLUR>
+// PAIR: no flip; every value of sample b (of gridDim.y) is also stored at column W - 1 - x of sample gridDim.y + b, so the
+// position work and the gathers of the mirrored twin are shared (the second store stream runs right to left per wave).
+template <bool BLUR, bool PAIR>
 __global__ __launch_bounds__(256) void crop_clips_kernel(const uint8_t* __restrict__ pool, int S, int Hp, int Wp,
                                                          const int* __restrict__ frame_idx, const double* __restrict__ Ms,
                                                          const uint8_t* __restrict__ flip, float* __restrict__ out, int F,
@@ -170,7 +173,7 @@ __global__ __launch_bounds__(256) void crop_clips_kernel(const uint8_t* __restri
 
     // remapBilinear, BORDER_CONSTANT 0: a corner outside the frame contributes nothing.  In memory the two columns
     // of a corner row are cl, cl + 1; flip reads column Wp - 1 - c, which swaps them.
-    const bool fl = flip != nullptr && flip[b] != 0;
+    const bool fl = !PAIR && flip != nullptr && flip[b] != 0;
     const int cl = fl ? Wp - 2 - sx : sx;
     const bool inL = cl >= 0 && cl < Wp, inR = cl + 1 >= 0 && cl + 1 < Wp;
     const bool in_r0 = sy >= 0 && sy < Hp, in_r1 = sy + 1 >= 0 && sy + 1 < Hp;
@@ -178,6 +181,7 @@ __global__ __launch_bounds__(256) void crop_clips_kernel(const uint8_t* __restri
     const size_t pool_bytes = (size_t)S * Hp * Wp * 3;
 
     float* o = out + (size_t)b * 3 * F * HW + p;
+    float* om = PAIR ? out + (size_t)(gridDim.y + b) * 3 * F * HW + (size_t)y * W + (W - 1 - x) : nullptr;
     for (int f = 0; f < F; ++f) {
         const int fi = frame_idx[(size_t)b * F + f];
         const bool fr = fi >= 0 && fi < S;
@@ -204,6 +208,12 @@ __global__ __launch_bounds__(256) void crop_clips_kernel(const uint8_t* __restri
         o[(size_t)HW] = (v[1] / 255.f - m1) / s1;
         o[(size_t)2 * HW] = (v[2] / 255.f - m2) / s2;
         o += (size_t)3 * HW;
+        if (PAIR) {                                           // (the same expressions: computed once)
+            om[0] = (v[0] / 255.f - m0) / s0;
+            om[(size_t)HW] = (v[1] / 255.f - m1) / s1;
+            om[(size_t)2 * HW] = (v[2] / 255.f - m2) / s2;
+            om += (size_t)3 * HW;
+        }
     }
 }
 
@@ -253,7 +263,7 @@ extern "C" int otp_crop_clips_u8(const void* pool_u8, int S, int Hp, int Wp, con
     if (Hp > 32767 || Wp > 32767 || std_r == 0.f || std_g == 0.f || std_b == 0.f) return OTP_ERR_UNSUPPORTED;
     if ((long long)H * W > INT32_MAX / 4 || B > 65535) return OTP_ERR_UNSUPPORTED;
     const unsigned blocks = (unsigned)otp_ceil_div(H * W, 256);
-    hipLaunchKernelGGL(crop_clips_kernel<false>, dim3(blocks, B), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL((crop_clips_kernel<false, false>), dim3(blocks, B), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint8_t*>(pool_u8), S, Hp, Wp, static_cast<const int*>(frame_idx),
                        static_cast<const double*>(M), static_cast<const uint8_t*>(flip), static_cast<float*>(out), F, H, W,
                        mean_r, mean_g, mean_b, std_r, std_g, std_b, nullptr, nullptr);
@@ -270,11 +280,26 @@ extern "C" int otp_crop_clips_blur_u8(const void* pool_u8, int S, int Hp, int Wp
     if ((long long)H * W > INT32_MAX / 4 || B > 65535) return OTP_ERR_UNSUPPORTED;
     if (Wp < 5) return OTP_ERR_UNSUPPORTED;          // the width reflection by 4 needs 5 columns (as torch's reflect pad)
     const unsigned blocks = (unsigned)otp_ceil_div(H * W, 256);
-    hipLaunchKernelGGL(crop_clips_kernel<true>, dim3(blocks, B), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL((crop_clips_kernel<true, false>), dim3(blocks, B), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint8_t*>(pool_u8), S, Hp, Wp, static_cast<const int*>(frame_idx),
                        static_cast<const double*>(M), static_cast<const uint8_t*>(flip), static_cast<float*>(out), F, H, W,
                        mean_r, mean_g, mean_b, std_r, std_g, std_b, static_cast<const float*>(blur),
                        static_cast<const uint8_t*>(blur_on));
+    return otp_launch_status();
+}
+
+extern "C" int otp_crop_clips_pair_u8(const void* pool_u8, int S, int Hp, int Wp, const void* frame_idx, const void* M,
+                                      void* out, int B, int F, int H, int W, float mean_r, float mean_g, float mean_b,
+                                      float std_r, float std_g, float std_b, void* stream) {
+    if (!pool_u8 || !frame_idx || !M || !out) return OTP_ERR_BAD_ARG;
+    if (S <= 0 || Hp <= 0 || Wp <= 0 || B <= 0 || F <= 0 || H <= 0 || W <= 0) return OTP_ERR_BAD_ARG;
+    if (Hp > 32767 || Wp > 32767 || std_r == 0.f || std_g == 0.f || std_b == 0.f) return OTP_ERR_UNSUPPORTED;
+    if ((long long)H * W > INT32_MAX / 4 || B > 65535) return OTP_ERR_UNSUPPORTED;
+    const unsigned blocks = (unsigned)otp_ceil_div(H * W, 256);
+    hipLaunchKernelGGL((crop_clips_kernel<false, true>), dim3(blocks, B), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint8_t*>(pool_u8), S, Hp, Wp, static_cast<const int*>(frame_idx),
+                       static_cast<const double*>(M), nullptr, static_cast<float*>(out), F, H, W, mean_r, mean_g, mean_b,
+                       std_r, std_g, std_b, nullptr, nullptr);
     return otp_launch_status();
 }
 

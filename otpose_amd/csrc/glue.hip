@@ -115,6 +115,44 @@ __device__ __forceinline__ bool better(float v, int i, float bv, int bi) {
     return v > bv || (v == bv && i < bi);
 }
 
+// (value, index) of the first maximum / first NaN of a wave's lane-partial pairs, in every lane
+__device__ __forceinline__ void wave_argmax(float& bv, int& bi) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || better(ov, oi, bv, bi))) { bv = ov; bi = oi; }
+    }
+}
+
+// get_final_preds of one plane from its argmax (bv, bi): the mask, the +-0.25 refinement on the plane's values at(y, x)
+// and the rot = 0 inverse crop transform of sample n; writes pred[0..1] and *maxval
+template <class At>
+__device__ __forceinline__ void decode_point(float bv, int bi, At at, int H, int W, int refine, const float* center,
+                                             const float* scale, int n, float* pred, float* maxval) {
+    const float m = bv > 0.f ? 1.f : 0.f;                      // pred_mask = maxvals > 0 (NaN -> 0)
+    float x = (float)(bi % W) * m, y = (float)(bi / W) * m;     // idx % width, floor(idx / width)
+    if (refine) {
+        const int px = (int)floorf(x + 0.5f), py = (int)floorf(y + 0.5f);
+        if (1 < px && px < W - 1 && 1 < py && py < H - 1) {      // the reference's strict bounds (heatmap.py:120)
+            const float dx = at(py, px + 1) - at(py, px - 1);
+            const float dy = at(py + 1, px) - at(py - 1, px);
+            x += dx > 0.f ? 0.25f : (dx < 0.f ? -0.25f : 0.f);    // np.sign(diff) * .25
+            y += dy > 0.f ? 0.25f : (dy < 0.f ? -0.25f : 0.f);
+        }
+    }
+    if (center && scale) {
+        // transform_preds with rot = 0: cv2.getAffineTransform of the three points of get_affine_transform(inv=1)
+        // (utils/transform.py:76-105) is the similarity  src = center + (dst - (W/2, H/2)) * (200 * scale_x / W)
+        const float k = 200.f * scale[2 * n] / (float)W;
+        x = center[2 * n] + (x - 0.5f * (float)W) * k;
+        y = center[2 * n + 1] + (y - 0.5f * (float)H) * k;
+    }
+    pred[0] = x;
+    pred[1] = y;
+    *maxval = bv;
+}
+
 __global__ __launch_bounds__(256) void heatmap_decode_kernel(const float* __restrict__ hm, float* __restrict__ preds,
                                                               float* __restrict__ maxvals, const float* __restrict__ center,
                                                               const float* __restrict__ scale, int NJ, int J, int H, int W,
@@ -129,36 +167,75 @@ __global__ __launch_bounds__(256) void heatmap_decode_kernel(const float* __rest
         const float v = p[i];
         if (bi == 0x7fffffff || better(v, i, bv, bi)) { bv = v; bi = i; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || better(ov, oi, bv, bi))) { bv = ov; bi = oi; }
+    wave_argmax(bv, bi);
+    if (lane == 0)
+        decode_point(bv, bi, [&](int y, int x) { return p[y * W + x]; }, H, W, refine, center, scale, plane / J,
+                     preds + 2 * plane, maxvals + plane);
+}
+
+// ---- flip test: HRNet's flip_back + optional one-column shift + average, fused with the decode above ---------------------
+// hm (2B, J, H, W): rows [0, B) the plain, rows [B, 2B) the mirrored clips' maps.  merged[b, j, y, x] = (hm[b, j, y, x] +
+// hm[B + b, perm[j], y, W - 1 - xs]) * 0.5f with xs = x - 1 if shift and x >= 1 else x; one wave per (b, j) plane writes
+// the merged plane and carries its argmax; the refinement's neighbours are recomputed from hm (merged is never read).
+constexpr int kFlipMaxJ = 256;
+struct FlipPerm {
+    int p[kFlipMaxJ];
+};
+
+__device__ __forceinline__ float flip_merged(const float* a, const float* f, int y, int x, int W, int shift) {
+#pragma clang fp contract(off)
+    const int xs = shift && x >= 1 ? x - 1 : x;
+    return (a[y * W + x] + f[y * W + (W - 1 - xs)]) * 0.5f;
+}
+
+__global__ __launch_bounds__(256) void heatmap_flip_decode_kernel(const float* __restrict__ hm, FlipPerm perm,
+                                                                   float* __restrict__ merged, float* __restrict__ preds,
+                                                                   float* __restrict__ maxvals,
+                                                                   const float* __restrict__ center,
+                                                                   const float* __restrict__ scale, int B, int J, int H,
+                                                                   int W, int shift) {
+    const int lane = threadIdx.x & 63;
+    const int plane = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (plane >= B * J) return;
+    const int HW = H * W, b = plane / J, j = plane - b * J;
+    const float* a = hm + (size_t)plane * HW;
+    const float* f = hm + ((size_t)(B + b) * J + perm.p[j]) * HW;
+    float* m = merged + (size_t)plane * HW;
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = lane; i < HW; i += 64) {
+        const int y = i / W;
+        const float v = flip_merged(a, f, y, i - y * W, W, shift);
+        m[i] = v;
+        if (bi == 0x7fffffff || better(v, i, bv, bi)) { bv = v; bi = i; }
     }
-    if (lane == 0) {
-        const float m = bv > 0.f ? 1.f : 0.f;                      // pred_mask = maxvals > 0 (NaN -> 0)
-        float x = (float)(bi % W) * m, y = (float)(bi / W) * m;     // idx % width, floor(idx / width)
-        if (refine) {
-            const int px = (int)floorf(x + 0.5f), py = (int)floorf(y + 0.5f);
-            if (1 < px && px < W - 1 && 1 < py && py < H - 1) {      // the reference's strict bounds (heatmap.py:120)
-                const float dx = p[py * W + px + 1] - p[py * W + px - 1];
-                const float dy = p[(py + 1) * W + px] - p[(py - 1) * W + px];
-                x += dx > 0.f ? 0.25f : (dx < 0.f ? -0.25f : 0.f);    // np.sign(diff) * .25
-                y += dy > 0.f ? 0.25f : (dy < 0.f ? -0.25f : 0.f);
-            }
-        }
-        if (center && scale) {
-            // transform_preds with rot = 0: cv2.getAffineTransform of the three points of get_affine_transform(inv=1)
-            // (utils/transform.py:76-105) is the similarity  src = center + (dst - (W/2, H/2)) * (200 * scale_x / W)
-            const int n = plane / J;
-            const float k = 200.f * scale[2 * n] / (float)W;
-            x = center[2 * n] + (x - 0.5f * (float)W) * k;
-            y = center[2 * n + 1] + (y - 0.5f * (float)H) * k;
-        }
-        preds[2 * plane] = x;
-        preds[2 * plane + 1] = y;
-        maxvals[plane] = bv;
-    }
+    wave_argmax(bv, bi);
+    if (lane == 0)
+        decode_point(bv, bi, [&](int y, int x) { return flip_merged(a, f, y, x, W, shift); }, H, W, 1, center, scale, b,
+                     preds + 2 * plane, maxvals + plane);
+}
+
+// ---- mirror pair of a clip tensor: out[:B] = x, out[B:] = x[..., ::-1] (the flip-test twin batch of normalised clips) ----
+// One float4 per thread: read once, stored straight and, reversed, at the mirrored column group of the same row.
+__global__ __launch_bounds__(256) void mirror_pair_kernel(const otp_f32x4* __restrict__ x, otp_f32x4* __restrict__ out,
+                                                           int W4, int total4) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total4) return;
+    const int row = i / W4, q = i - row * W4;
+    const otp_f32x4 v = x[i];
+    out[i] = v;
+    out[(size_t)total4 + (size_t)row * W4 + (W4 - 1 - q)] = (otp_f32x4){v.w, v.z, v.y, v.x};
+}
+
+// the same one float per thread (W % 4 != 0 or unaligned tensors)
+__global__ __launch_bounds__(256) void mirror_pair_scalar_kernel(const float* __restrict__ x, float* __restrict__ out, int W,
+                                                                  int total) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int row = i / W, c = i - row * W;
+    const float v = x[i];
+    out[i] = v;
+    out[(size_t)total + (size_t)row * W + (W - 1 - c)] = v;
 }
 
 // ---- nearest-upsample accumulate: out = act(res + up_f(low)) (HRNet fuse layers, model/HRNet.py:426-439,488-494) --------
@@ -464,6 +541,43 @@ extern "C" int otp_heatmap_decode(const void* heatmaps, void* preds, void* maxva
     hipLaunchKernelGGL(heatmap_decode_kernel, dim3(otp_ceil_div(NJ, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const float*>(heatmaps), static_cast<float*>(preds), static_cast<float*>(maxvals),
                        static_cast<const float*>(center), static_cast<const float*>(scale), NJ, J, H, W, refine);
+    return otp_launch_status();
+}
+
+extern "C" int otp_heatmap_flip_decode(const void* heatmaps, const int* perm, void* merged, void* preds, void* maxvals,
+                                       const void* center, const void* scale, int B, int J, int H, int W, int shift,
+                                       void* stream) {
+    if (!heatmaps || !perm || !merged || !preds || !maxvals || B <= 0 || J <= 0 || H <= 0 || W <= 0) return OTP_ERR_BAD_ARG;
+    if ((center == nullptr) != (scale == nullptr)) return OTP_ERR_BAD_ARG;
+    if (J > kFlipMaxJ || (long long)H * W > INT32_MAX || (long long)2 * B * J > INT32_MAX) return OTP_ERR_UNSUPPORTED;
+    FlipPerm P;
+    for (int j = 0; j < J; ++j) {                      // an int32 involution of [0, J): the flip pairs swapped, the rest fixed
+        const int k = perm[j];
+        if (k < 0 || k >= J || perm[k] != j) return OTP_ERR_BAD_ARG;
+        P.p[j] = k;
+    }
+    for (int j = J; j < kFlipMaxJ; ++j) P.p[j] = 0;
+    hipLaunchKernelGGL(heatmap_flip_decode_kernel, dim3(otp_ceil_div(B * J, 4)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), static_cast<const float*>(heatmaps), P, static_cast<float*>(merged),
+                       static_cast<float*>(preds), static_cast<float*>(maxvals), static_cast<const float*>(center),
+                       static_cast<const float*>(scale), B, J, H, W, shift ? 1 : 0);
+    return otp_launch_status();
+}
+
+extern "C" int otp_clip_mirror_pair(const void* x, void* out, int B, int C, int H, int W, void* stream) {
+    if (!x || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0) return OTP_ERR_BAD_ARG;
+    const long long total = (long long)B * C * H * W;
+    if (2 * total > INT32_MAX) return OTP_ERR_UNSUPPORTED;
+    const bool vec = W % 4 == 0 && !((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15);
+    if (vec) {
+        const int total4 = (int)(total / 4);
+        hipLaunchKernelGGL(mirror_pair_kernel, dim3(otp_ceil_div(total4, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                           static_cast<const otp_f32x4*>(x), static_cast<otp_f32x4*>(out), W / 4, total4);
+    } else {
+        hipLaunchKernelGGL(mirror_pair_scalar_kernel, dim3(otp_ceil_div((int)total, 256)), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), static_cast<const float*>(x), static_cast<float*>(out), W,
+                           (int)total);
+    }
     return otp_launch_status();
 }
 

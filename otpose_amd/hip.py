@@ -122,6 +122,7 @@ SIGNATURES = {
     "otp_crop_clips_u8": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 4 + [c_int] * 4 + [c_float] * 6 + [c_void_p]),
     "otp_crop_clips_blur_u8": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 4 + [c_int] * 4 + [c_float] * 6
                                + [c_void_p] * 3),
+    "otp_crop_clips_pair_u8": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_int] * 4 + [c_float] * 6 + [c_void_p]),
     "otp_pose_targets": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),
     "otp_conv2d_wgrad_workspace": (c_size_t, [c_int] * 2),
     "otp_conv2d_wgrad": (c_int, [c_void_p] * 3 + [c_int] * 14 + [c_void_p, c_size_t, c_void_p]),
@@ -209,6 +210,8 @@ SIGNATURES = {
     "otp_upsample_add_backward": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
     "otp_axpby": (c_int, [c_void_p, c_void_p, c_float, c_float, c_size_t, c_void_p]),
     "otp_heatmap_decode": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
+    "otp_heatmap_flip_decode": (c_int, [c_void_p] * 7 + [c_int] * 5 + [c_void_p]),
+    "otp_clip_mirror_pair": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_void_p]),
     "otp_loss_workspace": (c_size_t, [c_int, c_int]),
     "otp_loss_st_ohkw_grads": (c_int, [c_void_p] * 9 + [c_void_p, c_size_t] + [c_int] * 5 + [c_void_p]),
     "otp_loss_st_ohkw": (c_int, [c_void_p] * 8 + [c_void_p, c_size_t] + [c_int] * 5 + [c_void_p]),

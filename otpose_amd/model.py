@@ -292,16 +292,59 @@ class OTPose(nn.Module):
         margin = torch.as_tensor(margin, dtype=torch.float32).to(pool.device)
         return x, margin, target, weight
 
-    def predict(self, pool, frame_idx, center, scale, margin):
+    def predict(self, pool, frame_idx, center, scale, margin, flip_test=False, shift_heatmap=False):
         """Keypoints in source-image pixels for B persons: the eval :meth:`forward_video` (no rotation, no flip), then the
         argmax + quarter-pixel refinement + inverse crop transform of ``ops.get_final_preds`` on the output heat-maps.
-        Returns ``(preds (B, J, 2), maxvals (B, J, 1))`` float32 device tensors."""
+        Returns ``(preds (B, J, 2), maxvals (B, J, 1))`` float32 device tensors.
+
+        ``flip_test=True`` is HRNet's flip test (the reference's ``TEST.FLIP_TEST``; ``shift_heatmap`` its
+        ``TEST.SHIFT_HEATMAP``): the crops and their column mirrors are cut as one 2B batch straight into the engine's
+        input buffer, one forward runs with the margins repeated, and ``ops.flip_test_merge`` flips the mirrored maps
+        back, swaps ``augment.FLIP_PAIRS``, averages and decodes in one kernel.  The engine is built for 2B clips, so
+        alternating flip and plain calls rebuilds it each time."""
         if self.training:
             raise RuntimeError("OTPose.predict runs in eval mode (call model.eval())")
-        out = self.forward_video(pool, frame_idx, center, scale, margin)
         c = torch.as_tensor(_host(center), dtype=torch.float32)
         s = torch.as_tensor(_host(scale), dtype=torch.float32)
-        return ops.get_final_preds(out[0], c, s)
+        if not flip_test:
+            out = self.forward_video(pool, frame_idx, center, scale, margin)
+            return ops.get_final_preds(out[0], c, s)
+        from . import crop
+        w_img, h_img = self.cfg.MODEL.IMAGE_SIZE
+        fi = torch.as_tensor(frame_idx)
+        if fi.dim() != 2 or fi.shape[1] != self.window_frames:
+            raise ValueError(f"frame_idx must be (B, {self.window_frames})")
+        b = fi.shape[0]
+        M = crop.crop_matrix(_host(center), _host(scale), 0.0, (w_img, h_img))
+        x, mg = self.input_buffers(2 * b, pool.device)
+        ops.crop_clips(pool, fi, M, out=x, mirror_pair=True)
+        _, preds, maxvals = self._flip_forward(x, mg, margin, shift_heatmap, c, s)
+        return preds, maxvals
+
+    def flip_test_heatmaps(self, x, margin, shift_heatmap=False):
+        """The flip-test heat-maps of normalised clips ``x`` (B, 3F, H, W) on the GPU with ``margin`` (B, F - 1): ``x`` and
+        its mirror ``x.flip(3)`` go through one 2B forward (``ops.mirror_pair`` writes both into the engine's input
+        buffer), and the merged (B, J, h, w) maps of ``ops.flip_test_merge`` come back - what HRNet's ``validate`` feeds
+        to ``get_final_preds`` under ``TEST.FLIP_TEST`` (``shift_heatmap``: ``TEST.SHIFT_HEATMAP``)."""
+        if self.training:
+            raise RuntimeError("OTPose.flip_test_heatmaps runs in eval mode (call model.eval())")
+        if x.dim() != 4:
+            raise ValueError("x must be a (B, 3F, H, W) clip tensor")
+        xin, mg = self.input_buffers(2 * x.shape[0], x.device)
+        ops.mirror_pair(x, out=xin)
+        return self._flip_forward(xin, mg, margin, shift_heatmap)[0]
+
+    def _flip_forward(self, x2, mg2, margin, shift_heatmap, center=None, scale=None):
+        """One eval forward of the engine's own 2B input ``x2`` with the B margins repeated into ``mg2``, then the fused
+        flip-back merge + decode of its heat-maps."""
+        b = x2.shape[0] // 2
+        margin = torch.as_tensor(margin, dtype=torch.float32).to(x2.device)
+        if tuple(margin.shape) != (b, mg2.shape[1]):
+            raise ValueError(f"margin must be ({b}, {mg2.shape[1]})")
+        mg2[:b].copy_(margin)
+        mg2[b:].copy_(margin)
+        out = self._engine.run(x2, mg2, alias_outputs=True)
+        return ops.flip_test_merge(out[0], shift_heatmap=shift_heatmap, center=center, scale=scale)
 
     def input_buffers(self, batch, device):
         """The eval engine's own input tensors for ``batch`` clips on ``device``: ``(x (B, 3 F, H, W) fp32, margin (B, F - 1)

@@ -17,6 +17,7 @@ import torch
 from torch.autograd import Function
 
 from . import hip
+from .augment import FLIP_PAIRS
 
 _DTYPE_F32 = 0
 
@@ -1049,6 +1050,81 @@ def _decode(hm, center, scale, refine):
     return preds, maxvals
 
 
+def flip_permutation(pairs, num_joints):
+    """The involution of the left/right ``pairs`` over ``num_joints`` joints as an int32 numpy array (unpaired joints map
+    to themselves) - what HRNet's ``flip_back`` swaps.  Host only; raises ``ValueError`` for a joint outside
+    [0, num_joints) or one that appears twice (the pairs would not be an involution)."""
+    import numpy as np
+    j = int(num_joints)
+    if j <= 0:
+        raise ValueError("num_joints must be positive")
+    perm = np.arange(j, dtype=np.int32)
+    seen = set()
+    for pair in pairs:
+        if len(pair) != 2:
+            raise ValueError(f"flip pair {pair!r} is not a pair")
+        a, b = (int(v) for v in pair)
+        for v in (a, b):
+            if not 0 <= v < j:
+                raise ValueError(f"flip pair {pair!r}: joint {v} outside [0, {j})")
+            if v in seen:
+                raise ValueError(f"flip pairs: joint {v} appears twice (not an involution)")
+            seen.add(v)
+        perm[a], perm[b] = b, a
+    return perm
+
+
+def flip_test_merge(hm_pair, flip_pairs=FLIP_PAIRS, shift_heatmap=False, center=None, scale=None):
+    """Flip test of HRNet's ``validate`` (TEST.FLIP_TEST / TEST.SHIFT_HEATMAP) in one kernel: ``hm_pair`` (2B, J, H, W)
+    float32 are the heat-maps of one forward over the plain clips ``[:B]`` and their mirrors ``[B:]`` (:func:`mirror_pair`,
+    ``crop_clips(mirror_pair=True)``).  The mirrored maps are flipped back with the left/right joints of ``flip_pairs``
+    (``augment.FLIP_PAIRS``: PoseTrack's 17 joints) swapped, shifted one column right under ``shift_heatmap``, and averaged with the plain
+    maps as ``(a + b) * 0.5`` in float32; ``get_final_preds`` of the result comes out of the same pass.  Returns
+    ``(merged (B, J, H, W), preds (B, J, 2), maxvals (B, J, 1))``; ``center`` / ``scale`` (B, 2) as for
+    :func:`get_final_preds`."""
+    _require_gpu(hm_pair)
+    _check_f32(hm_pair)
+    if hm_pair.dim() != 4 or hm_pair.shape[0] % 2:
+        raise ValueError("hm_pair must be a (2B, J, H, W) tensor")
+    hm_pair = hm_pair.contiguous()
+    n2, j, h, w = hm_pair.shape
+    n = n2 // 2
+    perm = flip_permutation(flip_pairs, j)
+    merged = torch.empty((n, j, h, w), dtype=torch.float32, device=hm_pair.device)
+    preds = torch.empty((n, j, 2), dtype=torch.float32, device=hm_pair.device)
+    maxvals = torch.empty((n, j, 1), dtype=torch.float32, device=hm_pair.device)
+    c = s_ = None
+    if (center is None) != (scale is None):
+        raise ValueError("center and scale go together")
+    if center is not None:
+        c = torch.as_tensor(center, dtype=torch.float32, device=hm_pair.device).reshape(n, 2).contiguous()
+        s_ = torch.as_tensor(scale, dtype=torch.float32, device=hm_pair.device).reshape(n, 2).contiguous()
+    hip.check(hip.lib().otp_heatmap_flip_decode(hip.ptr(hm_pair), perm.ctypes.data_as(ctypes.c_void_p), hip.ptr(merged),
+                                                hip.ptr(preds), hip.ptr(maxvals), hip.ptr(c), hip.ptr(s_), n, j, h, w,
+                                                int(bool(shift_heatmap)), hip.stream_of(hm_pair)),
+              "otp_heatmap_flip_decode")
+    return merged, preds, maxvals
+
+
+def mirror_pair(x, out=None):
+    """The flip-test twin batch of clips that are already normalised: ``x`` (B, C, H, W) float32 -> (2B, C, H, W) with
+    ``[:B] = x`` and ``[B:] = x.flip(3)`` (script/Common.py:348-354), one streaming kernel.  ``out`` is written in place."""
+    _require_gpu(x)
+    _check_f32(x)
+    if x.dim() != 4:
+        raise ValueError("x must be a (B, C, H, W) tensor")
+    x = x.contiguous()
+    b, c, h, w = x.shape
+    if out is None:
+        out = torch.empty((2 * b, c, h, w), dtype=torch.float32, device=x.device)
+    elif (tuple(out.shape) != (2 * b, c, h, w) or out.dtype != torch.float32 or not out.is_contiguous()
+          or out.device != x.device):
+        raise ValueError("out must be a contiguous float32 (2B, C, H, W) tensor on x's device")
+    hip.check(hip.lib().otp_clip_mirror_pair(hip.ptr(x), hip.ptr(out), b, c, h, w, hip.stream_of(x)),
+              "otp_clip_mirror_pair")
+    return out
+
+
 def accuracy(output, target, hm_type="gaussian", thr=0.5):
     """Device form of reference utils/evaluate.py:384-415 (called per iteration at script/Common.py:147-150 on heat-maps
     copied to the host): PCK of the argmax of ``output`` against the argmax of ``target``.  Returns
@@ -1100,7 +1176,7 @@ def _host_or_device(x, dtype, device, name, shape):
 
 
 def crop_clips(pool, frame_idx, M, flip=None, out=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, size=None, blur=None,
-               blur_on=None):
+               blur_on=None, mirror_pair=False):
     """Person crops straight from whole frames: ``pool`` (S, Hp, Wp, 3) uint8 RGB on the GPU, ``frame_idx`` (B, F) pool
     frame of each window slot, ``M`` (B, 2, 3) float64 forward crop matrices (otpose_amd.crop.crop_matrix), ``flip`` (B)
     optional: mirror the frame first.  Returns the model input (B, 3F, H, W) float32: five cv2.warpAffine(INTER_LINEAR)
@@ -1114,7 +1190,11 @@ def crop_clips(pool, frame_idx, M, flip=None, out=None, mean=IMAGENET_MEAN, std=
     reference's training T.GaussianBlur((5, 9)) does (9 taps along the width, 5 across RGB, rows never mixed; see
     include/otpose_hip.h for the arithmetic); ``blur_on`` (B, F) optional selects the blurred slots (default: all).
     The blur reflects at column Wp - 1, so every frame of the pool must have the pool's width (a zero-padded narrower
-    frame would be blurred with its padding), and Wp >= 5.  ``blur=None`` takes the plain kernel."""
+    frame would be blurred with its padding), and Wp >= 5.  ``blur=None`` takes the plain kernel.
+
+    ``mirror_pair=True`` cuts the flip-test twin batch: (2B, 3F, H, W) with the plain crops in ``[:B]`` and their exact
+    column mirrors in ``[B:]`` (the mirrored network input, ``torch.flip(out[:B], [3])``), from one gather per value.
+    It takes no ``flip`` and no ``blur``."""
     _require_gpu(pool)
     if pool.dtype != torch.uint8 or pool.dim() != 4 or pool.shape[-1] != 3:
         raise TypeError("pool must be an (S, Hp, Wp, 3) uint8 tensor")
@@ -1131,19 +1211,28 @@ def crop_clips(pool, frame_idx, M, flip=None, out=None, mean=IMAGENET_MEAN, std=
         fi = fi.clamp(-1, s)                    # out-of-range stays out of range through the int32 cast
     fi = fi.to(device=dev, dtype=torch.int32).contiguous()
     M = _host_or_device(M, torch.float64, dev, "M", (b, 2, 3))
+    if mirror_pair and (flip is not None or blur is not None or blur_on is not None):
+        raise ValueError("mirror_pair takes no flip and no blur")
     fl = None if flip is None else _host_or_device(flip, torch.bool, dev, "flip", (b,)).to(torch.uint8)
+    nb = 2 * b if mirror_pair else b
     if out is None:
         if size is None:
             raise ValueError("crop_clips needs out= or size=(W, H)")
         w, h = int(size[0]), int(size[1])
-        out = torch.empty((b, 3 * f, h, w), dtype=torch.float32, device=dev)
+        out = torch.empty((nb, 3 * f, h, w), dtype=torch.float32, device=dev)
     else:
-        if (out.dim() != 4 or out.shape[:2] != (b, 3 * f) or out.dtype != torch.float32 or not out.is_contiguous()
+        if (out.dim() != 4 or out.shape[:2] != (nb, 3 * f) or out.dtype != torch.float32 or not out.is_contiguous()
                 or out.device != dev):
-            raise ValueError("out must be a contiguous float32 (B, 3F, H, W) tensor on the pool's device")
+            what = "(2B, 3F, H, W)" if mirror_pair else "(B, 3F, H, W)"
+            raise ValueError(f"out must be a contiguous float32 {what} tensor on the pool's device")
         h, w = out.shape[2:]
         if size is not None and (int(size[0]), int(size[1])) != (w, h):
             raise ValueError("size disagrees with out")
+    if mirror_pair:
+        hip.check(hip.lib().otp_crop_clips_pair_u8(hip.ptr(pool), s, hp, wp, hip.ptr(fi), hip.ptr(M), hip.ptr(out), b, f,
+                                                   h, w, *[float(v) for v in mean], *[float(v) for v in std],
+                                                   hip.stream_of(pool)), "otp_crop_clips_pair_u8")
+        return out
     if blur is None:
         if blur_on is not None:
             raise ValueError("blur_on needs blur")

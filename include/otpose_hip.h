@@ -778,6 +778,34 @@ int otp_gelu_dropout_bf16_forward(const void* x, void* y, void* keep_bits, size_
 int otp_gelu_dropout_bf16_backward(const void* x, const void* grad_y, const void* keep_bits, void* grad_x, size_t n, float p,
                                    void* stream);
 
+/* ---- PoseTrack / poseval pose evaluation (utils/evaluate.py: the AP at PCKh 0.5 the reference reports after every
+ * validation epoch), float64, deterministic (no float atomics, every sum in a fixed order) ----------------------------
+ * otp_pose_assign: removeIgnoredPoints (utils/evaluate.py:22-67) + assignGTmulti (:467-682) for F ground-truth frames in
+ * one launch, one workgroup per frame.  CSR-packed int32 offsets: pr_off (F+1) the predicted persons of each frame,
+ * pr_sample (NP) their index into preds (N,17,2) / maxvals (N,17[,1]) float32 (the decode's output as it is; -1 = the
+ * placeholder person of a frame without detections, :787-796: joint 0 at (0, 0), score -100), box_score (N) float64;
+ * gt_off (F+1), gt_xy (NG,15,2) float64, gt_has (NG) int32 bit k = joint k annotated, gt_head (NG,4) float64 x1 y1 x2 y2;
+ * poly_off (F+1) the ignore polygons of each frame, vert_off (NPOLY+1), vert_xy (NV,2) float64.  The kernel applies the
+ * 17 -> 15 joint permutation of coco2posetrack_ord; score = double(maxval) * box_score.  A point strictly inside a
+ * polygon (even-odd crossing test; a boundary point falls to either side) is removed from predictions and ground truth; in
+ * a frame with polygons a person with no point left is removed.  labels (NP,15) int8: 1 match, 0 false positive, -1 no
+ * entry (joint absent or removed); scores (NP,15) float64 (0 where there is no entry); ngt (F,15) int32 annotated joints
+ * left.  At most OTP_POSEVAL_MAX_PR predicted and OTP_POSEVAL_MAX_GT ground-truth persons per frame, which the CALLER checks
+ * (the offsets are device memory; a frame over the limit gets no entries); no limit on vertices.  N = NG = 0 allowed.
+ * otp_ap_curve: compute_rpc + vocap (:686-751) of J joints, one workgroup per joint.  labels_sorted int8 = the entries (0 / 1)
+ * of joint j at [joint_off[j], joint_off[j+1]) (int64, J+1) in descending score order; n_gt (J) int64 annotated joints.
+ * out (J,3) float64 = AP, last precision, last recall, x 100 (zeros for a joint without entries); precision / recall
+ * (one float64 per entry) receive the curve, or NULL. */
+#define OTP_POSEVAL_JOINTS 15
+#define OTP_POSEVAL_MAX_PR 64
+#define OTP_POSEVAL_MAX_GT 64
+int otp_pose_assign(const void* pr_off, const void* pr_sample, const void* preds, const void* maxvals,
+                    const void* box_score, const void* gt_off, const void* gt_xy, const void* gt_has, const void* gt_head,
+                    const void* poly_off, const void* vert_off, const void* vert_xy, double dist_thresh, void* labels,
+                    void* scores, void* ngt, int F, int NP, int N, int NG, void* stream);
+int otp_ap_curve(const void* labels_sorted, const void* joint_off, const void* n_gt, void* out, void* precision,
+                 void* recall, int J, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

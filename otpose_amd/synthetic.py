@@ -175,3 +175,87 @@ def synthetic_targets(batch: int, heatmap_size, num_joints: int = 17, sigma: flo
     d2 = (xs - cx[..., None, None].float()) ** 2 + (ys - cy[..., None, None].float()) ** 2
     target = torch.exp(-d2 / (2 * sigma * sigma)) * vis[..., None, None]
     return target.contiguous(), vis[..., None].contiguous()
+
+
+_SKELETON = (  # official PoseTrack joint order (right_ankle .. head_top): offsets in units of the person's size
+    (-0.15, 1.0), (-0.15, 0.6), (-0.12, 0.2), (0.12, 0.2), (0.15, 0.6), (0.15, 1.0), (-0.45, 0.1), (-0.35, -0.15),
+    (-0.22, -0.4), (0.22, -0.4), (0.35, -0.15), (0.45, 0.1), (0.0, -0.45), (0.0, -0.6), (0.0, -0.8))
+_COCO_OF_OFFICIAL = (16, 14, 12, 11, 13, 15, 10, 8, 6, 5, 7, 9, 1, 0, 2)
+
+
+def posetrack_eval_case(frames: int = 60, seed: int = 0, crowded=(), big_polygon=(), max_gt: int = 6, max_det: int = 8):
+    """Seeded synthetic input of the PoseTrack evaluation (otpose_amd.posetrack_eval): poseval-format ground-truth frames
+    with 0..max_gt persons (some with a subset of joints, a few rects without points, one with an empty point list), ignore
+    polygons (convex and concave) in about every sixth frame, some covering a whole frame's ground truth, and in every sixth
+    frame with two or more detections a box that swallows the first detection; and per frame
+    0..max_det detections as ``(preds (N,17,3) float32 = x, y, maxval in the model's joint order, box (N,) float64,
+    frame_id (N,) int64)``: jittered copies of ground-truth persons (pairs competing for one), and detections far from all.
+    Frames of ``crowded`` hold 64 persons and 64 detections, frames of ``big_polygon`` a 64-vertex ignore polygon."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    skel = np.asarray(_SKELETON)
+    crowded, big_polygon = set(crowded), set(big_polygon)
+    gt_frames, preds, box, frame_id = [], [], [], []
+    empty_points_done = False
+    for f in range(frames):
+        ng = 64 if f in crowded else int(rng.integers(0, max_gt + 1))
+        nd = 64 if f in crowded else int(rng.integers(0, max_det + 1))
+        poses, rects = [], []
+        for _ in range(ng):
+            c = rng.uniform((100, 100), (1820, 980))
+            s = rng.uniform(60, 200)
+            pose = c + skel * s + rng.normal(0, 0.02 * s, (15, 2))
+            hs = s * rng.uniform(0.2, 0.3)
+            poses.append((pose, hs))
+            keep = np.ones(15, bool) if rng.random() < 0.6 else rng.random(15) < 0.6
+            rect = {"x1": [float(c[0] - hs / 2)], "y1": [float(c[1] - 0.9 * s)], "x2": [float(c[0] + hs / 2)],
+                    "y2": [float(c[1] - 0.9 * s + hs)], "track_id": [len(rects)]}
+            u = rng.random()
+            if u < 0.03 and f not in crowded:
+                pass                                                   # a rect without annopoints: dropped by cleanupData
+            elif u < 0.05 and not empty_points_done and f not in crowded:
+                rect["annopoints"] = [{"point": []}]                   # stays: a person with no annotated joint
+                empty_points_done = True
+            else:
+                rect["annopoints"] = [{"point": [{"id": [k], "x": [float(pose[k, 0])], "y": [float(pose[k, 1])]}
+                                                 for k in range(15) if keep[k]]}]
+            rects.append(rect)
+        frame = {"annorect": rects}
+        regions = []
+        if f in big_polygon or rng.random() < 0.17:
+            for _ in range(int(rng.integers(1, 3))):
+                if poses and rng.random() < 0.7:
+                    centre = poses[int(rng.integers(len(poses)))][0].mean(0) + rng.normal(0, 30, 2)
+                else:
+                    centre = rng.uniform((0, 0), (1920, 1080))
+                nv = 64 if f in big_polygon else int(rng.integers(3, 13))
+                radius = rng.uniform(40, 260)
+                ang = np.sort(rng.uniform(0, 2 * np.pi, nv))
+                rad = radius * (rng.uniform(0.35, 1.0, nv) if rng.random() < 0.5 else rng.uniform(0.9, 1.0, nv))
+                regions.append(np.stack([centre[0] + rad * np.cos(ang), centre[1] + rad * np.sin(ang)], 1))
+        if rng.random() < 0.04 and f not in crowded:                   # everything in the frame is ignored
+            regions.append(np.array([[-4000.0, -4000.0], [6000.0, -4000.0], [6000.0, 5000.0], [-4000.0, 5000.0]]))
+        gt_frames.append(frame)
+        first_det = len(preds)
+        for d in range(nd):
+            det = np.empty((17, 3), np.float32)
+            det[:, :2] = rng.uniform((0, 0), (1920, 1080), (17, 2))   # far from everything unless overwritten below
+            u = rng.random()
+            if poses and (u < 0.75 or f in crowded):
+                # in a crowded frame detection d follows person d; else a random person (two may compete for one)
+                pose, hs = poses[d % len(poses)] if f in crowded else poses[int(rng.integers(len(poses)))]
+                sigma = (0.08, 0.25, 0.5)[int(rng.integers(3))] * 0.6 * hs * np.sqrt(2)
+                det[list(_COCO_OF_OFFICIAL), :2] = pose + rng.normal(0, sigma, (15, 2))
+            det[:, 2] = rng.uniform(0.05, 1.0, 17)
+            preds.append(det)
+            box.append(rng.uniform(0.3, 1.0))
+            frame_id.append(f)
+        if f % 6 == 1 and nd >= 2 and f not in crowded:
+            # a box around the frame's FIRST detection (no random draw): that person loses every point while later ones stay
+            q = preds[first_det][list(_COCO_OF_OFFICIAL), :2].astype(np.float64)
+            (x0, y0), (x1, y1) = q.min(0) - 5.0, q.max(0) + 5.0
+            regions.append(np.array([[x0, y0], [x1, y0], [x1, y1], [x0, y1]]))
+        if regions:
+            frame["ignore_regions"] = [{"point": [{"x": [float(x)], "y": [float(y)]} for x, y in r]} for r in regions]
+    preds = np.stack(preds) if preds else np.zeros((0, 17, 3), np.float32)
+    return gt_frames, preds.astype(np.float32), np.asarray(box, np.float64), np.asarray(frame_id, np.int64)

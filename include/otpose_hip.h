@@ -806,6 +806,44 @@ int otp_pose_assign(const void* pr_off, const void* pr_sample, const void* preds
 int otp_ap_curve(const void* labels_sorted, const void* joint_off, const void* n_gt, void* out, void* precision,
                  void* recall, int J, void* stream);
 
+/* ---- Pose NMS of top-down predictions, per frame: the step between the decode and otp_pose_assign when the boxes come
+ * from a detector (VAL/TEST.POST_PROCESS, IN_VIS_THRE, OKS_THRE, SOFT_NMS of configs/default.py:168-195; the reference
+ * declares these switches and carries no code behind them).  The arithmetic below is the contract.  It follows HRNet's
+ * lib/nms/nms.py (oks_iou, oks_nms, soft_oks_nms, rescore) and the rescoring loop of its COCO evaluate as the maintainers
+ * know them; HRNet's source was not at hand, so parity with it is NOT VERIFIED.  Everything is float64, every product,
+ * quotient and sum rounded on its own (no contraction), J = 17 joints in the model's order.
+ *
+ * otp_pose_nms: one workgroup per frame over the CSR of otp_pose_assign: pr_off (F+1) int32, pr_sample (NP) int32 index
+ * into preds (N,17,2) / maxvals (N,17[,1]) float32, box_score (N) / area (N) float64 (area of a crop = prod(scale * 200)).
+ * pr_sample -1 is the placeholder person: score 0, OKS 0 against everybody (it suppresses nobody), always kept.
+ *   person score   kpt = sum over j = 0..16, left to right, of double(maxval[j]) where double(maxval[j]) > in_vis_thre;
+ *                  n = the number of such joints; kpt = kpt / n when n > 0 (else it stays 0); score = kpt * box_score.
+ *   OKS(g, d)      of candidate d against kept person g: vars[j] = (2 * sigma[j])^2,
+ *                  e[j] = (dx^2 + dy^2) / vars[j] / ((area_g + area_d) / 2 + 2^-52) / 2 with dx = x_d - x_g,
+ *                  oks = (sum over j = 0..16, left to right, of exp(-e[j])) / 17.  With oks_in_vis_thre (NaN = none, HRNet's
+ *                  call) the sum runs over the joints where the CANDIDATE's double(maxval) > oks_in_vis_thre (HRNet's
+ *                  `list(vg > t) and list(vd > t)` evaluates to the second list), the divisor is their count, oks = 0 for none.
+ *   order          descending person score; equal scores in the order a stable ascending sort followed by a reversal gives
+ *                  (the later person first); a NaN score before every number, several NaNs by the same tie rule.
+ *   mode 0, hard   walk the order: the first person alive is kept and kills every later person whose OKS against it is NOT
+ *                  <= oks_thresh (a NaN OKS kills); repeat with the next person alive.
+ *   mode 1 / 2,    until nobody is left or max_dets are taken: the head of the order is taken; every remaining score is
+ *   soft           multiplied by exp(-(oks * oks) / oks_thresh) (1, gaussian) or, where oks >= oks_thresh, by (1 - oks)
+ *                  (2, linear), oks against the person just taken; the rest is ordered again by the same rule.
+ * Outputs: keep (NP) int8 0 / 1; person_score (NP) float64 = the person score (mode 0) or the decayed score the person had
+ * when it was taken or, if it never was, at the end (modes 1, 2); rank (NP) int32 = the position in the order (mode 0) or
+ * the step at which the person was taken, -1 if never (modes 1, 2); oks (NP, 64) float64 or NULL: row = person g, column =
+ * the d-th person of g's frame, zeros past the frame's persons.  The decayed scores select and rank; they do not replace
+ * the joint scores of the AP.  sigmas: 17 positive finite doubles in HOST memory, passed on by value.  At most
+ * OTP_POSEVAL_MAX_PR persons per frame, which the CALLER checks (the offsets are device memory; a frame over the limit is
+ * left unwritten).  No allocation, no synchronisation: graph-capturable.  -1 for null pointers, F or NP <= 0, N < 0, mode
+ * outside 0..2, max_dets < 1, an oks_thresh that is not finite and positive or a sigma that is not. */
+#define OTP_POSENMS_JOINTS 17
+int otp_pose_nms(const void* pr_off, const void* pr_sample, const void* preds, const void* maxvals, const void* box_score,
+                 const void* area, const double* sigmas, double in_vis_thre, double oks_thresh, double oks_in_vis_thre,
+                 int mode, int max_dets, void* keep, void* person_score, void* rank, void* oks, int F, int NP, int N,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -251,6 +251,8 @@ SIGNATURES = {
     "otp_loss_joints_mse": (c_int, [c_void_p] * 5 + [c_void_p, c_size_t] + [c_int] * 6 + [c_void_p]),
     "otp_pose_assign": (c_int, [c_void_p] * 12 + [ctypes.c_double] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),
     "otp_ap_curve": (c_int, [c_void_p] * 6 + [c_int, c_void_p]),
+    "otp_pose_nms": (c_int, [c_void_p] * 6 + [ctypes.POINTER(ctypes.c_double)] + [ctypes.c_double] * 3 + [c_int] * 2
+                     + [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
 }
 
 

@@ -1254,6 +1254,69 @@ def ap_curve(labels_sorted, joint_off, n_gt, return_curve=False):
     return (out, prec, rec) if return_curve else out
 
 
+# COCO's per-joint sigmas (17 joints in the model's order), as HRNet's lib/nms/nms.py carries them
+COCO_SIGMAS = tuple(v / 10.0 for v in (.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89))
+_SOFT_TYPES = {"gaussian": 1, "linear": 2}
+
+
+def pose_nms(pr_off, pr_sample, preds, maxvals, box_score, area, *, oks_thresh, in_vis_thre=0.0, oks_in_vis_thre=None,
+             sigmas=COCO_SIGMAS, soft=False, soft_type="gaussian", max_dets=20, return_oks=False):
+    """Keypoint rescoring and per-frame OKS suppression of top-down predictions over the CSR of :func:`pose_assign`, one
+    launch (``otp_pose_nms``; the arithmetic is the contract in include/otpose_hip.h).  ``area`` (N,) float64 is the
+    box area of each sample (``prod(scale * 200)`` for a crop).  Returns ``(keep (NP,) bool, person_score (NP,) float64,
+    rank (NP,) int32[, oks (NP,64) float64])``: hard NMS gives the rescored person score and the position in the
+    descending order, ``soft=True`` (``soft_type`` "gaussian" / "linear", at most ``max_dets`` kept per frame) the decayed
+    score and the step at which the person was taken (-1: never).  The placeholder person (-1) is always kept.
+    Raises ``ValueError`` for a frame with more than ``POSEVAL_MAX_PR`` persons, inconsistent offsets, a sample index
+    outside ``preds`` or a bad setting (the offsets are read back for the check: it synchronises)."""
+    i32, f64 = torch.int32, torch.float64
+    pr_off = _poseval_arg(pr_off, i32, (None,), "pr_off")
+    f = pr_off.numel() - 1
+    pr_sample = _poseval_arg(pr_sample, i32, (None,), "pr_sample")
+    preds = _poseval_arg(preds, torch.float32, (None, 17, 2), "preds")
+    n = preds.shape[0]
+    if torch.is_tensor(maxvals) and maxvals.dim() == 2:
+        maxvals = maxvals.unsqueeze(-1)
+    maxvals = _poseval_arg(maxvals, torch.float32, (n, 17, 1), "maxvals")
+    box_score = _poseval_arg(box_score, f64, (n,), "box_score")
+    area = _poseval_arg(area, f64, (n,), "area")
+    npr = pr_sample.numel()
+    if f <= 0 or npr <= 0:
+        raise ValueError("pose_nms needs at least one frame and one predicted person")
+    sig = [float(s) for s in sigmas]
+    if len(sig) != 17 or not all(math.isfinite(s) and s > 0 for s in sig):
+        raise ValueError("sigmas must be 17 positive finite numbers")
+    oks_thresh = float(oks_thresh)
+    if not (math.isfinite(oks_thresh) and oks_thresh > 0):
+        raise ValueError("oks_thresh must be finite and positive")
+    if int(max_dets) < 1:
+        raise ValueError("max_dets must be at least 1")
+    if soft and soft_type not in _SOFT_TYPES:
+        raise ValueError(f"soft_type must be one of {sorted(_SOFT_TYPES)}")
+    pmax, pmin, pfirst, plast, smax, smin = torch.stack([
+        (pr_off[1:] - pr_off[:-1]).max(), (pr_off[1:] - pr_off[:-1]).min(), pr_off[0], pr_off[-1],
+        pr_sample.max(), pr_sample.min()]).tolist()
+    if pmax > POSEVAL_MAX_PR:
+        raise ValueError(f"a frame has {pmax} predicted persons, the kernel's limit is {POSEVAL_MAX_PR}")
+    if pmin < 0 or pfirst != 0 or plast != npr:
+        raise ValueError("inconsistent CSR offsets")
+    if smax >= n or smin < -1:
+        raise ValueError(f"pr_sample outside [-1, {n})")
+    dev = pr_off.device
+    keep = torch.empty(npr, dtype=torch.int8, device=dev)
+    score = torch.empty(npr, dtype=f64, device=dev)
+    rank = torch.empty(npr, dtype=i32, device=dev)
+    oks = torch.empty((npr, POSEVAL_MAX_PR), dtype=f64, device=dev) if return_oks else None
+    hip.check(hip.lib().otp_pose_nms(
+        hip.ptr(pr_off), hip.ptr(pr_sample), hip.ptr(preds), hip.ptr(maxvals), hip.ptr(box_score), hip.ptr(area),
+        (ctypes.c_double * 17)(*sig), float(in_vis_thre), oks_thresh,
+        math.nan if oks_in_vis_thre is None else float(oks_in_vis_thre), _SOFT_TYPES[soft_type] if soft else 0,
+        int(max_dets), hip.ptr(keep), hip.ptr(score), hip.ptr(rank), hip.ptr(oks), f, npr, n, hip.stream_of(pr_off)),
+        "otp_pose_nms")
+    keep = keep.view(torch.bool)
+    return (keep, score, rank, oks) if return_oks else (keep, score, rank)
+
+
 IMAGENET_MEAN = (0.485, 0.456, 0.406)        # utils/transform.py:7-8
 IMAGENET_STD = (0.229, 0.224, 0.225)
 

@@ -3,6 +3,8 @@ checkpoint by (script/Common.py:442 -> dataset/PoseTrackDataset.py:453-608 ``eva
 
 ``pack_ground_truth`` walks the poseval-format annotation dicts once per dataset; ``PoseTrackEvaluator`` collects the device
 tensors ``OTPose.predict`` returns and evaluates them with two kernels (``ops.pose_assign``, ``ops.ap_curve``; csrc/poseval.hip).
+With a ``PoseNMS`` the evaluator first rescores the persons and suppresses duplicate poses per frame by OKS, hard or soft
+(``ops.pose_nms``; csrc/posenms.hip) - the post-processing of predictions made on detector boxes.
 Out of scope: MOTA / tracking, the JSON directory layout of poseval, YOLO boxes, 1-D NMS, image dumps.
 """
 from __future__ import annotations
@@ -125,25 +127,56 @@ def with_mean(per_joint):
     return np.concatenate([v, [v[~np.isnan(v)].mean()]])
 
 
+class PoseNMS:
+    """Settings of the pose NMS (``ops.pose_nms``): ``oks_thresh`` (OKS_THRE), ``in_vis_thre`` (IN_VIS_THRE: the joints that
+    count in a person's score), ``soft`` (SOFT_NMS) with ``soft_type`` "gaussian" / "linear" and ``max_dets``,
+    ``oks_in_vis_thre`` (the joint selection inside the OKS; None as HRNet calls it) and the per-joint ``sigmas``."""
+
+    def __init__(self, oks_thresh=0.9, in_vis_thre=0.0, soft=False, soft_type="gaussian", max_dets=20,
+                 oks_in_vis_thre=None, sigmas=ops.COCO_SIGMAS):
+        self.oks_thresh, self.in_vis_thre, self.soft = float(oks_thresh), float(in_vis_thre), bool(soft)
+        self.soft_type, self.max_dets, self.oks_in_vis_thre = soft_type, int(max_dets), oks_in_vis_thre
+        self.sigmas = tuple(float(s) for s in sigmas)
+
+    @classmethod
+    def from_cfg(cls, cfg, phase):
+        """The settings of ``cfg.VAL`` (``phase`` "validate", as dataset/PoseTrackDataset.py:57 spells it, or "val") or
+        ``cfg.TEST`` (any other phase): IN_VIS_THRE, OKS_THRE, SOFT_NMS (configs/default.py:168-195).  ``None`` - no NMS -
+        when POST_PROCESS is false or absent.  NMS_THRE is not read."""
+        node = cfg.get("VAL" if str(phase).lower() in ("validate", "val") else "TEST") or {}
+        if not node.get("POST_PROCESS", False):
+            return None
+        return cls(oks_thresh=node.get("OKS_THRE", 0.5), in_vis_thre=node.get("IN_VIS_THRE", 0.0),
+                       soft=node.get("SOFT_NMS", False))
+
+    def kwargs(self):
+        return {"oks_thresh": self.oks_thresh, "in_vis_thre": self.in_vis_thre, "oks_in_vis_thre": self.oks_in_vis_thre,
+                "sigmas": self.sigmas, "soft": self.soft, "soft_type": self.soft_type, "max_dets": self.max_dets}
+
+
 class PoseTrackEvaluator:
     """Collects predictions on the device and evaluates the PoseTrack AP table against a packed ground truth.
 
     ``gt`` is :func:`pack_ground_truth`'s result (or the annotation frames themselves).  ``add`` appends device tensors; no
-    prediction is copied to the host before ``summarize`` has reduced them to 15 x 3 numbers."""
+    prediction is copied to the host before ``summarize`` has reduced them to 15 x 3 numbers.  ``nms`` (a :class:`PoseNMS`
+    or None) suppresses duplicate poses per frame before the assignment; ``add`` then needs each sample's box area."""
 
-    def __init__(self, gt, dist_thresh=0.5):
+    def __init__(self, gt, dist_thresh=0.5, nms=None):
         self.gt = gt if isinstance(gt, dict) else pack_ground_truth(gt)
         self.dist_thresh = float(dist_thresh)
+        self.nms = nms
         self._gt_dev = None
         self.reset()
 
     def reset(self):
-        self._preds, self._maxvals, self._box, self._frame = [], [], [], []
+        self._preds, self._maxvals, self._box, self._frame, self._area = [], [], [], [], []
 
-    def add(self, preds, maxvals, box_score, frame_id):
+    def add(self, preds, maxvals, box_score, frame_id, area=None, scale=None):
         """``preds`` (B,17,2) / ``maxvals`` (B,17,1) float32 as ``OTPose.predict`` / ``ops.get_final_preds`` return them,
         ``box_score`` (B,) the detector's box score per sample (kept in float64), ``frame_id`` (B,) the index of each
-        sample's frame in the ORIGINAL ground-truth frame list.  Samples of a dropped frame are ignored."""
+        sample's frame in the ORIGINAL ground-truth frame list.  Samples of a dropped frame are ignored.  With ``nms`` set,
+        ``area`` (B,) is each sample's box area, or ``scale`` (B,2) the crop's scale, from which the area is formed in
+        float64 as ``prod(scale * 200)`` (``all_boxes[:, 4]``, script/Common.py:429)."""
         if not torch.is_tensor(preds) or not torch.is_tensor(maxvals):
             raise TypeError("preds and maxvals must be tensors")
         b = preds.shape[0]
@@ -158,6 +191,15 @@ class PoseTrackEvaluator:
             raise ValueError("box_score and frame_id must have one entry per sample")
         if b and (frame_id.min() < 0 or frame_id.max() >= self.gt["num_frames"]):
             raise ValueError(f"frame_id outside [0, {self.gt['num_frames']})")
+        if self.nms is not None:
+            if area is None and scale is None:
+                raise ValueError("the evaluator has an NMS: add() needs area= or scale=")
+            if area is None:
+                area = (torch.as_tensor(scale, dtype=torch.float64).reshape(-1, 2) * 200.0).prod(1)
+            area = torch.as_tensor(area, dtype=torch.float64).reshape(-1)
+            if area.numel() != b:
+                raise ValueError("area / scale must have one entry per sample")
+            self._area.append(area.to(preds.device))
         self._preds.append(preds.detach().reshape(b, 17, 2))
         self._maxvals.append(maxvals.detach().reshape(b, 17, 1))
         self._box.append(box.to(preds.device))
@@ -169,17 +211,43 @@ class PoseTrackEvaluator:
         frame_id = np.concatenate(self._frame)
         return torch.cat(self._preds), torch.cat(self._maxvals), torch.cat(self._box), frame_id
 
+    def _survivors(self, pr_off, pr_sample, preds, maxvals, box):
+        """The CSR (device tensors) after ``ops.pose_nms``: the survivors of each frame in their order of arrival.  Every
+        frame keeps at least the head of its order (or its placeholder), so no frame becomes empty."""
+        dev = preds.device
+        off, sample = torch.from_numpy(pr_off).to(dev), torch.from_numpy(pr_sample).to(dev)
+        keep = ops.pose_nms(off, sample, preds, maxvals, box, torch.cat(self._area), **self.nms.kwargs())[0]
+        before = torch.zeros(keep.numel() + 1, dtype=torch.int32, device=dev)
+        before[1:] = keep.cumsum(0)
+        return before[off.long()].contiguous(), sample[keep]
+
+    def kept_samples(self):
+        """Indices (ascending, numpy int64) of the added samples that reach the assignment: those of a kept frame and,
+        with ``nms``, not suppressed."""
+        preds, maxvals, box, frame_id = self._gathered()
+        g = self.gt
+        pr_off, pr_sample = pack_predictions(g["frame_map"], frame_id, len(g["kept"]))
+        if self.nms is not None:
+            pr_sample = self._survivors(pr_off, pr_sample, preds, maxvals, box)[1].cpu().numpy()
+        return np.sort(pr_sample[pr_sample >= 0].astype(np.int64))
+
     def assign(self):
-        """``ops.pose_assign`` over everything added: ``(labels, scores, ngt, pr_off, pr_sample)`` (the last two numpy)."""
+        """``ops.pose_assign`` over everything added: ``(labels, scores, ngt, pr_off, pr_sample)`` (the last two numpy);
+        with ``nms`` over the survivors of ``ops.pose_nms``, the CSR returned being theirs."""
         preds, maxvals, box, frame_id = self._gathered()
         g = self.gt
         pr_off, pr_sample = pack_predictions(g["frame_map"], frame_id, len(g["kept"]))
         dev = preds.device
+        if self.nms is not None:
+            off_dev, sample_dev = self._survivors(pr_off, pr_sample, preds, maxvals, box)
+            pr_off, pr_sample = off_dev.cpu().numpy(), sample_dev.cpu().numpy()
+        else:
+            off_dev, sample_dev = torch.from_numpy(pr_off).to(dev), torch.from_numpy(pr_sample).to(dev)
         if self._gt_dev is None or self._gt_dev[0] != dev:
             self._gt_dev = (dev, {k: torch.from_numpy(g[k]).to(dev) for k in _GT_KEYS})
         d = self._gt_dev[1]
         labels, scores, ngt = ops.pose_assign(
-            torch.from_numpy(pr_off).to(dev), torch.from_numpy(pr_sample).to(dev), preds, maxvals, box, d["gt_off"],
+            off_dev, sample_dev, preds, maxvals, box, d["gt_off"],
             d["gt_xy"], d["gt_has"], d["gt_head"], d["poly_off"], d["vert_off"], d["vert_xy"], self.dist_thresh)
         return labels, scores, ngt, pr_off, pr_sample
 
@@ -198,14 +266,16 @@ class PoseTrackEvaluator:
         """The prediction frames as the reference writes them for poseval (PoseTrackDataset.py:573-577 with
         convert_data_to_annorect_struct and coco2posetrack_ord): one ``{"annorect": [...]}`` per ORIGINAL ground-truth frame,
         official joint order, score = float64(maxval) * box score, the placeholder person where nothing was predicted.
-        This copies the predictions to the host."""
+        With ``nms`` only the persons it keeps are written (a dropped frame, which is not evaluated, keeps all of its samples).  This copies the predictions to the host."""
         preds, maxvals, box, frame_id = self._gathered()
+        kept = None if self.nms is None else set(self.kept_samples().tolist())
         preds = preds.cpu().numpy().astype(np.float64)
         maxvals = maxvals.cpu().numpy().reshape(-1, 17).astype(np.float64)
         box = box.cpu().numpy()
         per_frame = [[] for _ in range(self.gt["num_frames"])]
         for s, f in enumerate(frame_id):
-            per_frame[f].append(s)
+            if kept is None or s in kept or self.gt["frame_map"][f] < 0:
+                per_frame[f].append(s)
         frames = []
         for samples in per_frame:
             rects = []

@@ -259,3 +259,55 @@ def posetrack_eval_case(frames: int = 60, seed: int = 0, crowded=(), big_polygon
             frame["ignore_regions"] = [{"point": [{"x": [float(x)], "y": [float(y)]} for x, y in r]} for r in regions]
     preds = np.stack(preds) if preds else np.zeros((0, 17, 3), np.float32)
     return gt_frames, preds.astype(np.float32), np.asarray(box, np.float64), np.asarray(frame_id, np.int64)
+
+
+def pose_nms_case(frames: int = 300, seed: int = 0, low_vis: float = 0.05):
+    """Seeded synthetic input of the pose NMS (``ops.pose_nms``, ``posetrack_eval.PoseNMS``): :func:`posetrack_eval_case`
+    (one frame of 64 and one of 63 detections) with what a detector adds - jittered duplicates (0.5-20 px, lower box score)
+    of about every second detection - and one frame each for the special persons, named in the returned ``special`` dict by
+    sample index: ``exact`` (a copy of ``exact_of``: OKS 1), ``low_vis`` (every maxval below ``low_vis``), ``zero_area`` (a
+    copy of ``zero_area_of`` with area 0), ``equal`` (the person score of ``equal_of``, bit for bit, another pose),
+    ``nan_xy`` (NaN coordinates) and ``nan_score`` (a NaN box score), the last two in frames without another special person.
+    Returns ``(gt_frames, preds (N,17,3) float32, box (N,) float64, frame_id (N,) int64, area (N,) float64, special)``."""
+    import numpy as np
+    gt_frames, preds, box, fid = posetrack_eval_case(frames, seed, crowded=(5, frames // 2))
+    rng = np.random.default_rng([seed, 0x4e4d53])
+    last = np.nonzero(fid == frames // 2)[0][-1]                       # 64 -> 63 detections in the second crowded frame
+    preds, box, fid = np.delete(preds, last, 0), np.delete(box, last), np.delete(fid, last)
+    span = preds[:, :, :2].max(1).astype(np.float64) - preds[:, :, :2].min(1).astype(np.float64)
+    area = span.prod(1) * 1.25 ** 2 * rng.uniform(0.9, 1.1, fid.size)
+    count = np.bincount(fid, minlength=frames)
+    new_p, new_b, new_f, new_a = [], [], [], []
+
+    def add(src, jitter, frame=None):
+        det = preds[src].copy()
+        det[:, :2] += rng.normal(0, jitter, (17, 2)).astype(np.float32) if jitter else 0
+        new_p.append(det)
+        new_b.append(box[src] * rng.uniform(0.5, 0.95))
+        new_f.append(fid[src] if frame is None else frame)
+        new_a.append(area[src] * rng.uniform(0.9, 1.1))
+        return fid.size + len(new_p) - 1
+
+    for s in np.nonzero((count[fid] < 20) & (rng.random(fid.size) < 0.5))[0]:
+        for _ in range(int(rng.integers(1, 3))):
+            add(s, rng.uniform(0.5, 20.0))
+    # the special persons: one frame each, among the frames that are evaluated and hold 2..8 detections
+    plain = [f for f in range(frames) if 2 <= count[f] <= 8 and len(gt_frames[f]["annorect"]) > 0
+             and any("annopoints" in r for r in gt_frames[f]["annorect"])]
+    chosen = rng.choice(plain, 6, replace=False)
+    first = [int(np.nonzero(fid == f)[0][0]) for f in chosen]
+    special = {"exact_of": first[0], "exact": add(first[0], 0.0)}
+    special["low_vis"] = add(first[1], 3.0)
+    new_p[-1][:, 2] = rng.uniform(0.2, 0.8, 17).astype(np.float32) * np.float32(low_vis)
+    special["zero_area_of"], special["zero_area"] = first[2], add(first[2], 0.0)
+    new_a[-1] = 0.0
+    special["equal_of"], special["equal"] = first[3], add(first[3], 0.0)
+    new_p[-1][:, :2] += rng.uniform(150.0, 300.0, 2).astype(np.float32)
+    new_b[-1] = box[first[3]]
+    special["nan_xy"] = add(first[4], 2.0)
+    new_p[-1][3:6, :2] = np.nan
+    special["nan_score"] = add(first[5], 40.0)
+    new_b[-1] = np.nan
+    preds = np.concatenate([preds, np.stack(new_p)]).astype(np.float32)
+    return (gt_frames, preds, np.concatenate([box, new_b]), np.concatenate([fid, np.asarray(new_f, np.int64)]),
+            np.concatenate([area, new_a]), special)

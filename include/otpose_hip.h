@@ -158,6 +158,39 @@ int otp_mdcn_backward_ex(const void* x, const void* offset, const void* mask, co
                          size_t workspace_bytes, int N, int C, int H, int W, int Cout, int kh, int kw, int stride_h, int stride_w,
                          int pad_h, int pad_w, int dil_h, int dil_w, int groups, int deformable_groups, int dtype, void* stream);
 
+/* ---- deformable position-sensitive RoI pooling ---------------------------------------------------
+ * The other native operator of thirdparty/deform_conv (deform_psroi_pooling_cuda_forward / _backward, src/deform_pool_cuda.cpp,
+ * src/deform_pool_cuda_kernel.cu:20-253).  data (N, C, H, W) with C = out_channels * group_size^2; rois (num_rois, 5) rows
+ * (batch index, x1, y1, x2, y2) in the data's dtype; offset (num_rois, offset_channels, part_size, part_size) or NULL with
+ * no_trans != 0 (then offset_channels is ignored); out and out_count (num_rois, out_channels, pooled_size, pooled_size):
+ *   out[n,ctop,ph,pw] = mean of the valid ones of sample_per_part^2 bilinear samples of channel (ctop*G + gh)*G + gw, or 0 when
+ *   there is none; out_count = the number of valid samples, in the data's dtype.
+ * RoI corners pass through C round() (halves away from zero), each edge is round(x) * spatial_scale - 0.5, width and height are at
+ * least 0.1; a sample outside [-0.5, W - 0.5] x [-0.5, H - 0.5] is skipped, any other is clamped to the map.  A RoI whose batch
+ * index is outside [0, N) pools nothing (out = out_count = 0) where the reference would read out of bounds.
+ * dtype: OTP_DTYPE_F32 or OTP_DTYPE_F64 (coordinates and weights in that type); others OTP_ERR_UNSUPPORTED, as are
+ * N*C*H*W >= 2^31 and num_rois*out_channels*pooled_size^2 >= 2^31.  OTP_ERR_BAD_ARG: null required pointer, non-positive size,
+ * C != out_channels*group_size^2, and with offsets an odd offset_channels or out_channels % (offset_channels/2) != 0. */
+int otp_deform_psroi_pool_forward(const void* data, const void* rois, const void* offset, void* out, void* out_count, int N, int C,
+                                  int H, int W, int num_rois, int offset_channels, int no_trans, float spatial_scale,
+                                  int out_channels, int group_size, int pooled_size, int part_size, int sample_per_part,
+                                  float trans_std, int dtype, void* stream);
+/* grad_input (N, C, H, W) and grad_offset (offset's shape; may be NULL and is untouched with no_trans) are ADDED TO (the
+ * reference scatters with atomicAdd into buffers its caller zeroed, functions/deform_pool.py:56-58); elements with
+ * out_count <= 0 contribute nothing (out_count is the forward's output: whole numbers; a value below 1, or NaN, counts as 0).
+ * An inf or NaN in grad_out makes every element of grad_input NaN and flows into the grad_offset cells it feeds.
+ * No float atomics: grad_input is accumulated in 64-bit fixed point in the workspace and added once, grad_offset is a fixed-order sum per cell - two calls on the same inputs return the same bits.
+ * workspace: otp_deform_psroi_pool_backward_workspace bytes (0 for a geometry the operator rejects), 8-byte aligned;
+ * OTP_ERR_WORKSPACE when smaller. */
+size_t otp_deform_psroi_pool_backward_workspace(int N, int C, int H, int W, int num_rois, int offset_channels, int no_trans,
+                                                int out_channels, int group_size, int pooled_size, int part_size,
+                                                int sample_per_part, int dtype);
+int otp_deform_psroi_pool_backward(const void* grad_out, const void* data, const void* rois, const void* offset,
+                                   const void* out_count, void* grad_input, void* grad_offset, int N, int C, int H, int W,
+                                   int num_rois, int offset_channels, int no_trans, float spatial_scale, int out_channels,
+                                   int group_size, int pooled_size, int part_size, int sample_per_part, float trans_std,
+                                   void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
 /* ---- dense convolution (implicit GEMM on the f32 matrix cores) --------------------------------
  * out[n, out_coff+co, ho, wo] = act( scale[co] * conv(in (+ in2))[n,co,ho,wo] + shift[co] (+ res) )
  * groups = 1.  Tensors may be channel slices of wider tensors: `*_ctot` is the channel count of the

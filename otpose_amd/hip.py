@@ -81,6 +81,10 @@ SIGNATURES = {
     "otp_mdcn_backward_workspace": (c_size_t, [c_int] * 7),
     "otp_mdcn_backward_workspace_ex": (c_size_t, [c_int] * 17),
     "otp_mdcn_backward": (c_int, [c_void_p] * 10 + [c_void_p, c_size_t] + [c_int] * 12 + [c_int, c_void_p]),
+    "otp_deform_psroi_pool_forward": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_float] + [c_int] * 5 + [c_float, c_int, c_void_p]),
+    "otp_deform_psroi_pool_backward_workspace": (c_size_t, [c_int] * 13),
+    "otp_deform_psroi_pool_backward": (c_int, [c_void_p] * 7 + [c_int] * 7 + [c_float] + [c_int] * 5 + [c_float]
+                                       + [c_void_p, c_size_t, c_int, c_void_p]),
     "otp_conv2d_pack_weight": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "otp_conv2d": (c_int, [c_void_p] * 7 + [ctypes.POINTER(ConvDesc), c_void_p]),
     "otp_conv2d_wino_weight_bytes": (c_size_t, [c_int, c_int]),

@@ -467,7 +467,7 @@ int otp_pointwise_x3(const void* x, const void* packed, const void* res, void* o
                      int x_coff, int res_ctot, int res_coff, int out_ctot, int out_coff, int relu, void* stream);
 /* The same convolution writing the S8 image of its result ([B][Cout / 8][hi | lo][T] records, otp_s8_bytes(B, Cout, H, W) bytes:
  * the input format of otp_conv3x3_s8) instead of an fp32 tensor - a Bottleneck's conv1 in front of its 3x3 conv2.  Cin in
- * {64, 256}, Cout a multiple of 32 (<= 256), T a multiple of 4; packed from otp_pointwise_x3_s8_pack (its own row order). */
+ * {64, 256}, Cout a multiple of 32 (<= 256), T even; packed from otp_pointwise_x3_s8_pack (its own row order). */
 int otp_pointwise_x3_s8_supported(int Cin, int Cout, int T);
 size_t otp_pointwise_x3_s8_weight_bytes(int Cin, int Cout);
 int otp_pointwise_x3_s8_pack(const void* w, const void* scale, const void* shift, void* packed, int Cin, int Cout, void* stream);
@@ -477,6 +477,20 @@ int otp_pointwise_x3_s8(const void* x, const void* packed, void* out_s8, int B, 
  * (model/HRNet.py:566-571) whose result is read as S8 records only */
 int otp_pointwise_x3_s8_res(const void* x, const void* packed, const void* res, void* out_s8, int B, int Cin, int Cout, int T,
                             int x_ctot, int x_coff, int r_ctot, int r_coff, int relu, void* stream);
+/* A Bottleneck's conv3 and the NEXT Bottleneck's conv1 as one launch (layer1's block boundaries, model/HRNet.py:551-571):
+ *   out    = act1(scale1 * (W1 . x) + shift1 (+ res))     Cin -> Cmid, fp32 NCHW channel slice, as otp_pointwise_x3 writes it
+ *   out_s8 = S8 image of act2(scale2 * (W2 . out) + shift2)   Cmid -> Cout2, as otp_pointwise_x3_s8 on `out` writes it
+ * - the same bits as those two launches, without reading `out` back.  Cmid = 256, Cout2 = 64, T even, and the two forms layer1
+ * has: Cin = 64 with a residual (a Bottleneck's conv3), Cin = 128 without (the first block's shortcut folded over the
+ * concatenation); OTP_ERR_UNSUPPORTED otherwise.  packed: otp_pointwise_x3_pair_weight_bytes bytes from
+ * otp_pointwise_x3_pair_pack (w1: (Cmid, Cin), w2: (Cout2, Cmid) fp32; scale / shift may be NULL = 1 / 0). */
+int otp_pointwise_x3_pair_supported(int Cin, int Cmid, int Cout2, int T);
+size_t otp_pointwise_x3_pair_weight_bytes(int Cin, int Cmid, int Cout2);
+int otp_pointwise_x3_pair_pack(const void* w1, const void* scale1, const void* shift1, const void* w2, const void* scale2,
+                               const void* shift2, void* packed, int Cin, int Cmid, int Cout2, void* stream);
+int otp_pointwise_x3_pair(const void* x, const void* packed, const void* res, void* out, void* out_s8, int B, int Cin, int Cmid,
+                          int Cout2, int T, int x_ctot, int x_coff, int res_ctot, int res_coff, int out_ctot, int out_coff,
+                          int relu1, int relu2, void* stream);
 
 /* The same operator with split-half ("f16x3": two IEEE-half pieces per fp32 operand, csrc/common.h) products on the 16-bit matrix cores (csrc/mlpx.hip): fp32 storage, fp32
  * accumulation, LayerNorm / bias / GELU in fp32; each product is lo*hi + hi*lo + hi*hi of two bf16 pieces per operand.

@@ -311,6 +311,189 @@ __global__ __launch_bounds__(256, CIN <= 128 ? 3 : 2) void pointx_s8_kernel(PxAr
     otp_range_report(A.rflag, bad, OTP_RANGE_POINTX);
 }
 
+// A Bottleneck's conv3 (Cin -> 256, + residual, ReLU) and the NEXT Bottleneck's conv1 (256 -> 64, ReLU) as one launch
+// (model/HRNet.py:551-571, layer1's block boundaries).  The 256-channel fp32 tensor between them is still written - the next
+// block's conv3 reads it as its residual - but not read back: conv3 runs in the S8 kernel's tile-pair row order, so when pair pr
+// is through its epilogue lane (pixel pair n, kq) holds channels 32 pr + 8 kq .. + 7 of its two pixels, and those eight values,
+// split, ARE the B fragment of k-step ks = pr of the 256 -> 64 product (the map pointx_s8_kernel<256> builds from HBM).
+// Per trip (= tile pair of GEMM 1): residual loads, the DMA of the next trip's weights (GEMM 1's pair pr + 1, 4 KS KB, and GEMM 2's
+// k-slice pr, 8 KB: its four tiles' hi | lo fragments, 2 KB each at a 16 KB stride of the 256 -> 64 image), GEMM 1's MFMAs of pair
+// pr, GEMM 2's MFMAs of k-step pr - 1 (its operand comes from the previous trip's epilogue, so every MFMA of a trip still comes
+// before the first use of a residual value), epilogue and fp32 stores of pair pr, barrier on the DMA alone.  Both products keep
+// the order of the two kernels above (al Xh, ah Xl, ah Xh per k-step, ks ascending): the fp32 tensor and the S8 image are the
+// bits otp_pointwise_x3 followed by otp_pointwise_x3_s8 writes.
+struct PxPairArgs {
+    const float* x;
+    const unsigned char* w1;                                                 // conv3: S8 row order, 8 pairs, then scale / shift
+    const unsigned char* w2;                                                 // conv1 of the next block: the 256 -> 64 S8-order image
+    const float* res;
+    float* out;
+    float* out_s8;
+    int T, tiles_per_b, relu1, relu2;
+    int x_ctot, x_coff, r_ctot, r_coff, o_ctot, o_coff;
+    unsigned* rflag;
+};
+constexpr int PXP_CMID = 256, PXP_COUT2 = 64, PXP_PAIRS = PXP_CMID / 32, PXP_W2_SLICE = (PXP_COUT2 / 16) * 2048;
+
+// k-slice ks of the 256 -> 64 image ([tile][ks][hi, lo][1 KB]) -> [tile][hi, lo][1 KB] at lds: two passes of the 256 threads
+__device__ __forceinline__ void pxp_stage_w2(const unsigned char* __restrict__ w2, int ks, unsigned char* lds) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+#pragma unroll
+    for (int i = 0; i < PXP_W2_SLICE / 4096; ++i) {
+        const int u0 = i * 256 + wave * 64, t = u0 >> 7;                     // 128 units per tile
+        const unsigned char* src = w2 + (size_t)((t * (PXP_CMID / 32) + ks) * 2) * 1024 + (size_t)((u0 & 127) + lane) * 16;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                         (__attribute__((address_space(3))) void*)(lds + u0 * 16), 16, 0, 0);
+    }
+}
+
+template <int CIN, bool RES>
+__global__ __launch_bounds__(256, CIN <= 64 ? 3 : 2) void pointx_pair_kernel(PxPairArgs A) {
+    constexpr int KS = px_ks(CIN), W1B = KS * 4096, BUFB = W1B + PXP_W2_SLICE, NT2 = PXP_COUT2 / 16;
+    // (ONE LDS object, like pointx_kernel: [2][pair of GEMM 1 | k-slice of GEMM 2][scale, shift of GEMM 1][of GEMM 2])
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUFB + 4 * PX_MAX_COUT * 4];
+    float* ss1 = reinterpret_cast<float*>(lds + 2 * BUFB);
+    float* ss2 = ss1 + 2 * PX_MAX_COUT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, n = lane & 15;
+    const int b = blockIdx.x / A.tiles_per_b, tile = blockIdx.x - b * A.tiles_per_b;
+    const int T = A.T, tok = tile * 128 + wave * 32 + 2 * n;
+    const bool valid = tok < T;
+    px_stage<W1B>(A.w1, lds);
+    {
+        const unsigned char* tail = tid < 128 ? A.w1 + (size_t)PXP_PAIRS * W1B : A.w2 + (size_t)NT2 * (PXP_CMID / 32) * 2048;
+        reinterpret_cast<f32x4*>(ss1)[tid] = reinterpret_cast<const f32x4*>(tail)[tid & 127];
+    }
+    const float* __restrict__ x = A.x + ((size_t)b * A.x_ctot + A.x_coff) * T + (valid ? tok : T - 2);
+    h16x8 Xh[KS][2], Xl[KS][2];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        float v0[8], v1[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const f32x2 v = *reinterpret_cast<const f32x2*>(x + (size_t)(32 * ks + 8 * kq + j) * T);
+            v0[j] = v.x;
+            v1[j] = v.y;
+        }
+        px_split8(v0, Xh[ks][0], Xl[ks][0]);
+        px_split8(v1, Xh[ks][1], Xl[ks][1]);
+    }
+    const unsigned plane = (unsigned)((size_t)PXP_CMID * T * sizeof(float));
+    const otp_rsrc ro = make_rsrc32(A.out + ((size_t)b * A.o_ctot + A.o_coff) * T, plane);
+    const otp_rsrc rr = make_rsrc32(RES ? A.res + ((size_t)b * A.r_ctot + A.r_coff) * T : A.out, RES ? plane : 0u);
+    const float lo1 = A.relu1 ? 0.f : -__builtin_inff(), lo2 = A.relu2 ? 0.f : -__builtin_inff();
+    bool bad = false;                                  // range guard (common.h), both outputs, before the clamps
+    f32x4 acc2[NT2][2];
+#pragma unroll
+    for (int t = 0; t < NT2; ++t) acc2[t][0] = acc2[t][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    h16x8 Yh[2] = {}, Yl[2] = {};                      // the previous pair's results: B fragments of GEMM 2's k-step pr - 1
+    __syncthreads();                                   // pair 0 and the scale / shift vectors landed
+    // k-step ks of GEMM 2 from the slice at W (a trip's buffer behind GEMM 1's pair)
+    auto gemm2 = [&](const unsigned char* W) {
+#pragma unroll
+        for (int t = 0; t < NT2; ++t) {
+            const h16x8 ah = *reinterpret_cast<const h16x8*>(W + (t * 2) * 1024 + lane * 16);
+            const h16x8 al = *reinterpret_cast<const h16x8*>(W + (t * 2 + 1) * 1024 + lane * 16);
+            acc2[t][0] = OTP_X3_MFMA(al, Yh[0], acc2[t][0], 0, 0, 0);
+            acc2[t][1] = OTP_X3_MFMA(al, Yh[1], acc2[t][1], 0, 0, 0);
+            acc2[t][0] = OTP_X3_MFMA(ah, Yl[0], acc2[t][0], 0, 0, 0);
+            acc2[t][1] = OTP_X3_MFMA(ah, Yl[1], acc2[t][1], 0, 0, 0);
+            acc2[t][0] = OTP_X3_MFMA(ah, Yh[0], acc2[t][0], 0, 0, 0);
+            acc2[t][1] = OTP_X3_MFMA(ah, Yh[1], acc2[t][1], 0, 0, 0);
+        }
+    };
+    // Every wave issues the SAME vector-memory instructions per trip - 8 residual loads, KS + 2 DMA passes, 8 stores, lanes without
+    // a pixel masked by an out-of-range offset - so the barrier waits for the DMA alone (`s_waitcnt vmcnt(8)`).
+#pragma unroll 1
+    for (int pr = 0; pr < PXP_PAIRS; ++pr) {
+        const int c8 = 32 * pr + 8 * kq;                                     // the lane's 8 channels of this pair
+        int voff[8];
+        f32x2 rv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            voff[e] = valid ? ((c8 + e) * T + tok) * 4 : -16;
+            if (RES) rv[e] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rr, voff[e], 0, 0));
+        }
+        asm volatile("" ::: "memory");
+        // (the last trip re-stages pair 0, which nobody reads, next to k-slice 7, which the step behind the loop reads)
+        unsigned char* nxt = lds + ((pr + 1) & 1) * BUFB;
+        px_stage<W1B>(A.w1 + (size_t)((pr + 1) & (PXP_PAIRS - 1)) * W1B, nxt);
+        pxp_stage_w2(A.w2, pr, nxt + W1B);
+        asm volatile("" ::: "memory");
+        const unsigned char* P = lds + (pr & 1) * BUFB;
+        f32x4 acc[2][2];
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const h16x8 ah = *reinterpret_cast<const h16x8*>(P + ((m * KS + ks) * 2) * 1024 + lane * 16);
+                const h16x8 al = *reinterpret_cast<const h16x8*>(P + ((m * KS + ks) * 2 + 1) * 1024 + lane * 16);
+                acc0 = OTP_X3_MFMA(al, Xh[ks][0], acc0, 0, 0, 0);
+                acc1 = OTP_X3_MFMA(al, Xh[ks][1], acc1, 0, 0, 0);
+                acc0 = OTP_X3_MFMA(ah, Xl[ks][0], acc0, 0, 0, 0);
+                acc1 = OTP_X3_MFMA(ah, Xl[ks][1], acc1, 0, 0, 0);
+                acc0 = OTP_X3_MFMA(ah, Xh[ks][0], acc0, 0, 0, 0);
+                acc1 = OTP_X3_MFMA(ah, Xh[ks][1], acc1, 0, 0, 0);
+            }
+            acc[m][0] = acc0;
+            acc[m][1] = acc1;
+        }
+        if (pr > 0) gemm2(P + W1B);
+        asm volatile("" ::: "memory");
+        const f32x4 sc0 = *reinterpret_cast<const f32x4*>(ss1 + c8), sc1 = *reinterpret_cast<const f32x4*>(ss1 + c8 + 4);
+        const f32x4 sh0 = *reinterpret_cast<const f32x4*>(ss1 + PX_MAX_COUT + c8);
+        const f32x4 sh1 = *reinterpret_cast<const f32x4*>(ss1 + PX_MAX_COUT + c8 + 4);
+        float v[2][8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float u0 = acc[0][h][i] * sc0[i] + sh0[i], u1 = acc[1][h][i] * sc1[i] + sh1[i];
+                if (RES) u0 += rv[i][h], u1 += rv[4 + i][h];
+                bad |= otp_out_of_range(u0);
+                bad |= otp_out_of_range(u1);
+                v[h][i] = fmaxf(u0, lo1);
+                v[h][4 + i] = fmaxf(u1, lo1);
+            }
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, (f32x2){v[0][e], v[1][e]}), ro, voff[e], 0, 0);
+        px_split8(v[0], Yh[0], Yl[0]);
+        px_split8(v[1], Yh[1], Yl[1]);
+        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // this wave's part of the next trip's weights has landed (after the last
+        __builtin_amdgcn_s_barrier();                      // trip: nothing may land in the LDS once the wave has ended); stores fly on
+        asm volatile("" ::: "memory");
+    }
+    gemm2(lds + (PXP_PAIRS & 1) * BUFB + W1B);             // k-step 7
+    // the S8 records of the 64 channels: pointx_s8_kernel's epilogue
+    const otp_rsrc r8 = make_rsrc32(A.out_s8 + (size_t)b * PXP_COUT2 * T, (unsigned)((size_t)PXP_COUT2 * T * sizeof(float)));
+#pragma unroll
+    for (int m = 0; m < NT2; m += 2) {
+        const int p = m >> 1, c8 = 32 * p + 8 * kq, g = 4 * p + kq;                              // channel group of this lane
+        const f32x4 sc0 = *reinterpret_cast<const f32x4*>(ss2 + c8), sc1 = *reinterpret_cast<const f32x4*>(ss2 + c8 + 4);
+        const f32x4 sh0 = *reinterpret_cast<const f32x4*>(ss2 + PX_MAX_COUT + c8);
+        const f32x4 sh1 = *reinterpret_cast<const f32x4*>(ss2 + PX_MAX_COUT + c8 + 4);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            float v[8];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float u0 = acc2[m][h][i] * sc0[i] + sh0[i] + 0.f, u1 = acc2[m + 1][h][i] * sc1[i] + sh1[i] + 0.f;
+                bad |= otp_out_of_range(u0);
+                bad |= otp_out_of_range(u1);
+                v[i] = fmaxf(u0, lo2);
+                v[4 + i] = fmaxf(u1, lo2);
+            }
+            h16x8 hi, lo;
+            px_split8(v, hi, lo);
+            const int o = valid ? ((g * 2) * T + tok + h) * 16 : -16;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), r8, o, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), r8, valid ? o + T * 16 : -16, 0, 0);
+        }
+    }
+    otp_range_report(A.rflag, bad, OTP_RANGE_POINTX);
+}
+
 bool px_cin_ok(int Cin) { return Cin >= 16 && Cin <= 256; }
 int px_cin_pad(int Cin) { return Cin <= 64 ? 64 : (Cin <= 128 ? 128 : 256); }              // the kernel instantiation that holds it
 
@@ -321,7 +504,7 @@ extern "C" int otp_pointwise_x3_supported(int Cin, int Cout, int T) {
 }
 
 extern "C" int otp_pointwise_x3_s8_supported(int Cin, int Cout, int T) {
-    return ((Cin == 64 || Cin == 256) && Cout > 0 && Cout <= PX_MAX_COUT && Cout % 32 == 0 && T >= 4 && T % 4 == 0 &&
+    return ((Cin == 64 || Cin == 256) && Cout > 0 && Cout <= PX_MAX_COUT && Cout % 32 == 0 && T >= 2 && T % 2 == 0 &&
             (size_t)Cout * T * 4 < (1ull << 31)) ? 1 : 0;
 }
 
@@ -426,5 +609,67 @@ extern "C" int otp_pointwise_x3_s8_res(const void* x, const void* packed, const 
         if (Cin == 64) hipLaunchKernelGGL((pointx_s8_kernel<64, false>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((pointx_s8_kernel<256, false>), grid, dim3(256), 0, st, a);
     }
+    return otp_launch_status();
+}
+
+// ---- conv3 of one Bottleneck + conv1 of the next as one launch (pointx_pair_kernel) ----------------------------------------
+
+extern "C" int otp_pointwise_x3_pair_supported(int Cin, int Cmid, int Cout2, int T) {
+    return ((Cin == 64 || Cin == 128) && Cmid == PXP_CMID && Cout2 == PXP_COUT2 && T >= 2 && T % 2 == 0 &&
+            (size_t)Cmid * T * 4 < (1ull << 31)) ? 1 : 0;
+}
+
+namespace {
+// the two images of the pair in one buffer: conv3's in the S8 kernel's row order (8 tile pairs of 4 KS KB, scale / shift), then
+// conv1's 256 -> 64 image of otp_pointwise_x3_s8_pack
+size_t pxp_w1_bytes(int Cin) { return (size_t)PXP_PAIRS * (Cin / 32) * 4096 + 2 * PX_MAX_COUT * sizeof(float); }
+}  // namespace
+
+extern "C" size_t otp_pointwise_x3_pair_weight_bytes(int Cin, int Cmid, int Cout2) {
+    if (!otp_pointwise_x3_pair_supported(Cin, Cmid, Cout2, 2)) return 0;
+    return pxp_w1_bytes(Cin) + otp_pointwise_x3_s8_weight_bytes(Cmid, Cout2);
+}
+
+extern "C" int otp_pointwise_x3_pair_pack(const void* w1, const void* scale1, const void* shift1, const void* w2, const void* scale2,
+                                          const void* shift2, void* packed, int Cin, int Cmid, int Cout2, void* stream) {
+    if (!w1 || !w2 || !packed) return OTP_ERR_BAD_ARG;
+    if (!otp_pointwise_x3_pair_weight_bytes(Cin, Cmid, Cout2)) return OTP_ERR_UNSUPPORTED;
+    // conv3: tile pairs whole, 8 / KS < 2 ? 2 : 8 / KS tiles per block of the pack kernel - the blocks are contiguous either way
+    const int KS = Cin / 32, MPB = 8 / KS < 2 ? 2 : 8 / KS, nblk = (Cmid / 16) / MPB, total = (int)(pxp_w1_bytes(Cin) / 16);
+    hipLaunchKernelGGL(pointx_pack_kernel, dim3(otp_ceil_div(total, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const float*>(w1), static_cast<const float*>(scale1), static_cast<const float*>(shift1),
+                       static_cast<unsigned char*>(packed), Cin, Cin, Cmid, nblk, 1);
+    const int rc = otp_launch_status();
+    if (rc) return rc;
+    return px_pack(w2, scale2, shift2, static_cast<unsigned char*>(packed) + pxp_w1_bytes(Cin), Cmid, Cout2, 1, stream);
+}
+
+extern "C" int otp_pointwise_x3_pair(const void* x, const void* packed, const void* res, void* out, void* out_s8, int B, int Cin,
+                                     int Cmid, int Cout2, int T, int x_ctot, int x_coff, int res_ctot, int res_coff, int out_ctot,
+                                     int out_coff, int relu1, int relu2, void* stream) {
+    if (!x || !packed || !out || !out_s8 || B <= 0) return OTP_ERR_BAD_ARG;
+    if (!otp_pointwise_x3_pair_supported(Cin, Cmid, Cout2, T)) return OTP_ERR_UNSUPPORTED;
+    // the two forms layer1 has: 64 -> 256 + residual (a Bottleneck's conv3), 128 -> 256 without (the first block's folded shortcut)
+    if ((Cin == 64) != (res != nullptr)) return OTP_ERR_UNSUPPORTED;
+    if (x_coff < 0 || x_coff + Cin > x_ctot || out_coff < 0 || out_coff + Cmid > out_ctot ||
+        (res && (res_coff < 0 || res_coff + Cmid > res_ctot)))
+        return OTP_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(out)) & 7 ||
+        (reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(out_s8)) & 15)
+        return OTP_ERR_BAD_ARG;
+    PxPairArgs a;
+    a.x = static_cast<const float*>(x);
+    a.w1 = static_cast<const unsigned char*>(packed);
+    a.w2 = a.w1 + pxp_w1_bytes(Cin);
+    a.res = static_cast<const float*>(res);
+    a.out = static_cast<float*>(out);
+    a.out_s8 = static_cast<float*>(out_s8);
+    a.T = T, a.tiles_per_b = otp_ceil_div(T, 128), a.relu1 = relu1 ? 1 : 0, a.relu2 = relu2 ? 1 : 0;
+    a.x_ctot = x_ctot, a.x_coff = x_coff, a.r_ctot = res_ctot, a.r_coff = res_coff, a.o_ctot = out_ctot, a.o_coff = out_coff;
+    a.rflag = otp_range_word();
+    const dim3 grid((unsigned)(B * a.tiles_per_b));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (Cin == 64) hipLaunchKernelGGL((pointx_pair_kernel<64, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((pointx_pair_kernel<128, false>), grid, dim3(256), 0, st, a);
     return otp_launch_status();
 }

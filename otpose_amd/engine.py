@@ -48,6 +48,8 @@ class InferenceEngine:
         self.W_img, self.H_img = cfg.MODEL.IMAGE_SIZE
         self.h, self.w = model.pe_h, model.pe_w
         self.ops: List[Callable] = []
+        self._pair_s8 = {}                    # id(NCHW tensor) -> S8 image of the next Bottleneck's conv1, written with it (pointx_pair)
+        self.l1_pairs = 0                     # conv3 + next conv1 pair launches emitted (tests)
         self._aux = {}                        # id(NCHW tensor) -> {"s8", "c4", "nchw_needed"}: S8 / C4 images written by its producer
         self._keep = []                       # parameter-derived tensors that must outlive the ops
         self._bufs = []                       # every activation buffer (see new())
@@ -574,19 +576,55 @@ class InferenceEngine:
         self._emit(run)
         return out
 
+    def _conv1_conv2_s8_ok(self, xc, n, h, w, conv1, conv2) -> bool:
+        """Shape test of :meth:`conv1_conv2_s8` for an input of ``xc`` channels (the conv's own buffer as output)."""
+        if not (self.use_s8 and self.use_pointx and os.environ.get("OTPOSE_L1_S8", "1") != "0"):
+            return False
+        c1i, c1o, c2o = conv1.in_channels, conv1.out_channels, conv2.out_channels
+        if (conv1.kernel_size != (1, 1) or conv1.stride != (1, 1) or conv1.padding != (0, 0) or conv1.bias is not None
+                or conv1.groups != 1 or conv2.kernel_size != (3, 3) or conv2.stride != (1, 1) or conv2.padding != (1, 1)
+                or conv2.dilation != (1, 1) or conv2.bias is not None or conv2.groups != 1 or conv2.in_channels != c1o
+                or xc != c1i or not ops.pointwise_x3_s8_supported(c1i, c1o, h * w)):
+            return False
+        return bool(ops.s8_conv_supported(ops.s8_conv_desc(n, c1o, c2o, h, w, ACT_RELU)))
+
+    def pointx_pair(self, inp: View, weight, sc, sh, res: View, nxt):
+        """relu(sc * conv1x1(inp) + sh (+ res)) in front of Bottleneck ``nxt`` (a layer1 block boundary, HRNet.py:551-571) with
+        nxt's conv1 + bn1 + relu in the same launch (csrc/pointx.hip, pointx_pair_kernel): the 256-channel tensor is written for
+        nxt's residual and not read back, nxt's conv1_conv2_s8 finds the S8 image of its conv1 ready.  The same bits as the two
+        launches; OTPOSE_L1_PAIR=0 keeps those.  Returns None when either convolution is not of that shape."""
+        if not (self.use_pointx and not self._exact and os.environ.get("OTPOSE_L1_PAIR", "1") != "0"):
+            return None
+        w = self.dev_param(weight)
+        n, _, h, wd = inp.t.shape
+        cmid, cin = w.shape[:2]
+        c1 = nxt.conv1
+        if (w.dim() == 4 and tuple(w.shape[2:]) != (1, 1)) or inp.C != cin or (res is not None and res.C != cmid) \
+                or not ops.pointwise_x3_supported(cin, cmid, h * wd) or not self._conv1_conv2_s8_ok(cmid, n, h, wd, c1, nxt.conv2) \
+                or not ops.pointwise_x3_pair_supported(cin, cmid, c1.out_channels, h * wd) or (cin == 64) != (res is not None):
+            return None
+        for v_ in (inp, res):
+            self._needs_nchw(v_)
+        sc1, sh1 = self._bn_fold(nxt.bn1)
+        pk = ops.pack_pointwise_x3_pair(w, sc, sh, self.dev_param(c1.weight), sc1, sh1)
+        out = View(self.new(n, cmid, h, wd))
+        y8 = self.new(n * c1.out_channels * h * wd)
+        self._keep.append(pk)
+        self._pair_s8[id(out.t)] = y8
+        self.l1_pairs += 1
+        self.call(self.lib.otp_pointwise_x3_pair, "otp_pointwise_x3_pair", hip.ptr(inp.t), hip.ptr(pk),
+                  hip.ptr(res.t if res is not None else None), hip.ptr(out.t), hip.ptr(y8), n, cin, cmid, c1.out_channels, h * wd,
+                  inp.ctot, inp.coff, res.ctot if res is not None else 0, res.coff if res is not None else 0, out.ctot, out.coff, 1, 1)
+        return out
+
     def conv1_conv2_s8(self, x: View, conv1, bn1, conv2, bn2, out: View = None):
         """relu(bn2(conv2(relu(bn1(conv1(x)))))) of a Bottleneck (HRNet.py:551-571: 1x1 then 3x3) with the intermediate kept as S8
         records: conv1 on csrc/pointx.hip writes the operand records of csrc/convs.hip, conv2 reads them and writes fp32 NCHW -
         no fp32 round trip of the 64-channel tensor and the S8 conv kernel instead of the implicit-GEMM one (179 -> 115 us at
         cfg2).  Returns None when the pair is not of that shape."""
-        if not (self.use_s8 and self.use_pointx and os.environ.get("OTPOSE_L1_S8", "1") != "0"):
-            return None
         n, _, h, w = x.t.shape
         c1i, c1o, c2o = conv1.in_channels, conv1.out_channels, conv2.out_channels
-        if (conv1.kernel_size != (1, 1) or conv1.stride != (1, 1) or conv1.padding != (0, 0) or conv1.bias is not None
-                or conv1.groups != 1 or conv2.kernel_size != (3, 3) or conv2.stride != (1, 1) or conv2.padding != (1, 1)
-                or conv2.dilation != (1, 1) or conv2.bias is not None or conv2.groups != 1 or conv2.in_channels != c1o
-                or x.C != c1i or not ops.pointwise_x3_s8_supported(c1i, c1o, h * w)):
+        if not self._conv1_conv2_s8_ok(x.C, n, h, w, conv1, conv2):
             return None
         if out is None:
             out = View(self.new(n, c2o, h, w))
@@ -594,23 +632,27 @@ class InferenceEngine:
         if not ops.s8_conv_supported(d2):
             return None
         L = self.lib
-        self._needs_nchw(x)
-        sc1, sh1 = self._bn_fold(bn1)
         sc2, sh2 = self._bn_fold(bn2)
-        pk = ops.pack_pointwise_x3_s8(self.dev_param(conv1.weight), sc1, sh1)
         w2 = self._pack_s8(conv2, sc2, d2)
-        y8 = self.new(n * c1o * h * w)
-        self._keep += [pk, w2, d2]
-        self.call(L.otp_pointwise_x3_s8, "otp_pointwise_x3_s8", hip.ptr(x.t), hip.ptr(pk), hip.ptr(y8), n, c1i, c1o, h * w, x.ctot,
-                  x.coff, 1)
+        y8 = self._pair_s8.pop(id(x.t), None)          # conv1's S8 image, already written by the launch that wrote x (pointx_pair)
+        if y8 is None:
+            self._needs_nchw(x)
+            sc1, sh1 = self._bn_fold(bn1)
+            pk = ops.pack_pointwise_x3_s8(self.dev_param(conv1.weight), sc1, sh1)
+            y8 = self.new(n * c1o * h * w)
+            self._keep.append(pk)
+            self.call(L.otp_pointwise_x3_s8, "otp_pointwise_x3_s8", hip.ptr(x.t), hip.ptr(pk), hip.ptr(y8), n, c1i, c1o, h * w,
+                      x.ctot, x.coff, 1)
+        self._keep += [w2, d2]
         self.call(L.otp_conv3x3_s8, "otp_conv3x3_s8", hip.ptr(y8), hip.ptr(w2), hip.ptr(sh2), None, hip.ptr(out.t), ops.S8_F32_NCHW,
                   None, d2)
         return out
 
-    def bottleneck(self, blk, x: View, s8_only=False) -> View:
+    def bottleneck(self, blk, x: View, s8_only=False, nxt=None) -> View:
         """One Bottleneck (model/HRNet.py:551-571).  ``s8_only``: the result is wanted as S8 records (transition1's convs read
         them) - conv3 writes them straight from its accumulators (csrc/pointx.hip) and the NCHW tensor of the returned view is
-        filled, by a conversion pass, only if some consumer asks for it."""
+        filled, by a conversion pass, only if some consumer asks for it.  ``nxt``: the Bottleneck that follows - its conv1 rides
+        on this block's conv3 launch (:meth:`pointx_pair`)."""
         res = x
         if blk.downsample is not None:
             # the 1x1 shortcut only needs x: a side stream next to conv1 / conv2
@@ -648,6 +690,12 @@ class InferenceEngine:
                     hip.check(L.otp_s8_unpack(hip.ptr(o8), hip.ptr(out.t), n, co, h, w, self._stream), "otp_s8_unpack")
             self._emit(run)
             return out
+        if (nxt is not None and c3.kernel_size == (1, 1) and c3.stride == (1, 1) and c3.padding == (0, 0) and c3.bias is None
+                and c3.groups == 1):
+            sc, sh = self._bn_fold(blk.bn3)
+            out = self.pointx_pair(y, c3.weight, sc, sh, res, nxt)
+            if out is not None:
+                return out
         return self.conv_bn(y, blk.conv3, blk.bn3, ACT_RELU, res=res)
 
     def hr_module(self, mod, xs: List[View], fork_in=True, join_out=True) -> List[View]:
@@ -793,15 +841,17 @@ class InferenceEngine:
             wd, shd = fold(b0.downsample[0], b0.downsample[1])
             w3, sh3 = fold(b0.conv3, b0.bn3)
             cout = b0.conv3.out_channels
-            x = self.conv(View(cat), torch.cat([wd, w3], 1), View(self.new(n, cout, ho, wo)),
-                          scale=torch.ones(cout, device=self.dev), shift=shd + sh3, act=ACT_RELU)
+            wcat, ones, shcat = torch.cat([wd, w3], 1), torch.ones(cout, device=self.dev), shd + sh3
+            x = self.pointx_pair(View(cat), wcat, ones, shcat, None, blocks[1]) if len(blocks) > 1 else None
+            if x is None:
+                x = self.conv(View(cat), wcat, View(self.new(n, cout, ho, wo)), scale=ones, shift=shcat, act=ACT_RELU)
             blocks = blocks[1:]
         else:
             x = self.conv_bn(x, net.conv2, net.bn2, ACT_RELU)
         t1_s8 = self.use_s8 and not self._exact and os.environ.get("OTPOSE_T1_S8", "1") != "0" \
             and os.environ.get("OTPOSE_S8_STRIDE2", "1") != "0"
         for bi, blk in enumerate(blocks):
-            x = self.bottleneck(blk, x, s8_only=t1_s8 and bi == len(blocks) - 1)
+            x = self.bottleneck(blk, x, s8_only=t1_s8 and bi == len(blocks) - 1, nxt=blocks[bi + 1] if bi + 1 < len(blocks) else None)
         ys = [x]
         for s in (2, 3, 4):
             trans = getattr(net, f"transition{s - 1}")

@@ -868,6 +868,48 @@ def pointwise_x3_s8(x: View, packed, cout, out_s8=None, relu=False, stream=None,
     return out_s8
 
 
+def pointwise_x3_pair_supported(cin, cmid, cout2, t) -> bool:
+    return bool(hip.lib().otp_pointwise_x3_pair_supported(int(cin), int(cmid), int(cout2), int(t)))
+
+
+def pack_pointwise_x3_pair(weight1, scale1, shift1, weight2, scale2=None, shift2=None):
+    """Weight image of :func:`pointwise_x3_pair`: conv3 (Cmid, Cin) of one Bottleneck and conv1 (Cout2, Cmid) of the next, each
+    with its folded BatchNorm - the two images of :func:`pack_pointwise_x3_s8` in one buffer."""
+    _require_gpu(weight1, weight2)
+    cmid, cin = weight1.shape[:2]
+    cout2 = weight2.shape[0]
+    L = hip.lib()
+    nbytes = L.otp_pointwise_x3_pair_weight_bytes(cin, cmid, cout2) if weight2.shape[1] == cmid else 0
+    if not nbytes:
+        raise RuntimeError(f"otp_pointwise_x3_pair: unsupported weight shapes {tuple(weight1.shape)}, {tuple(weight2.shape)}")
+    f = lambda t: None if t is None else t.detach().to(weight1.device, torch.float32).contiguous()   # noqa: E731
+    ws = []
+    for wt, sc, sh, co, ci in ((weight1, scale1, shift1, cmid, cin), (weight2, scale2, shift2, cout2, cmid)):
+        w, sc, sh = f(wt).reshape(co, ci), f(sc), f(sh)
+        e = x3_weight_exponent(w)                 # weights stored times 2^e, undone by the kernel's per-channel epilogue scale
+        if e:
+            w, sc = w * float(2.0 ** e), _scaled_vec(sc, -e, co, w.device)
+        ws += [w, sc, sh]
+    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=weight1.device)
+    hip.check(L.otp_pointwise_x3_pair_pack(*[hip.ptr(t) for t in ws], hip.ptr(packed), cin, cmid, cout2, hip.stream_of(ws[0])),
+              "otp_pointwise_x3_pair_pack")
+    return packed
+
+
+def pointwise_x3_pair(x: View, packed, out: View, cout2, res: View = None, out_s8=None, relu1=True, relu2=True, stream=None):
+    """out = act1(scale1 * (W1 . x) + shift1 (+ res)) as :func:`pointwise_x3` writes it AND the S8 image of
+    act2(scale2 * (W2 . out) + shift2) as :func:`pointwise_x3_s8` of ``out`` writes it, in one launch; returns the S8 image."""
+    _require_gpu(x.t, out.t)
+    b, _, h, w = x.t.shape
+    out_s8 = s8_empty(b, cout2, h, w, x.t.device) if out_s8 is None else out_s8
+    hip.check(hip.lib().otp_pointwise_x3_pair(hip.ptr(x.t), hip.ptr(packed), hip.ptr(res.t if res is not None else None),
+                                              hip.ptr(out.t), hip.ptr(out_s8), b, x.C, out.C, cout2, h * w, x.ctot, x.coff,
+                                              res.ctot if res is not None else 0, res.coff if res is not None else 0, out.ctot,
+                                              out.coff, int(bool(relu1)), int(bool(relu2)),
+                                              stream if stream is not None else hip.stream_of(x.t)), "otp_pointwise_x3_pair")
+    return out_s8
+
+
 def pack_qkv_table(dwq, dwk, dwv, gq, bq, gk, bk, gv, bv):
     """Depthwise (C, 1, 3) weights and LayerNorm (C) gamma / beta of MaskedMHCA's query / key / value paths
     (model/blocks.py:359-381) -> the per-channel table of :func:`qkv_front`."""

@@ -36,3 +36,41 @@ for cin, cout, res in ((256, 64, False), (64, 256, True), (128, 256, False), (64
     byts = 4.0 * n * h * w * (cin + cout * (2 if res else 1))
     print("%3d -> %3d%s: pointx %.1f us (%.2f TB/s), convx 1x1 %.1f us; max |diff| %.2e of %.2f" % (
         cin, cout, " + res" if res else "", ts[0], byts / ts[0] / 1e6, ts[1], float((o1 - o2).abs().max()), float(o2.abs().max())))
+
+
+def _time(f, reps=20):
+    for _ in range(3):
+        f()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        f()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps * 1e3
+
+
+# conv3 of a Bottleneck + conv1 of the next as one launch (pointx_pair_kernel) against the two launches it replaces; algorithmic
+# bytes of the pair: the input, the residual, the 256-channel tensor written once, the 64-channel S8 image
+cmid, cout2 = 256, 64
+for cin, res in ((64, True), (128, False)):
+    x = torch.randn(n, cin, h, w, device="cuda")
+    w1, w2 = torch.randn(cmid, cin, device="cuda") / cin ** 0.5, torch.randn(cout2, cmid, device="cuda") / cmid ** 0.5
+    sc1, sh1 = torch.rand(cmid, device="cuda") + 0.5, torch.randn(cmid, device="cuda")
+    sc2, sh2 = torch.rand(cout2, device="cuda") + 0.5, torch.randn(cout2, device="cuda")
+    r = torch.randn(n, cmid, h, w, device="cuda") if res else None
+    xv, rv = ops.View(x), (ops.View(r) if res else None)
+    oa, ob = torch.empty(n, cmid, h, w, device="cuda"), torch.empty(n, cmid, h, w, device="cuda")
+    s8a, s8b = ops.s8_empty(n, cout2, h, w, x.device), ops.s8_empty(n, cout2, h, w, x.device)
+    pk1, pk2 = ops.pack_pointwise_x3(w1, sc1, sh1), ops.pack_pointwise_x3_s8(w2, sc2, sh2)
+    pkp = ops.pack_pointwise_x3_pair(w1, sc1, sh1, w2, sc2, sh2)
+    g1 = lambda: ops.pointwise_x3(xv, pk1, ops.View(oa), rv, True)                        # noqa: E731
+    g2 = lambda: ops.pointwise_x3_s8(ops.View(oa), pk2, cout2, out_s8=s8a, relu=True)     # noqa: E731
+    gp = lambda: ops.pointwise_x3_pair(xv, pkp, ops.View(ob), cout2, res=rv, out_s8=s8b)  # noqa: E731
+    byts = 4.0 * n * h * w * (cin + cmid * (2 if res else 1) + cout2)
+    for rep in range(3):
+        t1, t2, tp = _time(g1), _time(g2), _time(gp)
+        print("pair %3d -> 256%s -> 64, rep %d: two launches %.1f + %.1f = %.1f us, pair launch %.1f us (%.2f TB/s of %.2f GB)" % (
+            cin, " + res" if res else "", rep, t1, t2, t1 + t2, tp, byts / tp / 1e6, byts / 1e9))
+    print("    bit-identical: fp32 %s, S8 %s" % (torch.equal(oa, ob), torch.equal(s8a, s8b)))

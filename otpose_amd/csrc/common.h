@@ -36,6 +36,21 @@ static inline int otp_launch_status() {
 
 static inline int otp_ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// the vector types of every kernel file (16-bit element vectors: otp_x3x2 / otp_x3x8 below; csrc/h16.hip and csrc/nhwc.hip keep
+// their own element type, switched by OTP_H16_BF16)
+typedef float otp_f32x4 __attribute__((ext_vector_type(4)));
+typedef float otp_f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int otp_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int otp_u32x2 __attribute__((ext_vector_type(2)));
+
+// ---- index arithmetic --------------------------------------------------------------------------------------------------------
+// floor(i / d) for i * d < 2^32 with magic = floor(2^32 / d) + 1 (0 encodes d == 1); the host side computes the magic number
+__device__ __forceinline__ uint32_t otp_magic_div(uint32_t i, uint32_t magic) { return magic ? __umulhi(i, magic) : i; }
+static inline uint32_t otp_magic(uint32_t d) { return d <= 1 ? 0u : (uint32_t)((1ull << 32) / d) + 1u; }   // exact while i * d < 2^32
+// a * b for per-lane index arithmetic whose operands stay below 2^24 (checked by the plans): v_mul_u32_u24 issues at full rate,
+// v_mul_lo_u32 at a quarter of it - 40 of them sat in the set-up of every tile of csrc/h16.hip
+__device__ __forceinline__ int otp_mul24(int a, int b) { return (int)__umul24((unsigned)a, (unsigned)b); }
+
 // wave64 reductions (DPP-lowered __shfl_xor)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -47,11 +62,60 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+__device__ __forceinline__ float otp_kslot_sum(float v) {  // sum over the four k-slot lane groups (lanes n, n+16, n+32, n+48)
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
+// sum over the 16 lanes of a DPP row (one MFMA pixel column group) with four VALU adds; every lane ends with the total.
+// (__shfl_xor with offsets 4 and 8 lowers to ds_bpermute on gfx950: 96 LDS round trips in the old epilogue of csrc/nhwc.hip)
+template <int CTRL>
+__device__ __forceinline__ float otp_dpp_mov(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
+}
+__device__ __forceinline__ float otp_row16_sum(float v) {
+    v += otp_dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
+    v += otp_dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
+    v += otp_dpp_mov<0x124>(v);   // row_ror:4
+    v += otp_dpp_mov<0x128>(v);   // row_ror:8
+    return v;
+}
+
+// ---- GELU ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float otp_gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
+// erf-GELU on a pair of accumulator values, branch-free and in packed-f32 form (v_pk_fma_f32): erf(t) = t P(t^2) / Q(t^2)
+// on |t| <= 4 (the classic single-precision rational fit; erf is 1 - 1.5e-8 beyond), max abs error 4.2e-7 on erf and
+// 7e-7 on gelu(x) over the whole real line - checked against fp64 in tests/test_gpu_ops.py.  The libm erff the other
+// epilogues call has two data-dependent paths, and both would run for every accumulator register of a wave in the MLP
+// kernels (csrc/mlp.hip, csrc/mlpx.hip).
+__device__ __forceinline__ otp_f32x2 otp_gelu2(otp_f32x2 x) {
+    otp_f32x2 t = x * 0.70710678118654752440f;
+    t.x = __builtin_amdgcn_fmed3f(t.x, -4.f, 4.f);
+    t.y = __builtin_amdgcn_fmed3f(t.y, -4.f, 4.f);
+    const otp_f32x2 t2 = t * t;
+    otp_f32x2 p = t2 * -2.72614225801306e-10f + 2.77068142495902e-08f;
+    p = p * t2 + -2.10102402082508e-06f;
+    p = p * t2 + -5.69250639462346e-05f;
+    p = p * t2 + -7.34990630326855e-04f;
+    p = p * t2 + -2.95459980854025e-03f;
+    p = p * t2 + -1.60960333262415e-02f;
+    p = p * t;
+    otp_f32x2 q = t2 * -1.45660718464996e-05f + -2.13374055278905e-04f;
+    q = q * t2 + -1.68282697438203e-03f;
+    q = q * t2 + -7.37332916720468e-03f;
+    q = q * t2 + -1.42647390514189e-02f;
+    otp_f32x2 r;
+    r.x = __builtin_amdgcn_rcpf(q.x);
+    r.y = __builtin_amdgcn_rcpf(q.y);
+    const otp_f32x2 e = p * r, hx = x * 0.5f;
+    return hx * e + hx;
+}
 
 // ---- buffer (SRSRC) addressing: one VGPR byte offset + one SGPR byte offset per access -------------
 // gfx9-family dword3 (DST_SEL/format) constant for raw buffers
 #define OTP_BUFFER_DWORD3 0x00020000
 typedef __amdgpu_buffer_rsrc_t otp_rsrc;
+constexpr int OTP_OOB = -16;              // byte offset outside every descriptor: a load returns zeros, the LDS-DMA writes zeros, a store is dropped
 __device__ __forceinline__ otp_rsrc make_rsrc(const void* p, size_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0,
                                              (int)(bytes > 0xffffffffull ? 0xffffffffull : bytes), OTP_BUFFER_DWORD3);
@@ -63,8 +127,6 @@ __device__ __forceinline__ otp_rsrc make_rsrc32(const void* p, unsigned bytes) {
 __device__ __forceinline__ float bload(otp_rsrc r, int voff_bytes, int soff_bytes) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff_bytes, soff_bytes, 0));
 }
-typedef float otp_f32x4 __attribute__((ext_vector_type(4)));
-typedef float otp_f32x2 __attribute__((ext_vector_type(2)));
 
 // ---- the 16-bit operand type of the split ("x3") products ------------------------------------------------------------------
 // Every fp32 operand a of the convolutions / projections / MLPs / attention products of the eval path is carried as two 16-bit
@@ -87,7 +149,6 @@ typedef otp_x3_t otp_x3x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ otp_f32x2 otp_x3_widen(uint32_t pair) {
     return __builtin_convertvector(__builtin_bit_cast(otp_x3x2, pair), otp_f32x2);
 }
-typedef unsigned int otp_u32x4 __attribute__((ext_vector_type(4)));
 
 // ---- range guard of the 16-bit-operand kernels (csrc/range.hip) ----------------------------------------------------------------
 // A half piece overflows at 65504: hi = rne(a) = inf, lo = rne(a - hi) = -inf, every product with it NaN - and a ReLU (v_max_f32
@@ -127,4 +188,22 @@ __device__ __forceinline__ otp_f32x4 bload4(otp_rsrc r, int voff_bytes) {
 }
 __device__ __forceinline__ void bstore(float v, otp_rsrc r, int voff_bytes, int soff_bytes) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), r, voff_bytes, soff_bytes, 0);
+}
+
+// ---- LDS-DMA ----------------------------------------------------------------------------------------------------------------------
+// copy one block of BLKB bytes (a multiple of 1 KB) global -> LDS with the LDS-DMA (global_load_lds, no staging registers), all NTHR
+// threads of the workgroup: unit u (16 bytes) lands at lds + 16 u; a wave-instruction covers 64 units, so it is inside the block
+// or past it, and the bound test exists only when the last pass of the workgroup is partial
+template <int NTHR, int BLKB>
+__device__ __forceinline__ void otp_lds_stage(const unsigned char* __restrict__ src, unsigned char* lds) {
+    constexpr int UNITS = BLKB / 16, NST = (UNITS + NTHR - 1) / NTHR;
+    static_assert(BLKB % 1024 == 0, "whole wave-instructions");
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+#pragma unroll
+    for (int i = 0; i < NST; ++i) {
+        const int u0 = i * NTHR + wave * 64;                       // wave-uniform first unit of this wave-instruction
+        if (UNITS % NTHR != 0 && u0 * 16 >= BLKB) break;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)(u0 + lane) * 16),
+                                         (__attribute__((address_space(3))) void*)(lds + u0 * 16), 16, 0, 0);
+    }
 }

@@ -30,14 +30,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
-
-// floor(i / d) for i * d < 2^32 with magic = floor(2^32 / d) + 1 (0 encodes d == 1)
-__device__ __forceinline__ uint32_t fdiv(uint32_t i, uint32_t magic) { return magic ? __umulhi(i, magic) : i; }
-uint32_t magic_of(uint32_t d) { return d <= 1 ? 0u : (uint32_t)((1ull << 32) / d) + 1u; }
-
 constexpr int MAXJI_LIN = 10, MAXJI_GEN = 10, MAXJW = 5;   // float4 prefetch registers per thread: input windows / weight slab of a chunk
 
 struct WinPlan {
@@ -95,7 +87,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_kernel(
         const int per = 8 * P.nM;
         const int g = t / per, r = t - g * per;
         const int pt = g * 8 + (r & 7);
-        T.n = (int)fdiv((uint32_t)pt, P.magicTpi);
+        T.n = (int)otp_magic_div((uint32_t)pt, P.magicTpi);
         T.q0 = (pt - T.n * P.tiles_per_img) * P.Ptile;
         T.m_wg = (r >> 3) * P.Mtile;
         return T;
@@ -107,13 +99,13 @@ __global__ __launch_bounds__(256, 2) void conv_win_kernel(
     // the hardware range check zero-fills rows above / below the image and missing channels, so a load costs one
     // v_add.  Weights: item w = tid + j*nthreads of the [KK*CK][M4] slab of this M tile; byte offset inside the
     // (chunk, M tile) slice of the packed tensor and LDS offset are computed once per kernel.
-    f32x4 pfi[MAXJI], pfw[MAXJW];
+    otp_f32x4 pfi[MAXJI], pfw[MAXJW];
     int wvoff[MAXJW], wdst[MAXJW];
 #pragma unroll
     for (int j = 0; j < MAXJW; ++j) {
         const uint32_t w = tid + j * P.nthreads;
-        const uint32_t row = fdiv(w, P.magicM4), m4 = w - row * P.M4;
-        const uint32_t tap = fdiv(row, P.magicCK), c = row - tap * P.CK;
+        const uint32_t row = otp_magic_div(w, P.magicM4), m4 = w - row * P.M4;
+        const uint32_t tap = otp_magic_div(row, P.magicCK), c = row - tap * P.CK;
         const bool live = j < P.NJW && w < (uint32_t)P.NW4;
         wvoff[j] = live ? (int)((tap * P.Cin + c) * P.Cout16 + 4 * m4) * 4 : -1;
         wdst[j] = live ? (int)(P.CK * P.CS + row * P.MS + 4 * m4) : -1;
@@ -128,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_kernel(
             img = in + ((size_t)T.n * P.in_ctot + P.in_coff) * P.HW;
         }
         // first needed position of the flattened plane, rounded down to 16 bytes (may be negative)
-        const int y_first = P.flat ? 0 : (int)fdiv((uint32_t)T.q0, P.magicWo);
+        const int y_first = P.flat ? 0 : (int)otp_magic_div((uint32_t)T.q0, P.magicWo);
         const int f0a = (P.flat ? T.q0 : (y_first * P.stride - P.pad) * P.W) & ~3;
         const int vbase = (f0a + 4 * lane) * 4;
         int jc = 0, jr = 0;
@@ -157,13 +149,13 @@ __global__ __launch_bounds__(256, 2) void conv_win_kernel(
         for (int j = 0; j < MAXJI; ++j) {
             if (j < P.NJI) {
                 const int c = wave * P.CKW + jc, r4 = lane + 64 * jr;
-                if (c < P.CK && r4 < P.L4) *reinterpret_cast<f32x4*>(inp + c * P.CS + P.G + 4 * r4) = pfi[j];
+                if (c < P.CK && r4 < P.L4) *reinterpret_cast<otp_f32x4*>(inp + c * P.CS + P.G + 4 * r4) = pfi[j];
                 if (++jr == P.JR) { jr = 0; ++jc; }
             }
         }
 #pragma unroll
         for (int j = 0; j < MAXJW; ++j)
-            if (j < P.NJW && wdst[j] >= 0) *reinterpret_cast<f32x4*>(smem + wdst[j]) = pfw[j];
+            if (j < P.NJW && wdst[j] >= 0) *reinterpret_cast<otp_f32x4*>(smem + wdst[j]) = pfw[j];
     };
 
     // ---- lane geometry of the current tile ------------------------------------------------------------------------
@@ -175,7 +167,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_kernel(
     int poff[PB];
     uint32_t cm0 = 0, cm1 = 0, cm2 = 0;
 
-    f32x4 acc[MB][PB];
+    otp_f32x4 acc[MB][PB];
 
     // ---- epilogue: scale/shift (+res) (+act), optional nearest-upsample accumulate --------------------------
     // The accumulators of one 16-row block go through a per-wave LDS tile [16][RS] (lane = pixel column, so a
@@ -222,13 +214,13 @@ __global__ __launch_bounds__(256, 2) void conv_win_kernel(
                 constexpr int EB = 2;                  // loads of a batch are issued before its first store
 #pragma unroll
                 for (int it0 = 0; it0 < PB; it0 += EB) {
-                    f32x4 v[EB], rv[EB];
+                    otp_f32x4 v[EB], rv[EB];
 #pragma unroll
                     for (int e = 0; e < EB; ++e) {
                         if (it0 + e < PB) {
                             const int q = q_lane + 16 * (it0 + e);
-                            v[e] = *reinterpret_cast<const f32x4*>(ep_row + 16 * (it0 + e));
-                            if (res && obytes && q < P.HoWo) rv[e] = *reinterpret_cast<const f32x4*>(rrow + q);
+                            v[e] = *reinterpret_cast<const otp_f32x4*>(ep_row + 16 * (it0 + e));
+                            if (res && obytes && q < P.HoWo) rv[e] = *reinterpret_cast<const otp_f32x4*>(rrow + q);
                         }
                     }
 #pragma unroll
@@ -236,14 +228,14 @@ __global__ __launch_bounds__(256, 2) void conv_win_kernel(
                         if (it0 + e < PB) {
                             const int q = q_lane + 16 * (it0 + e);
                             const bool ok = obytes && q < P.HoWo;
-                            f32x4 o = v[e] * sc + sh;
+                            otp_f32x4 o = v[e] * sc + sh;
                             if (res && ok) o += rv[e];
                             if (P.act == OTP_ACT_RELU) {
                                 o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
                             } else if (P.act == OTP_ACT_GELU) {
-                                o.x = gelu_erf(o.x); o.y = gelu_erf(o.y); o.z = gelu_erf(o.z); o.w = gelu_erf(o.w);
+                                o.x = otp_gelu_erf(o.x); o.y = otp_gelu_erf(o.y); o.z = otp_gelu_erf(o.z); o.w = otp_gelu_erf(o.w);
                             }
-                            if (ok) *reinterpret_cast<f32x4*>(orow + q) = o;
+                            if (ok) *reinterpret_cast<otp_f32x4*>(orow + q) = o;
                         }
                     }
                 }
@@ -269,7 +261,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_kernel(
                                 float v = v0;
                                 if (res) v += res[rb + sub];
                                 if (P.act == OTP_ACT_RELU) v = fmaxf(v, 0.f);
-                                else if (P.act == OTP_ACT_GELU) v = gelu_erf(v);
+                                else if (P.act == OTP_ACT_GELU) v = otp_gelu_erf(v);
                                 out[ob + sub] = v;
                             }
                     }
@@ -297,7 +289,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_kernel(
             // ---- per-tile lane geometry and fresh accumulators ------------------------------------------------------
             const TileId T = decode(tile);
             const int pix_wave = T.q0 + wpi * 16 * PB;
-            const int y_first = P.flat ? 0 : (int)fdiv((uint32_t)T.q0, P.magicWo);
+            const int y_first = P.flat ? 0 : (int)otp_magic_div((uint32_t)T.q0, P.magicWo);
             const int f0 = P.flat ? T.q0 : (y_first * P.stride - P.pad) * P.W;
             const int f0a = f0 & ~3;
             if (LIN) {
@@ -310,7 +302,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_kernel(
                         keepL[pb] = keepR[pb] = -1;
                     } else {
                         const int q = pix_wave + pb * 16 + i16;
-                        const int y = (int)fdiv((uint32_t)q, P.magicWo), x = q - y * P.Wo;
+                        const int y = (int)otp_magic_div((uint32_t)q, P.magicWo), x = q - y * P.Wo;
                         keepL[pb] = (x - P.dil >= 0) ? -1 : 0;
                         keepR[pb] = (x + P.dil < P.W) ? -1 : 0;
                     }
@@ -321,7 +313,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_kernel(
                 for (int pb = 0; pb < PB; ++pb) {
                     int q = pix_wave + pb * 16 + i16;
                     q = q < P.HoWo ? q : T.q0;   // padding lanes compute a valid pixel and are never stored
-                    const int y = (int)fdiv((uint32_t)q, P.magicWo), x = q - y * P.Wo;
+                    const int y = (int)otp_magic_div((uint32_t)q, P.magicWo), x = q - y * P.Wo;
                     poff[pb] = P.G + (f0 - f0a) - P.pad + (y - y_first) * P.stride * P.W + x * P.stride;
                     const int xi = x * P.stride - P.pad;
                     m0 |= (xi >= 0 && xi < P.W) ? 1u << pb : 0u;
@@ -333,7 +325,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_kernel(
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-                for (int pb = 0; pb < PB; ++pb) acc[mb][pb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                for (int pb = 0; pb < PB; ++pb) acc[mb][pb] = (otp_f32x4){0.f, 0.f, 0.f, 0.f};
         }
         // ---- next step: next chunk of this tile, else first chunk of the next tile, else none ---------------------
         const bool last_chunk = c0 + P.CK >= P.Cin;
@@ -506,11 +498,11 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(
     }
     const int kl = lane >> 4;                   // k index of this lane inside a K-step of 4
 
-    f32x4 acc[MB][PB];
+    otp_f32x4 acc[MB][PB];
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-        for (int pb = 0; pb < PB; ++pb) acc[mb][pb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int pb = 0; pb < PB; ++pb) acc[mb][pb] = (otp_f32x4){0.f, 0.f, 0.f, 0.f};
 
     for (int c0 = 0; c0 < d.Cin; c0 += P.CK) {
         __syncthreads();
@@ -617,7 +609,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(
                             float v = fmaf(acc[mb][pb][r], sc, sh);
                             if (res) v += res[rbase + qhi[pb]];
                             if (d.act == OTP_ACT_RELU) v = fmaxf(v, 0.f);
-                            else if (d.act == OTP_ACT_GELU) v = gelu_erf(v);
+                            else if (d.act == OTP_ACT_GELU) v = otp_gelu_erf(v);
                             out[obase + qhi[pb]] = v;
                         }
                     }
@@ -674,10 +666,10 @@ bool fill_plan(WinPlan& P, const Tile& t, int KS, size_t& lds_bytes) {
     P.ntiles = ((P.nP + 7) / 8) * 8 * P.nM;
     const size_t ep_lds = (size_t)nwaves * 16 * (16 * t.PB + 4) * sizeof(float);
     lds_bytes = best_lds > ep_lds ? best_lds : ep_lds;
-    P.magicM4 = magic_of(P.M4);
-    P.magicCK = magic_of(P.CK);
-    P.magicWo = magic_of(P.Wo);
-    P.magicTpi = magic_of(P.tiles_per_img);
+    P.magicM4 = otp_magic(P.M4);
+    P.magicCK = otp_magic(P.CK);
+    P.magicWo = otp_magic(P.Wo);
+    P.magicTpi = otp_magic(P.tiles_per_img);
     return true;
 }
 

@@ -13,8 +13,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct SmallPlan {
     int N, Cin, H, W, HW, Cout;
     int in_ctot, in_coff, in2_ctot, in2_coff, out_ctot, out_coff, act;

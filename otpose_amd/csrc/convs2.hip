@@ -17,72 +17,12 @@
 // Epilogue: S8 records straight from the accumulators (chain intermediates: conv + BN + ReLU, model/HRNet.py:452-461), or the
 // workgroup's [channels][pixels] tile through the LDS and out as 16-byte stores into a channel slice of an fp32 NCHW tensor,
 // with an NCHW residual added on the way (a fuse row accumulates its terms in place: HRNet.py:488-494) and ReLU after it.
-#include "common.h"
+#include "x3.h"
 #include <cstdlib>
 
 namespace {
 
-typedef otp_x3x8 h16x8;              // 8 operand pieces of the split products (common.h: IEEE half since round 4)
-typedef otp_x3x2 h16x2;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-// ---- shared conventions of csrc/convs.hip (weight image, row permutation of a cout-tile pair) -----------------------------------
-__host__ __device__ constexpr int swch(int ntw) { return 8 * ntw + ntw; }     // 1 KB pieces of a chunk's packed weights
-constexpr int SKS = 5;                    // k-steps per 16-channel chunk: 18 (tap, group) slots of 8 channels in 5 x 4
-constexpr int SOOB = -16;                 // buffer offset outside every descriptor: the load returns / writes zeros
 constexpr int MAXJ = 4;                   // 64-record window pieces per wave and plane (window planes of at most 1024 records)
-
-__device__ __forceinline__ uint32_t sdiv(uint32_t i, uint32_t magic) { return magic ? __umulhi(i, magic) : i; }
-uint32_t smagic(uint32_t d) { return d <= 1 ? 0u : (uint32_t)((1ull << 32) / d) + 1u; }   // exact while i * d < 2^32
-
-__device__ __forceinline__ void ssplit8(const float (&v)[8], u32x4& hi, u32x4& lo) {
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x2 a = {v[2 * i], v[2 * i + 1]};
-        const h16x2 ah = __builtin_convertvector(a, h16x2);
-        const uint32_t hb = __builtin_bit_cast(uint32_t, ah);
-        const f32x2 af = otp_x3_widen(hb);
-        const h16x2 al = __builtin_convertvector(a - af, h16x2);
-        h[i] = hb;
-        l[i] = __builtin_bit_cast(uint32_t, al);
-    }
-    hi = (u32x4){h[0], h[1], h[2], h[3]};
-    lo = (u32x4){l[0], l[1], l[2], l[3]};
-}
-
-__host__ __device__ inline bool stile_paired(int co_blk, int t, int ntw, int Cout) {
-    const int tb = t | 1;
-    return tb < ntw && co_blk + 16 * tb < Cout;
-}
-__host__ __device__ inline int srow2ch(int co_blk, int t, int row, int ntw, int Cout) {
-    return stile_paired(co_blk, t, ntw, Cout) ? co_blk + 32 * (t >> 1) + 8 * (row >> 2) + 4 * (t & 1) + (row & 3)
-                                               : co_blk + 16 * t + row;
-}
-
-template <int NM, int NR>
-__device__ __forceinline__ void sblock_sched() {
-    if constexpr (NR == 0) {
-        __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-    } else if constexpr (NR >= NM - 1) {
-#pragma unroll
-        for (int g = 0; g < NM - 1; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        if constexpr (NR > NM - 1) __builtin_amdgcn_sched_group_barrier(0x100, NR - (NM - 1), 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    } else {
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, NM / 2 - 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, NR - 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, NM - 1 - NM / 2, 0);
-    }
-}
 
 struct S2Plan {
     int N, C, H, W, HW, Ho, Wo, HWo, Cout, total;      // total = N * Ho * Wo output pixels
@@ -97,13 +37,13 @@ struct S2Plan {
 
 // NCHW: fp32 result (+ residual) into a channel slice of an NCHW tensor; otherwise the S8 image of the result only
 template <int NTW, bool NCHW, int NPT>
-__global__ __launch_bounds__(256, 2) void convs2_kernel(const unsigned char* __restrict__ xs, const u32x4* __restrict__ wpk,
+__global__ __launch_bounds__(256, 2) void convs2_kernel(const unsigned char* __restrict__ xs, const otp_u32x4* __restrict__ wpk,
                                                          const float* __restrict__ shift, const float* res, float* outf,
-                                                         u32x4* outs, const S2Plan P) {
+                                                         otp_u32x4* outs, const S2Plan P) {
     constexpr int BM = 64 * NPT;
-    constexpr int WCH = swch(NTW);
+    constexpr int WCH = otp_s8_wch(NTW);
     constexpr int WBYTES = WCH * 1024;
-    constexpr int NBLK = SKS * NPT;
+    constexpr int NBLK = OTP_S8_KS * NPT;
     constexpr int NM = 3 * NTW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int PL = P.pl;
@@ -120,7 +60,7 @@ __global__ __launch_bounds__(256, 2) void convs2_kernel(const unsigned char* __r
     if (tile >= P.nTiles) return;
     const int P0 = tile * BM;
     const int n0 = P0 / P.HWo, p0 = P0 - n0 * P.HWo;              // (uniform, once per workgroup)
-    const int y0 = (int)sdiv((uint32_t)p0, P.mWo);
+    const int y0 = (int)otp_magic_div((uint32_t)p0, P.mWo);
     const int Vf = n0 * P.VR + 2 * y0;                             // first virtual row of the window: input row 2 y0 - 1
     const int imgB = P.C * P.HW * 4;                               // bytes of one image of the S8 input
     const int co_blk = cb * NTW * 16;
@@ -132,12 +72,12 @@ __global__ __launch_bounds__(256, 2) void convs2_kernel(const unsigned char* __r
     for (int j = 0; j < MAXJ; ++j) {
         const int v = 64 * (wave + 4 * j) + lane;
         vlive[j] = v < P.NV;
-        const int r = (int)sdiv((uint32_t)v, P.mW1), i = v - r * P.W1;
+        const int r = (int)otp_magic_div((uint32_t)v, P.mW1), i = v - r * P.W1;
         const int V = Vf + r;
-        const int n = (int)sdiv((uint32_t)V, P.mVR), yy = V - n * P.VR;
+        const int n = (int)otp_magic_div((uint32_t)V, P.mVR), yy = V - n * P.VR;
         const int col = i <= P.Wo ? 2 * (i - 1) + 1 : 2 * (i - P.Wo - 1);      // odd columns first, then the even ones
         const bool ok = i >= 1 && yy >= 1 && n < P.N;
-        voff[j] = ok ? (n - n0) * imgB + ((yy - 1) * P.W + col) * 16 : SOOB;
+        voff[j] = ok ? (n - n0) * imgB + ((yy - 1) * P.W + col) * 16 : OTP_OOB;
     }
     const size_t left = (size_t)(P.N - n0) * imgB;
     const otp_rsrc rin = make_rsrc32(xs + (size_t)n0 * imgB, left > 0x7fffff00ull ? 0x7fffff00u : (unsigned)left);
@@ -170,11 +110,11 @@ __global__ __launch_bounds__(256, 2) void convs2_kernel(const unsigned char* __r
     const size_t obytes = (size_t)P.N * P.Cout * P.HWo * 4;        // S8 image of the (N, Cout, Ho, Wo) result
     const otp_rsrc rs8 = make_rsrc32(outs, outs ? (unsigned)obytes : 0u);
     const otp_rsrc rsh = make_rsrc32(shift ? shift : reinterpret_cast<const float*>(xs), shift ? (unsigned)(P.Cout * 4) : 0u);
-    int pb[NPT], toff[SKS], offS[NPT], ch0[NTW];
-    f32x4 acc[NTW][NPT];
+    int pb[NPT], toff[OTP_S8_KS], offS[NPT], ch0[NTW];
+    otp_f32x4 acc[NTW][NPT];
     {
 #pragma unroll
-        for (int s = 0; s < SKS; ++s) {
+        for (int s = 0; s < OTP_S8_KS; ++s) {
             const int q = 4 * s + kl;
             int tap = q >> 1;
             if (tap > 8) tap = 8;                                  // zero weights: any finite data
@@ -182,11 +122,11 @@ __global__ __launch_bounds__(256, 2) void convs2_kernel(const unsigned char* __r
             const int rx = dx == 0 ? 0 : (dx == 1 ? P.Wo + 1 : 1); // record of the tap relative to record x of its virtual row
             toff[s] = (dy * P.W1 + rx) * 16 + (q & 1) * (2 * PL);
         }
-        f32x4 sh[NTW];
+        otp_f32x4 sh[NTW];
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
-            ch0[t] = srow2ch(co_blk, t, 4 * kl, NTW, P.Cout);
-            sh[t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsh, co_blk + 16 * t < P.Cout ? ch0[t] * 4 : SOOB, 0, 0));
+            ch0[t] = otp_row2ch(co_blk, t, 4 * kl, NTW, P.Cout);
+            sh[t] = __builtin_bit_cast(otp_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsh, co_blk + 16 * t < P.Cout ? ch0[t] * 4 : OTP_OOB, 0, 0));
         }
 #pragma unroll
         for (int p = 0; p < NPT; ++p) {
@@ -194,28 +134,28 @@ __global__ __launch_bounds__(256, 2) void convs2_kernel(const unsigned char* __r
             const bool pv = P0 + m < P.total;
             if (!pv) m = P.total - 1 - P0;                         // tail tile: a finite address, the result is dropped
             const int q = p0 + m;
-            const int dn = (int)sdiv((uint32_t)q, P.mHWo), pi = q - dn * P.HWo;
-            const int y = (int)sdiv((uint32_t)pi, P.mWo), x = pi - y * P.Wo;
+            const int dn = (int)otp_magic_div((uint32_t)q, P.mHWo), pi = q - dn * P.HWo;
+            const int y = (int)otp_magic_div((uint32_t)pi, P.mWo), x = pi - y * P.Wo;
             pb[p] = (((n0 + dn) * P.VR + 2 * y - Vf) * P.W1 + x) * 16;    // record x of the virtual row of tap dy = 0
-            offS[p] = pv ? ((n0 + dn) * (P.Cout >> 2) * P.HWo + pi) * 16 : SOOB;   // S8 image: (((img Go + ch / 8) 2 + part) HWo + pi) 16
+            offS[p] = pv ? ((n0 + dn) * (P.Cout >> 2) * P.HWo + pi) * 16 : OTP_OOB;   // S8 image: (((img Go + ch / 8) 2 + part) HWo + pi) 16
 #pragma unroll
             for (int t = 0; t < NTW; ++t) acc[t][p] = sh[t] * P.pre;
         }
     }
 
     auto mfma_phase = [&]() __attribute__((always_inline)) {
-        h16x8 ah[2][NTW], al[2][NTW], bh[3], bl[3];
+        otp_x3x8 ah[2][NTW], al[2][NTW], bh[3], bl[3];
         auto load_a = [&](int buf, int s) __attribute__((always_inline)) {
 #pragma unroll
             for (int t = 0; t < NTW; ++t) {
-                if (s < SKS - 1) {
+                if (s < OTP_S8_KS - 1) {
                     const unsigned char* a = wl + ((s * NTW + t) * 2) * 1024 + lane * 16;
-                    ah[buf][t] = *reinterpret_cast<const h16x8*>(a);
-                    al[buf][t] = *reinterpret_cast<const h16x8*>(a + 1024);
+                    ah[buf][t] = *reinterpret_cast<const otp_x3x8*>(a);
+                    al[buf][t] = *reinterpret_cast<const otp_x3x8*>(a + 1024);
                 } else {
-                    const unsigned char* a = wl + (SKS - 1) * NTW * 2048 + t * 1024 + (lane & 31) * 16;
-                    const h16x8 h = *reinterpret_cast<const h16x8*>(a), l = *reinterpret_cast<const h16x8*>(a + 512);
-                    const h16x8 z = __builtin_bit_cast(h16x8, (u32x4){0u, 0u, 0u, 0u});
+                    const unsigned char* a = wl + (OTP_S8_KS - 1) * NTW * 2048 + t * 1024 + (lane & 31) * 16;
+                    const otp_x3x8 h = *reinterpret_cast<const otp_x3x8*>(a), l = *reinterpret_cast<const otp_x3x8*>(a + 512);
+                    const otp_x3x8 z = __builtin_bit_cast(otp_x3x8, (otp_u32x4){0u, 0u, 0u, 0u});
                     ah[buf][t] = upper ? z : h;
                     al[buf][t] = upper ? z : l;
                 }
@@ -223,8 +163,8 @@ __global__ __launch_bounds__(256, 2) void convs2_kernel(const unsigned char* __r
         };
         auto load_b = [&](int buf, int blk) __attribute__((always_inline)) {
             const unsigned char* b = win + (pb[blk % NPT] + toff[blk / NPT]);
-            bh[buf] = *reinterpret_cast<const h16x8*>(b);
-            bl[buf] = *reinterpret_cast<const h16x8*>(b + PL);
+            bh[buf] = *reinterpret_cast<const otp_x3x8*>(b);
+            bl[buf] = *reinterpret_cast<const otp_x3x8*>(b + PL);
         };
         load_a(0, 0);
         load_b(0, 0);
@@ -233,7 +173,7 @@ __global__ __launch_bounds__(256, 2) void convs2_kernel(const unsigned char* __r
         for (int blk = 0; blk < NBLK; ++blk) {
             const int s = blk / NPT, p = blk % NPT, cur = blk % 3, sa = s & 1;
             const bool nb = blk + 2 < NBLK;
-            const bool na = (NPT >= 2 ? p == NPT - 2 : true) && s + 1 < SKS;
+            const bool na = (NPT >= 2 ? p == NPT - 2 : true) && s + 1 < OTP_S8_KS;
             if (nb) load_b((blk + 2) % 3, blk + 2);
             if (na) load_a(sa ^ 1, s + 1);
 #pragma unroll
@@ -242,10 +182,10 @@ __global__ __launch_bounds__(256, 2) void convs2_kernel(const unsigned char* __r
                 acc[t][p] = OTP_X3_MFMA(ah[sa][t], bl[cur], acc[t][p], 0, 0, 0);
                 acc[t][p] = OTP_X3_MFMA(ah[sa][t], bh[cur], acc[t][p], 0, 0, 0);
             }
-            if (!nb && !na) sblock_sched<NM, 0>();
-            else if (nb && na) sblock_sched<NM, 2 + 2 * NTW>();
-            else if (na) sblock_sched<NM, 2 * NTW>();
-            else sblock_sched<NM, 2>();
+            if (!nb && !na) otp_s8_block_sched<NM, 0>();
+            else if (nb && na) otp_s8_block_sched<NM, 2 + 2 * NTW>();
+            else if (na) otp_s8_block_sched<NM, 2 * NTW>();
+            else otp_s8_block_sched<NM, 2>();
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -286,27 +226,27 @@ __global__ __launch_bounds__(256, 2) void convs2_kernel(const unsigned char* __r
 #pragma unroll
                     for (int r = 0; r < 4; ++r) acc[t][p][r] = otp_relu(acc[t][p][r]);
         }
-        u32x4 rec[(NTW + 1) / 2][NPT][2];
+        otp_u32x4 rec[(NTW + 1) / 2][NPT][2];
 #pragma unroll
         for (int t = 0; t < NTW; t += 2) {
-            const bool paired = stile_paired(co_blk, t, NTW, P.Cout);
+            const bool paired = otp_tile_paired(co_blk, t, NTW, P.Cout);
             const int t1 = t + 1 < NTW ? t + 1 : t;
 #pragma unroll
             for (int p = 0; p < NPT; ++p) {
                 const float f[8] = {acc[t][p][0], acc[t][p][1], acc[t][p][2], acc[t][p][3],
                                     paired ? acc[t1][p][0] : 0.f, paired ? acc[t1][p][1] : 0.f,
                                     paired ? acc[t1][p][2] : 0.f, paired ? acc[t1][p][3] : 0.f};
-                ssplit8(f, rec[t >> 1][p][0], rec[t >> 1][p][1]);
+                otp_x3_split8(f, rec[t >> 1][p][0], rec[t >> 1][p][1]);
             }
         }
 #pragma unroll
         for (int t = 0; t < NTW; t += 2) {
             const bool tav = co_blk + 16 * t < P.Cout;
             const int so = (ch0[t] >> 3) * 2 * P.HWo * 16;
-            if (stile_paired(co_blk, t, NTW, P.Cout)) {
+            if (otp_tile_paired(co_blk, t, NTW, P.Cout)) {
 #pragma unroll
                 for (int p = 0; p < NPT; ++p) {
-                    const int o = offS[p] != SOOB ? offS[p] + so : SOOB;
+                    const int o = offS[p] != OTP_OOB ? offS[p] + so : OTP_OOB;
                     __builtin_amdgcn_raw_buffer_store_b128(rec[t >> 1][p][0], rs8, o, 0, 0);
                     __builtin_amdgcn_raw_buffer_store_b128(rec[t >> 1][p][1], rs8, o, P.HWo * 16, 0);
                 }
@@ -314,9 +254,9 @@ __global__ __launch_bounds__(256, 2) void convs2_kernel(const unsigned char* __r
                 const int half = (ch0[t] >> 2) & 1;
 #pragma unroll
                 for (int p = 0; p < NPT; ++p) {
-                    const int o = (tav && offS[p] != SOOB) ? offS[p] + so + 8 * half : SOOB;
-                    __builtin_amdgcn_raw_buffer_store_b64((u32x2){rec[t >> 1][p][0][0], rec[t >> 1][p][0][1]}, rs8, o, 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b64((u32x2){rec[t >> 1][p][1][0], rec[t >> 1][p][1][1]}, rs8, o, P.HWo * 16, 0);
+                    const int o = (tav && offS[p] != OTP_OOB) ? offS[p] + so + 8 * half : OTP_OOB;
+                    __builtin_amdgcn_raw_buffer_store_b64((otp_u32x2){rec[t >> 1][p][0][0], rec[t >> 1][p][0][1]}, rs8, o, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b64((otp_u32x2){rec[t >> 1][p][1][0], rec[t >> 1][p][1][1]}, rs8, o, P.HWo * 16, 0);
                 }
             }
         }
@@ -342,30 +282,30 @@ __global__ __launch_bounds__(256, 2) void convs2_kernel(const unsigned char* __r
     const int g = tid % G, c0 = tid / G;
     const bool gv = P0 + 4 * g < P.total;                            // (a group of 4 stays inside one image: Ho Wo % 4 == 0)
     const int q = gv ? p0 + 4 * g : p0;
-    const int qn = (int)sdiv((uint32_t)q, P.mHWo), qi = q - qn * P.HWo;
-    const int ob = gv ? (((n0 + qn) * P.out_ctot + P.out_coff + co_blk) * P.HWo + qi) * 4 : SOOB;
-    const int rb = (gv && res) ? (((n0 + qn) * P.res_ctot + P.res_coff + co_blk) * P.HWo + qi) * 4 : SOOB;
+    const int qn = (int)otp_magic_div((uint32_t)q, P.mHWo), qi = q - qn * P.HWo;
+    const int ob = gv ? (((n0 + qn) * P.out_ctot + P.out_coff + co_blk) * P.HWo + qi) * 4 : OTP_OOB;
+    const int rb = (gv && res) ? (((n0 + qn) * P.res_ctot + P.res_coff + co_blk) * P.HWo + qi) * 4 : OTP_OOB;
     const bool relu = P.act == OTP_ACT_RELU;
-    f32x4 rv[NTW * 16 / CPI];
+    otp_f32x4 rv[NTW * 16 / CPI];
 #pragma unroll
     for (int k = 0; k < NTW * 16 / CPI; ++k) {
         const int ch = c0 + CPI * k;
-        rv[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-            rres, (rb != SOOB && co_blk + ch < P.Cout) ? rb + ch * P.HWo * 4 : SOOB, 0, 0));
+        rv[k] = __builtin_bit_cast(otp_f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+            rres, (rb != OTP_OOB && co_blk + ch < P.Cout) ? rb + ch * P.HWo * 4 : OTP_OOB, 0, 0));
     }
     bool bad = false;                                                // range guard (common.h), before the ReLU
 #pragma unroll
     for (int k = 0; k < NTW * 16 / CPI; ++k) {
         const int ch = c0 + CPI * k;
-        f32x4 v = *reinterpret_cast<const f32x4*>(tl + ch * RS + 4 * g) + rv[k];
+        otp_f32x4 v = *reinterpret_cast<const otp_f32x4*>(tl + ch * RS + 4 * g) + rv[k];
 #pragma unroll
         for (int e = 0; e < 4; ++e) bad |= otp_out_of_range(v[e]);
         if (relu) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
         }
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rof,
-                                               (ob != SOOB && co_blk + ch < P.Cout) ? ob + ch * P.HWo * 4 : SOOB, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(otp_u32x4, v), rof,
+                                               (ob != OTP_OOB && co_blk + ch < P.Cout) ? ob + ch * P.HWo * 4 : OTP_OOB, 0, 0);
     }
     otp_range_report(P.rflag, bad, OTP_RANGE_CONVS2);
 }
@@ -411,7 +351,7 @@ bool convs2_plan(const otp_conv_desc& d, S2Plan& P, bool nchw) {
         P.NPT = npt;
         P.nTiles = (P.total + bm - 1) / bm;
         const int NV = window_records(P, bm);
-        size_t lds = (size_t)4 * NV * 16 + swch(P.NTW) * 1024;
+        size_t lds = (size_t)4 * NV * 16 + otp_s8_wch(P.NTW) * 1024;
         if (nchw && lds < (size_t)P.NTW * 16 * (bm + 4) * 4) lds = (size_t)P.NTW * 16 * (bm + 4) * 4;
         if (NV <= 64 * 4 * MAXJ && lds <= 80 * 1024) {
             // small launches: prefer more, smaller workgroups while that still leaves >= 1 tile per CU pair
@@ -430,7 +370,7 @@ bool convs2_plan(const otp_conv_desc& d, S2Plan& P, bool nchw) {
     P.tpx = (P.nTiles + 7) / 8;
     P.pl = P.NV * 16;
     P.NIW = (P.NV + 63) / 64;
-    P.mHWo = smagic(P.HWo); P.mWo = smagic(Wo); P.mW1 = smagic(P.W1); P.mVR = smagic(P.VR);
+    P.mHWo = otp_magic(P.HWo); P.mWo = otp_magic(Wo); P.mW1 = otp_magic(P.W1); P.mVR = otp_magic(P.VR);
     if ((long)(P.HWo + 256) * P.HWo >= (1l << 32) || (long)P.HWo * Wo >= (1l << 32)) return false;
     if ((long)(d.N + 2) * P.VR * P.VR >= (1l << 32) || (long)(64 * 4 * MAXJ) * P.W1 >= (1l << 32)) return false;
     {   // images a tile's window may touch (a 256-pixel tile of a small map spans many): (n - n0) * imgB stays below 2^31
@@ -439,7 +379,7 @@ bool convs2_plan(const otp_conv_desc& d, S2Plan& P, bool nchw) {
     }
     if ((size_t)d.N * d.out_ctot * P.HWo * 4 >= (1ull << 31) || (size_t)d.N * (d.res_ctot > 0 ? d.res_ctot : 1) * P.HWo * 4 >= (1ull << 31))
         return false;
-    if ((size_t)P.nN * P.nChunks * swch(P.NTW) * 1024 >= (1ull << 31)) return false;
+    if ((size_t)P.nN * P.nChunks * otp_s8_wch(P.NTW) * 1024 >= (1ull << 31)) return false;
     if (P.HWo < 16) return false;
     return true;
 }
@@ -448,11 +388,11 @@ template <int NTW, bool NCHW, int NPT>
 int convs2_launch(const void* xs, const void* wpk, const float* shift, const float* res, float* outf, void* outs, const S2Plan& P,
                   hipStream_t st) {
     auto kern = convs2_kernel<NTW, NCHW, NPT>;
-    size_t need = (size_t)4 * P.pl + swch(NTW) * 1024;
+    size_t need = (size_t)4 * P.pl + otp_s8_wch(NTW) * 1024;
     if (NCHW && need < (size_t)NTW * 16 * (64 * NPT + 4) * 4) need = (size_t)NTW * 16 * (64 * NPT + 4) * 4;
     OTP_ALLOW_BIG_LDS(kern, need);
     hipLaunchKernelGGL(kern, dim3(8 * P.tpx * P.nN), dim3(256), need, st, static_cast<const unsigned char*>(xs),
-                       static_cast<const u32x4*>(wpk), shift, res, outf, static_cast<u32x4*>(outs), P);
+                       static_cast<const otp_u32x4*>(wpk), shift, res, outf, static_cast<otp_u32x4*>(outs), P);
     return otp_launch_status();
 }
 

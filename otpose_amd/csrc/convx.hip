@@ -15,18 +15,13 @@
 // [16 ch hi | 16 ch lo | 16 B pad] (80 B: an odd multiple of 16 B, so the 16 lanes of a fragment read hit 16 distinct bank
 // groups), the packed weights arrive in MFMA fragment order (lane-linear, conflict-free).  One k-step = 2 taps x 16 channels;
 // the loads of chunk c+1 are in flight under the MFMAs of chunk c.
-#include "common.h"
+#include "x3.h"
 #include <type_traits>
 #include <cstdlib>
 
 namespace {
 
 typedef __bf16 bf16;
-typedef otp_x3x8 h16x8;              // 8 operand pieces of the split products (common.h: IEEE half since round 4)
-typedef otp_x3x2 h16x2;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // Two shapes.  Stride 1: chunks of CK = 16 channels (k-step = 2 taps x 16 channels, 5 steps, the tenth tap has zero
 // weights), 256 pixels (4 m-tiles per wave).  Stride 2 reads 4x the input per output pixel: chunks of 8 channels (k-step =
@@ -36,7 +31,6 @@ constexpr int xck(int stride, int taps = 9) { return taps == 1 ? 32 : (stride ==
 constexpr int xmtw(int stride) { return stride == 2 ? 2 : 4; }            // m-tiles (16 pixels) per wave
 constexpr int xpix(int ck) { return ck * 4 + 16; }                        // bytes of a window pixel record: hi | lo | 16 B pad
 constexpr int xks(int ck, int taps = 9) { return (taps * (ck / 8) + 3) / 4; }   // k-steps per chunk
-constexpr int XOOB = -16;      // buffer offset past any descriptor: the load returns zeros
 
 #ifdef OTP_CONVX_TIMING
 // development build only (tools/convx_timing.py): per-workgroup phase stamps, never in libotpose_hip.so
@@ -48,9 +42,6 @@ __device__ unsigned long long otp_convx_stamps[8192 * 16];
 #else
 #define XSTAMP(slot)
 #endif
-
-__device__ __forceinline__ uint32_t xdiv(uint32_t i, uint32_t magic) { return magic ? __umulhi(i, magic) : i; }
-uint32_t xmagic(uint32_t d) { return d <= 1 ? 0u : (uint32_t)((1ull << 32) / d) + 1u; }   // exact while i * d < 2^32
 
 struct XPlan {
     int N, Cin, H, W, HW, Cout, Ho, Wo, HoWo, total;
@@ -64,27 +55,10 @@ struct XPlan {
     uint32_t mHoWo, mWo, mW;
 };
 
-// split 8 floats into bf16 hi / lo vectors
-__device__ __forceinline__ void split8(const float (&v)[8], u32x4& hi, u32x4& lo) {
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x2 a = {v[2 * i], v[2 * i + 1]};
-        const h16x2 ah = __builtin_convertvector(a, h16x2);
-        const uint32_t hb = __builtin_bit_cast(uint32_t, ah);
-        const f32x2 af = otp_x3_widen(hb);
-        const h16x2 al = __builtin_convertvector(a - af, h16x2);
-        h[i] = hb;
-        l[i] = __builtin_bit_cast(uint32_t, al);
-    }
-    hi = (u32x4){h[0], h[1], h[2], h[3]};
-    lo = (u32x4){l[0], l[1], l[2], l[3]};
-}
-
 // (Cout, Cin, 3, 3) fp32 (x scale[cout]) -> [cout block][chunk][k-step][n-tile][hi, lo][lane][8] bf16: the B fragments of
 // v_mfma_f32_16x16x32_bf16 (lane = (cout & 15) + 16 * kl; G = CK / 8 channel groups: kl -> tap (4 / G) s + kl / G, channels
 // 8 (kl % G) .. + 7 of the chunk)
-__global__ void convx_pack_kernel(const float* __restrict__ w, const float* __restrict__ scale, u32x4* __restrict__ out, int Cout,
+__global__ void convx_pack_kernel(const float* __restrict__ w, const float* __restrict__ scale, otp_u32x4* __restrict__ out, int Cout,
                                   int Cin, int NTW, int nN, int nChunks, int CK, int TAPS) {
     const int G = CK / 8, XKS = xks(CK, TAPS);
     const int total = nN * nChunks * XKS * NTW * 64;
@@ -102,8 +76,8 @@ __global__ void convx_pack_kernel(const float* __restrict__ w, const float* __re
             const int ci = ci0 + j;
             v[j] = (tap < TAPS && cout < Cout && ci < Cin) ? w[((size_t)cout * Cin + ci) * TAPS + tap] * (scale ? scale[cout] : 1.f) : 0.f;
         }
-        u32x4 hi, lo;
-        split8(v, hi, lo);
+        otp_u32x4 hi, lo;
+        otp_x3_split8(v, hi, lo);
         const size_t o = ((((size_t)(cb * nChunks + chunk) * XKS + s) * NTW + t) * 2) * 64 + lane;
         out[o] = hi;
         out[o + 64] = lo;
@@ -111,7 +85,7 @@ __global__ void convx_pack_kernel(const float* __restrict__ w, const float* __re
 }
 
 template <int CK, int MTW, int NI, int NTW, int TAPS>
-__global__ __launch_bounds__(256, 2) void convx_kernel(const float* __restrict__ in, const u32x4* __restrict__ wpk,
+__global__ __launch_bounds__(256, 2) void convx_kernel(const float* __restrict__ in, const otp_u32x4* __restrict__ wpk,
                                                         const float* __restrict__ shift, const float* res, float* out,
                                                         const XPlan P) {
     constexpr int G = CK / 8, XKS = xks(CK, TAPS), XPIX = xpix(CK), XBM = 64 * MTW, LO = CK * 2;
@@ -156,9 +130,9 @@ __global__ __launch_bounds__(256, 2) void convx_kernel(const float* __restrict__
             const int i = tid + 256 * j, g = i / TQ, q = i - g * TQ;
             const int flat = P0 + 4 * q;
             const bool ok = g < G && flat < P.total;
-            const int n = (int)xdiv((uint32_t)(ok ? flat - n0 * P.HW : 0), P.mHoWo);      // images past the tile's first
+            const int n = (int)otp_magic_div((uint32_t)(ok ? flat - n0 * P.HW : 0), P.mHoWo);      // images past the tile's first
             const int pin = (ok ? flat - n0 * P.HW : 0) - n * P.HW;
-            goff[j] = ok ? ((n * P.in_ctot + 8 * g) * P.HW + pin) * 4 : XOOB;
+            goff[j] = ok ? ((n * P.in_ctot + 8 * g) * P.HW + pin) * 4 : OTP_OOB;
 #pragma unroll
             for (int k = 0; k < 4; ++k) ldst[j][k] = ok ? (flat + k - row0) * XPIX + g * 16 : -1;
         }
@@ -182,8 +156,8 @@ __global__ __launch_bounds__(256, 2) void convx_kernel(const float* __restrict__
                 if (f < 0 && rem >= 0 && rem < c) { f = ((ya * P.W) >> 2) + rem; n = ns; }
                 rem -= (f < 0) ? c : 0;
             }
-            goff[j] = f >= 0 ? ((((n - n0) * P.in_ctot + 8 * g) * P.HW) + 4 * f) * 4 : XOOB;
-            const int y0 = (int)xdiv((uint32_t)(f >= 0 ? 4 * f : 0), P.mW);
+            goff[j] = f >= 0 ? ((((n - n0) * P.in_ctot + 8 * g) * P.HW) + 4 * f) * 4 : OTP_OOB;
+            const int y0 = (int)otp_magic_div((uint32_t)(f >= 0 ? 4 * f : 0), P.mW);
             int y = y0, x = (f >= 0 ? 4 * f : 0) - y0 * P.W;
     #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -197,15 +171,15 @@ __global__ __launch_bounds__(256, 2) void convx_kernel(const float* __restrict__
     }
     const size_t in_base = ((size_t)n0 * P.in_ctot + P.in_coff) * P.HW;
     const size_t in_left = ((size_t)P.N * P.in_ctot) * P.HW - in_base;
-    // (descriptor size capped below XOOB so that the masked offset is always out of range)
+    // (descriptor size capped below OTP_OOB so that the masked offset is always out of range)
     const otp_rsrc rin = make_rsrc32(in + in_base, in_left * 4 > 0x7fffffffull ? 0x7fffffffu : (unsigned)(in_left * 4));
     const otp_rsrc rw = make_rsrc32(wpk, (unsigned)((size_t)P.nN * P.nChunks * WUNITS * 16));
 
     // staging registers: one set (the loads of chunk c + 1 fly under the MFMAs of chunk c); pointwise launches - one item per
     // thread, short MFMA phases, bound by the HBM round trip - keep two sets and load two chunks ahead
     constexpr int NBUF = TAPS == 1 ? 2 : 1;
-    f32x4 xv[NBUF][NI][8];
-    u32x4 wv[NBUF][NWL];
+    otp_f32x4 xv[NBUF][NI][8];
+    otp_u32x4 wv[NBUF][NWL];
     auto load_chunk = [&](int c, auto bufc) __attribute__((always_inline)) {
         constexpr int b = decltype(bufc)::value;
         const int cs = c * CK * P.HW * 4;                          // scalar byte offset of the chunk's first channel
@@ -213,12 +187,12 @@ __global__ __launch_bounds__(256, 2) void convx_kernel(const float* __restrict__
         for (int j = 0; j < NI; ++j)
 #pragma unroll
             for (int e = 0; e < 8; ++e)
-                xv[b][j][e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, goff[j], cs + e * P.HW * 4, 0));
+                xv[b][j][e] = __builtin_bit_cast(otp_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, goff[j], cs + e * P.HW * 4, 0));
         const int wb = ((cb * P.nChunks + c) * WUNITS) * 16;
 #pragma unroll
         for (int j = 0; j < NWL; ++j) {
             const int i = tid + 256 * j;
-            wv[b][j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, i < WUNITS ? wb + i * 16 : XOOB, 0, 0));
+            wv[b][j] = __builtin_bit_cast(otp_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, i < WUNITS ? wb + i * 16 : OTP_OOB, 0, 0));
         }
     };
     auto store_chunk = [&](auto bufc) __attribute__((always_inline)) {
@@ -230,17 +204,17 @@ __global__ __launch_bounds__(256, 2) void convx_kernel(const float* __restrict__
                 float v[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = xv[b][j][e][k];
-                u32x4 hi, lo;
-                split8(v, hi, lo);
+                otp_u32x4 hi, lo;
+                otp_x3_split8(v, hi, lo);
                 if (ldst[j][k] >= 0) {
-                    *reinterpret_cast<u32x4*>(win + ldst[j][k]) = hi;
-                    *reinterpret_cast<u32x4*>(win + ldst[j][k] + LO) = lo;
+                    *reinterpret_cast<otp_u32x4*>(win + ldst[j][k]) = hi;
+                    *reinterpret_cast<otp_u32x4*>(win + ldst[j][k] + LO) = lo;
                 }
             }
 #pragma unroll
         for (int j = 0; j < NWL; ++j) {
             const int i = tid + 256 * j;
-            if (i < WUNITS) reinterpret_cast<u32x4*>(wl)[i] = wv[b][j];
+            if (i < WUNITS) reinterpret_cast<otp_u32x4*>(wl)[i] = wv[b][j];
         }
     };
     using B0 = std::integral_constant<int, 0>;
@@ -255,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void convx_kernel(const float* __restrict__
     // (a pointwise window has no such records: every record a fragment reads is written, the rows of a ragged last tile read
     // a clamped valid record)
     if constexpr (TAPS != 1)
-        for (int i = tid; i < P.winBytes / 16; i += 256) reinterpret_cast<u32x4*>(win)[i] = (u32x4){0u, 0u, 0u, 0u};
+        for (int i = tid; i < P.winBytes / 16; i += 256) reinterpret_cast<otp_u32x4*>(win)[i] = (otp_u32x4){0u, 0u, 0u, 0u};
 
     XSTAMP(13);
     // ---- fragment addresses ---------------------------------------------------------------------------------------------------
@@ -265,8 +239,8 @@ __global__ __launch_bounds__(256, 2) void convx_kernel(const float* __restrict__
         int m = (wave * MTW + mt) * 16 + i16;
         if (P0 + m >= P.total) m = P.total - 1 - P0;               // tail tile: a finite address, the result is dropped
         const int p = p0 + m;
-        const int dn = (int)xdiv((uint32_t)p, P.mHoWo), pi = p - dn * P.HoWo;
-        const int yo = (int)xdiv((uint32_t)pi, P.mWo), xo = pi - yo * P.Wo;
+        const int dn = (int)otp_magic_div((uint32_t)p, P.mHoWo), pi = p - dn * P.HoWo;
+        const int yo = (int)otp_magic_div((uint32_t)pi, P.mWo), xo = pi - yo * P.Wo;
         const int r = (n0 + dn) * P.VR + yo * P.stride - Vfirst;
         mbase[mt] = (r * P.WPp + xo) * XPIX;                        // (columns are de-interleaved by x mod stride)
     }
@@ -281,28 +255,28 @@ __global__ __launch_bounds__(256, 2) void convx_kernel(const float* __restrict__
         toff[s] = ((dy * P.dil) * P.WPp + (P.stride == 2 ? (xs & 1) * P.CS + (xs >> 1) : xs)) * XPIX + (q % G) * 16;
     }
 
-    f32x4 acc[MTW][NTW];
+    otp_f32x4 acc[MTW][NTW];
 #pragma unroll
     for (int mt = 0; mt < MTW; ++mt)
 #pragma unroll
-        for (int t = 0; t < NTW; ++t) acc[mt][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < NTW; ++t) acc[mt][t] = (otp_f32x4){0.f, 0.f, 0.f, 0.f};
 
     // Fragment pipeline: the LDS reads of the next n-tile (and, at the last n-tile of a k-step, of the next step's pixel
     // fragments) are issued before the 12 MFMAs of the current one, so no MFMA waits on an LDS round trip.
     auto mfma_phase = [&]() __attribute__((always_inline)) {
-        h16x8 ah[2][MTW], al[2][MTW], bh[2], bl[2];
+        otp_x3x8 ah[2][MTW], al[2][MTW], bh[2], bl[2];
         auto load_a = [&](int buf, int s) __attribute__((always_inline)) {
 #pragma unroll
             for (int mt = 0; mt < MTW; ++mt) {
                 const unsigned char* a = win + mbase[mt] + toff[s];
-                ah[buf][mt] = *reinterpret_cast<const h16x8*>(a);
-                al[buf][mt] = *reinterpret_cast<const h16x8*>(a + LO);
+                ah[buf][mt] = *reinterpret_cast<const otp_x3x8*>(a);
+                al[buf][mt] = *reinterpret_cast<const otp_x3x8*>(a + LO);
             }
         };
         auto load_b = [&](int buf, int s, int t) __attribute__((always_inline)) {
             const unsigned char* b = wl + ((s * NTW + t) * 2) * 1024 + lane * 16;
-            bh[buf] = *reinterpret_cast<const h16x8*>(b);
-            bl[buf] = *reinterpret_cast<const h16x8*>(b + 1024);
+            bh[buf] = *reinterpret_cast<const otp_x3x8*>(b);
+            bl[buf] = *reinterpret_cast<const otp_x3x8*>(b + 1024);
         };
         load_a(0, 0);
         load_b(0, 0, 0);
@@ -372,12 +346,12 @@ __global__ __launch_bounds__(256, 2) void convx_kernel(const float* __restrict__
         const int m = (wave * MTW + mt) * 16 + 4 * kl;
         ev[mt] = P0 + m < P.total;
         const int p = p0 + (ev[mt] ? m : 0);
-        const int dn = (int)xdiv((uint32_t)p, P.mHoWo), pi = p - dn * P.HoWo;
+        const int dn = (int)otp_magic_div((uint32_t)p, P.mHoWo), pi = p - dn * P.HoWo;
         eo[mt] = ((n0 + dn) * P.out_ctot + P.out_coff) * P.HoWo + pi;
         ro[mt] = ((n0 + dn) * P.res_ctot + P.res_coff) * P.HoWo + pi;
     }
     // residual: unconditional loads (a masked element re-reads a valid address of the output's own first pixel row)
-    f32x4 rv[MTW][NTW];
+    otp_f32x4 rv[MTW][NTW];
     const float* rp = res ? res : out;
 #pragma unroll
     for (int mt = 0; mt < MTW; ++mt)
@@ -386,8 +360,8 @@ __global__ __launch_bounds__(256, 2) void convx_kernel(const float* __restrict__
             const int co = co0 + 16 * t;
             const bool ok = res && ev[mt] && co < P.Cout;
             const size_t o = ok ? (size_t)ro[mt] + (size_t)co * P.HoWo : 0;
-            rv[mt][t] = *reinterpret_cast<const f32x4*>(rp + o);
-            if (!ok) rv[mt][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            rv[mt][t] = *reinterpret_cast<const otp_f32x4*>(rp + o);
+            if (!ok) rv[mt][t] = (otp_f32x4){0.f, 0.f, 0.f, 0.f};
         }
     float shv[NTW];
 #pragma unroll
@@ -409,13 +383,13 @@ __global__ __launch_bounds__(256, 2) void convx_kernel(const float* __restrict__
         const float sh = shv[t];
 #pragma unroll
         for (int mt = 0; mt < MTW; ++mt) {
-            f32x4 y = acc[mt][t] * P.post + sh + rv[mt][t];      // post = 2^-k: the packed weights carry 2^k (out_scale)
+            otp_f32x4 y = acc[mt][t] * P.post + sh + rv[mt][t];      // post = 2^-k: the packed weights carry 2^k (out_scale)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 bad |= otp_out_of_range(y[r]);
                 y[r] = fmaxf(y[r], lo);
             }
-            if (ev[mt] && co < P.Cout) *reinterpret_cast<f32x4*>(out + (size_t)eo[mt] + (size_t)co * P.HoWo) = y;
+            if (ev[mt] && co < P.Cout) *reinterpret_cast<otp_f32x4*>(out + (size_t)eo[mt] + (size_t)co * P.HoWo) = y;
         }
     }
     otp_range_report(P.rflag, bad, OTP_RANGE_CONVX);
@@ -480,7 +454,7 @@ bool convx_plan(const otp_conv_desc& d, XPlan& P) {
     P.winBytes = (rows * P.WPp + KE + 4) * XPIX;                   // + slack: the clamped tenth tap / tail pixels stay inside
     P.winBytes = (P.winBytes + 15) & ~15;
     P.wBytes = XKS * P.NTW * 2 * 1024;
-    P.mHoWo = xmagic(P.HoWo); P.mWo = xmagic(Wo); P.mW = xmagic(d.W);
+    P.mHoWo = otp_magic(P.HoWo); P.mWo = otp_magic(Wo); P.mW = otp_magic(d.W);
     // exactness of the magic divisions (numerators < 2^32 / divisor) and 31-bit byte offsets
     if ((long)(P.HoWo + XBM) * P.HoWo >= (1l << 32) || (long)P.HW * d.W >= (1l << 32)) return false;
     if ((long)(S + 1) * d.in_ctot * P.HW * 4 >= (1l << 31)) return false;
@@ -492,7 +466,7 @@ bool convx_plan(const otp_conv_desc& d, XPlan& P) {
 }
 
 template <int CK, int MTW, int NI, int NTW, int TAPS>
-int convx_launch(const float* in, const u32x4* wpk, const float* shift, const float* res, float* out, const XPlan& P, hipStream_t st) {
+int convx_launch(const float* in, const otp_u32x4* wpk, const float* shift, const float* res, float* out, const XPlan& P, hipStream_t st) {
     auto kern = convx_kernel<CK, MTW, NI, NTW, TAPS>;
     const size_t lds = (size_t)P.winBytes + P.wBytes;
     OTP_ALLOW_BIG_LDS(kern, lds);
@@ -502,7 +476,7 @@ int convx_launch(const float* in, const u32x4* wpk, const float* shift, const fl
 }
 
 template <int NTW>
-int convx_dispatch(const float* in, const u32x4* wpk, const float* shift, const float* res, float* out, const XPlan& P, hipStream_t st) {
+int convx_dispatch(const float* in, const otp_u32x4* wpk, const float* shift, const float* res, float* out, const XPlan& P, hipStream_t st) {
     if (P.taps == 1)
         return P.NI <= 1 ? convx_launch<xck(1, 1), xmtw(1), 1, NTW, 1>(in, wpk, shift, res, out, P, st)
                          : convx_launch<xck(1, 1), xmtw(1), 2, NTW, 1>(in, wpk, shift, res, out, P, st);
@@ -552,7 +526,7 @@ extern "C" int otp_conv2d_x3_pack_weight(const void* weight, const void* scale, 
     const int total = nN * nChunks * xks(CK, TAPS) * NTW * 64;
     hipLaunchKernelGGL(convx_pack_kernel, dim3(otp_ceil_div(total, 256) > 2048 ? 2048 : otp_ceil_div(total, 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), static_cast<const float*>(weight), static_cast<const float*>(scale),
-                       static_cast<u32x4*>(wpacked), Cout, Cin, NTW, nN, nChunks, CK, TAPS);
+                       static_cast<otp_u32x4*>(wpacked), Cout, Cin, NTW, nN, nChunks, CK, TAPS);
     return otp_launch_status();
 }
 
@@ -571,7 +545,7 @@ extern "C" int otp_conv2d_x3(const void* in, const void* wpacked, const void* sh
     P.rflag = otp_range_word();
     auto st = static_cast<hipStream_t>(stream);
     auto fi = static_cast<const float*>(in);
-    auto fw = static_cast<const u32x4*>(wpacked);
+    auto fw = static_cast<const otp_u32x4*>(wpacked);
     auto fs = static_cast<const float*>(shift);
     auto fr = static_cast<const float*>(res);
     auto fo = static_cast<float*>(out);

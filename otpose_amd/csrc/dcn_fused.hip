@@ -19,15 +19,9 @@
 //     interval (-1, H) x (-1, W) exactly like deform_conv_cuda_kernel.cu:403-432, 549-556) and accumulates
 //     mask * sample * W_dcn[:, g, tap] into J output registers.
 // The J outputs accumulate over groups AND dilations in registers; one store per pixel at the end.
-#include "common.h"
+#include "x3.h"
 
 namespace {
-
-typedef otp_x3x8 h16x8;              // 8 operand pieces of the split products (common.h: IEEE half since round 4)
-typedef otp_x3x2 h16x2;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int FCIN = 32;                      // channels of `trans`
 constexpr int FBLK = 40960;                   // bytes of one (dilation, group) weight block: 9 taps x 2 n-tiles x (hi, lo) x 1 KB, padded
@@ -48,22 +42,8 @@ struct FusedPlan {
     unsigned* rflag;                                                // range-guard word (common.h)
 };
 
-__device__ __forceinline__ void f_split8(const float (&v)[8], u32x4& hi, u32x4& lo) {
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x2 a = {v[2 * i], v[2 * i + 1]};
-        const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, h16x2));
-        const f32x2 af = otp_x3_widen(hb);
-        h[i] = hb;
-        l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a - af, h16x2));
-    }
-    hi = (u32x4){h[0], h[1], h[2], h[3]};
-    lo = (u32x4){l[0], l[1], l[2], l[3]};
-}
-
 // trans (B, 32, H, W) fp32 -> (B, H, W, [32 bf16 hi | 32 bf16 lo]): thread = (pixel, 8-channel group)
-__global__ __launch_bounds__(256) void dcnf_split_kernel(const float* __restrict__ trans, u32x4* __restrict__ ws, int B, int HW) {
+__global__ __launch_bounds__(256) void dcnf_split_kernel(const float* __restrict__ trans, otp_u32x4* __restrict__ ws, int B, int HW) {
     const size_t total = (size_t)B * HW * 4;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int q = (int)(i & 3);
@@ -72,8 +52,8 @@ __global__ __launch_bounds__(256) void dcnf_split_kernel(const float* __restrict
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = trans[(n * FCIN + 8 * q + j) * HW + p];
-        u32x4 hi, lo;
-        f_split8(v, hi, lo);
+        otp_u32x4 hi, lo;
+        otp_x3_split8(v, hi, lo);
         ws[px * 8 + q] = hi;
         ws[px * 8 + 4 + q] = lo;
     }
@@ -131,7 +111,7 @@ __global__ void dcnf_pack_kernel(const float* const* __restrict__ w_off, const f
     const size_t nW = (size_t)ND * J * units, nT = (size_t)ND * J * 9 * 5, total = nW + nT + 5;
     const float* post = reinterpret_cast<const float*>(packed + (total << 4));          // written by dcnf_exp_kernel before this launch
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        u32x4 o = {0u, 0u, 0u, 0u};
+        otp_u32x4 o = {0u, 0u, 0u, 0u};
         if (idx < nW) {
             const int blk = (int)(idx / units), u = (int)(idx - (size_t)blk * units);
             const int di = blk / J, g = blk - di * J;
@@ -146,8 +126,8 @@ __global__ void dcnf_pack_kernel(const float* const* __restrict__ w_off, const f
                     v[j] = pre * (ch < 18 ? w_off[di][((size_t)(18 * g + ch) * FCIN + ci) * 9 + tap]
                                           : (ch < 27 ? w_mask[di][((size_t)(9 * g + ch - 18) * FCIN + ci) * 9 + tap] : 0.f));
                 }
-                u32x4 hi, lo;
-                f_split8(v, hi, lo);
+                otp_u32x4 hi, lo;
+                otp_x3_split8(v, hi, lo);
                 o = part ? lo : hi;
             }
         } else if (idx < nW + nT) {
@@ -159,7 +139,7 @@ __global__ void dcnf_pack_kernel(const float* const* __restrict__ w_off, const f
                 const int oc = 4 * q + i;
                 v[i] = oc < J ? w_dcn[di][((size_t)oc * J + g) * 9 + k] : 0.f;
             }
-            o = (u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]), __builtin_bit_cast(uint32_t, v[2]),
+            o = (otp_u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]), __builtin_bit_cast(uint32_t, v[2]),
                         __builtin_bit_cast(uint32_t, v[3])};
         } else {
             const int q = (int)(idx - nW - nT);
@@ -171,13 +151,15 @@ __global__ void dcnf_pack_kernel(const float* const* __restrict__ w_off, const f
                 for (int di = 0; di < ND; ++di) s += (oc < J && bias[di]) ? bias[di][oc] : 0.f;
                 v[i] = s;
             }
-            o = (u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]), __builtin_bit_cast(uint32_t, v[2]),
+            o = (otp_u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]), __builtin_bit_cast(uint32_t, v[2]),
                         __builtin_bit_cast(uint32_t, v[3])};
         }
-        reinterpret_cast<u32x4*>(packed)[idx] = o;
+        reinterpret_cast<otp_u32x4*>(packed)[idx] = o;
     }
 }
 
+// one weight block global -> LDS with the LDS-DMA: common.h's otp_lds_stage<64 NW, FBLK> with its bound test written as a
+// predicate on the load instead of a loop exit - folding this copy into the shared one changes the kernel's register allocation
 template <int NW>
 __device__ __forceinline__ void f_stage(const unsigned char* __restrict__ src, unsigned char* lds) {
     constexpr int UNITS = FBLK / 16, NST = (UNITS + NW * 64 - 1) / (NW * 64);   // 64-unit runs, one wave each
@@ -234,16 +216,16 @@ __global__ __launch_bounds__(64 * NW) void dcn_fused_kernel(const unsigned char*
         const float post0 = postv[2 * di], post1 = i16 < 2 ? post0 : postv[2 * di + 1];
         __syncthreads();                                            // the previous dilation's table / weight buffers are free
         for (int i = tid; i < J * 9 * 5; i += 64 * NW)
-            reinterpret_cast<u32x4*>(wd)[i] = reinterpret_cast<const u32x4*>(packed + table_off)[(size_t)di * J * 45 + i];
+            reinterpret_cast<otp_u32x4*>(wd)[i] = reinterpret_cast<const otp_u32x4*>(packed + table_off)[(size_t)di * J * 45 + i];
         // pixel fragments of all nine taps (rows outside the image / columns outside the row: offset past the descriptor = 0)
-        u32x4 ah[9], al[9];
+        otp_u32x4 ah[9], al[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
             const int yy = y + (k / 3 - 1) * d, xx = xx0 + (k % 3 - 1) * d;
             const bool ok = yy >= 0 && yy < P.H && xx >= 0 && xx < P.W;
             const int off = ok ? (yy * P.W + xx) * 128 + kq * 16 : -128;
-            ah[k] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rws, off, 0, 0));
-            al[k] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rws, off, 64, 0));
+            ah[k] = __builtin_bit_cast(otp_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rws, off, 0, 0));
+            al[k] = __builtin_bit_cast(otp_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rws, off, 64, 0));
         }
         f_stage<NW>(packed + (size_t)(di * J) * FBLK, wbuf);
         __syncthreads();                                            // block 0 landed, table visible
@@ -252,14 +234,14 @@ __global__ __launch_bounds__(64 * NW) void dcn_fused_kernel(const unsigned char*
         for (int g = 0; g < J; ++g) {
             if (g + 1 < J) f_stage<NW>(packed + (size_t)(di * J + g + 1) * FBLK, wbuf + ((g + 1) & 1) * FBLK);
             const unsigned char* wb = wbuf + (g & 1) * FBLK + lane * 16;
-            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+            otp_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int k = 0; k < 9; ++k) {
-                const h16x8 b0h = *reinterpret_cast<const h16x8*>(wb + (k * 4 + 0) * 1024);
-                const h16x8 b0l = *reinterpret_cast<const h16x8*>(wb + (k * 4 + 1) * 1024);
-                const h16x8 b1h = *reinterpret_cast<const h16x8*>(wb + (k * 4 + 2) * 1024);
-                const h16x8 b1l = *reinterpret_cast<const h16x8*>(wb + (k * 4 + 3) * 1024);
-                const h16x8 a_h = __builtin_bit_cast(h16x8, ah[k]), a_l = __builtin_bit_cast(h16x8, al[k]);
+                const otp_x3x8 b0h = *reinterpret_cast<const otp_x3x8*>(wb + (k * 4 + 0) * 1024);
+                const otp_x3x8 b0l = *reinterpret_cast<const otp_x3x8*>(wb + (k * 4 + 1) * 1024);
+                const otp_x3x8 b1h = *reinterpret_cast<const otp_x3x8*>(wb + (k * 4 + 2) * 1024);
+                const otp_x3x8 b1l = *reinterpret_cast<const otp_x3x8*>(wb + (k * 4 + 3) * 1024);
+                const otp_x3x8 a_h = __builtin_bit_cast(otp_x3x8, ah[k]), a_l = __builtin_bit_cast(otp_x3x8, al[k]);
                 acc0 = OTP_X3_MFMA(a_l, b0h, acc0, 0, 0, 0);
                 acc1 = OTP_X3_MFMA(a_l, b1h, acc1, 0, 0, 0);
                 acc0 = OTP_X3_MFMA(a_h, b0l, acc0, 0, 0, 0);
@@ -303,7 +285,7 @@ __global__ __launch_bounds__(64 * NW) void dcn_fused_kernel(const unsigned char*
                 const float* wrow = wd + (g * 9 + k) * 20;
 #pragma unroll
                 for (int q = 0; q < JP / 4; ++q) {
-                    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wrow + 4 * q);
+                    const otp_f32x4 w4 = *reinterpret_cast<const otp_f32x4*>(wrow + 4 * q);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) part[4 * q + i] = fmaf(w4[i], val, part[4 * q + i]);
                 }
@@ -393,7 +375,7 @@ extern "C" int otp_dcn_fused_forward(const void* trans, const void* x, const voi
     }
     const size_t nsplit = (size_t)B * P.HW * 4;
     hipLaunchKernelGGL(dcnf_split_kernel, dim3((unsigned)((nsplit + 255) / 256 > 4096 ? 4096 : (nsplit + 255) / 256)), dim3(256), 0,
-                       st, static_cast<const float*>(trans), static_cast<u32x4*>(workspace), B, P.HW);
+                       st, static_cast<const float*>(trans), static_cast<otp_u32x4*>(workspace), B, P.HW);
     float* xp = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + dcnf_split_bytes(B, H, W));
     {
         const size_t npad = (size_t)B * J * (H + 2) * (W + 2);

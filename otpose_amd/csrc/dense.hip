@@ -10,9 +10,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 // floats per 16-row output block: A fragments [kgroup][lane][4 k-steps], scale[16], shift[16]; whole 256 x 16-byte passes
 constexpr int dense_block_floats(int C) { return (((C / 4 + 3) / 4) * 256 + 32 + 1023) / 1024 * 1024; }
 
@@ -56,29 +53,29 @@ __global__ __launch_bounds__(256, 3) void dense_cc_kernel(DenseArgs A, int T, in
     const float* __restrict__ x = A.x[blockIdx.y];
     const float* __restrict__ res = A.res[blockIdx.y];
     float* __restrict__ out = A.out[blockIdx.y];
-    const f32x4* pk = reinterpret_cast<const f32x4*>(A.packed[blockIdx.y]);
+    const otp_f32x4* pk = reinterpret_cast<const otp_f32x4*>(A.packed[blockIdx.y]);
 
-    f32x4* l4 = reinterpret_cast<f32x4*>(lds);
+    otp_f32x4* l4 = reinterpret_cast<otp_f32x4*>(lds);
 #pragma unroll
     for (int i = 0; i < NST; ++i) l4[tid + i * 256] = pk[tid + i * 256];
-    f32x2 X[KS];
+    otp_f32x2 X[KS];
 #pragma unroll
     for (int s = 0; s < KS; ++s)       // columns past T read the last pair instead (their results are never stored)
-        X[s] = *reinterpret_cast<const f32x2*>(x + base + (size_t)(4 * s + kq) * T + (valid ? tok : T - 2));
+        X[s] = *reinterpret_cast<const otp_f32x2*>(x + base + (size_t)(4 * s + kq) * T + (valid ? tok : T - 2));
     __syncthreads();
 
     for (int mt = 0; mt < MT; ++mt) {
-        f32x4 stage[NST];
+        otp_f32x4 stage[NST];
         if (mt + 1 < MT) {
-            const f32x4* src = pk + (size_t)(mt + 1) * BLK4;
+            const otp_f32x4* src = pk + (size_t)(mt + 1) * BLK4;
 #pragma unroll
             for (int i = 0; i < NST; ++i) stage[i] = src[tid + i * 256];
         }
         const float* P = lds + (mt & 1) * BLK;
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+        otp_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int sg = 0; sg < KG; ++sg) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(P + (sg * 64 + lane) * 4);
+            const otp_f32x4 a = *reinterpret_cast<const otp_f32x4*>(P + (sg * 64 + lane) * 4);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int s = 4 * sg + q;
@@ -88,22 +85,22 @@ __global__ __launch_bounds__(256, 3) void dense_cc_kernel(DenseArgs A, int T, in
                 }
             }
         }
-        const f32x4 sc = *reinterpret_cast<const f32x4*>(P + KG * 256 + 4 * kq);
-        const f32x4 sh = *reinterpret_cast<const f32x4*>(P + KG * 256 + 16 + 4 * kq);
+        const otp_f32x4 sc = *reinterpret_cast<const otp_f32x4*>(P + KG * 256 + 4 * kq);
+        const otp_f32x4 sh = *reinterpret_cast<const otp_f32x4*>(P + KG * 256 + 16 + 4 * kq);
         if (valid) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int c = 16 * mt + 4 * kq + i;
                 if (c < C) {
                     const size_t o = base + (size_t)c * T + tok;
-                    f32x2 v = {acc0[i] * sc[i] + sh[i], acc1[i] * sc[i] + sh[i]};
-                    if (res) v += *reinterpret_cast<const f32x2*>(res + o);
-                    *reinterpret_cast<f32x2*>(out + o) = v;
+                    otp_f32x2 v = {acc0[i] * sc[i] + sh[i], acc1[i] * sc[i] + sh[i]};
+                    if (res) v += *reinterpret_cast<const otp_f32x2*>(res + o);
+                    *reinterpret_cast<otp_f32x2*>(out + o) = v;
                 }
             }
         }
         if (mt + 1 < MT) {
-            f32x4* dst = reinterpret_cast<f32x4*>(lds + ((mt + 1) & 1) * BLK);
+            otp_f32x4* dst = reinterpret_cast<otp_f32x4*>(lds + ((mt + 1) & 1) * BLK);
 #pragma unroll
             for (int i = 0; i < NST; ++i) dst[tid + i * 256] = stage[i];
         }
@@ -137,12 +134,6 @@ struct QkvArgs {
     float* out[3];
 };
 
-__device__ __forceinline__ float kslot_sum(float v) {      // sum over the four k-slot lane groups (lanes n, n+16, n+32, n+48)
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
 template <int C>
 __global__ __launch_bounds__(256, 2) void qkv_front_kernel(const float* __restrict__ x, const float* __restrict__ table,
                                                            QkvArgs A, int T, int tiles_per_b, float eps) {
@@ -162,33 +153,33 @@ __global__ __launch_bounds__(256, 2) void qkv_front_kernel(const float* __restri
     const int voff = (kq * T + tokc) * 4;
     constexpr float inv_c = 1.f / (float)C;
     for (int i = tid; i < TAB / 4; i += 256)
-        reinterpret_cast<f32x4*>(tab)[i] = reinterpret_cast<const f32x4*>(table)[i];
-    f32x4* l4 = reinterpret_cast<f32x4*>(lds);
+        reinterpret_cast<otp_f32x4*>(tab)[i] = reinterpret_cast<const otp_f32x4*>(table)[i];
+    otp_f32x4* l4 = reinterpret_cast<otp_f32x4*>(lds);
 
     for (int p = 0; p < 3; ++p) {
-        const f32x4* pk = reinterpret_cast<const f32x4*>(A.packed[p]);
+        const otp_f32x4* pk = reinterpret_cast<const otp_f32x4*>(A.packed[p]);
         float* __restrict__ out = A.out[p];
         // (every wave is past the last block of the previous problem: the barrier that ends its loop)
 #pragma unroll
         for (int i = 0; i < NST; ++i) l4[tid + i * 256] = pk[tid + i * 256];
         if (p == 0) __syncthreads();                 // parameter table visible
         const float* tp = tab + p * C * 8 + kq * 8;
-        f32x2 X[KS];
+        otp_f32x2 X[KS];
         float s0 = 0.f, s1 = 0.f;
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             const int so = 4 * s * T * 4;
-            const f32x2 m = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rx, voff, so, 0));
+            const otp_f32x2 m = __builtin_bit_cast(otp_f32x2, __builtin_amdgcn_raw_buffer_load_b64(rx, voff, so, 0));
             const float la = bload(rx, voff - 4, so), ld = bload(rx, voff + 8, so);
             const float a = l_ok ? la : 0.f, d = r_ok ? ld : 0.f;
-            const f32x4 w = *reinterpret_cast<const f32x4*>(tp + s * 32);
+            const otp_f32x4 w = *reinterpret_cast<const otp_f32x4*>(tp + s * 32);
             if ((s & 7) == 7) __builtin_amdgcn_sched_barrier(0);      // bound the loads in flight (registers)
             X[s].x = w[0] * a + w[1] * m.x + w[2] * m.y;
             X[s].y = w[0] * m.x + w[1] * m.y + w[2] * d;
             s0 += X[s].x;
             s1 += X[s].y;
         }
-        const float m0 = kslot_sum(s0) * inv_c, m1 = kslot_sum(s1) * inv_c;
+        const float m0 = otp_kslot_sum(s0) * inv_c, m1 = otp_kslot_sum(s1) * inv_c;
         float v0 = 0.f, v1 = 0.f;
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
@@ -197,7 +188,7 @@ __global__ __launch_bounds__(256, 2) void qkv_front_kernel(const float* __restri
             v0 += X[s].x * X[s].x;
             v1 += X[s].y * X[s].y;
         }
-        const float r0 = 1.f / sqrtf(kslot_sum(v0) * inv_c + eps), r1 = 1.f / sqrtf(kslot_sum(v1) * inv_c + eps);
+        const float r0 = 1.f / sqrtf(otp_kslot_sum(v0) * inv_c + eps), r1 = 1.f / sqrtf(otp_kslot_sum(v1) * inv_c + eps);
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             const float g = tp[s * 32 + 3], be = tp[s * 32 + 4];
@@ -207,17 +198,17 @@ __global__ __launch_bounds__(256, 2) void qkv_front_kernel(const float* __restri
         __syncthreads();                             // weight block 0 of this problem visible
 
         for (int mt = 0; mt < MT; ++mt) {
-            f32x4 stage[NST];
+            otp_f32x4 stage[NST];
             if (mt + 1 < MT) {
-                const f32x4* src = pk + (size_t)(mt + 1) * BLK4;
+                const otp_f32x4* src = pk + (size_t)(mt + 1) * BLK4;
 #pragma unroll
                 for (int i = 0; i < NST; ++i) stage[i] = src[tid + i * 256];
             }
             const float* P = lds + (mt & 1) * BLK;
-            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+            otp_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int sg = 0; sg < KG; ++sg) {
-                const f32x4 a = *reinterpret_cast<const f32x4*>(P + (sg * 64 + lane) * 4);
+                const otp_f32x4 a = *reinterpret_cast<const otp_f32x4*>(P + (sg * 64 + lane) * 4);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int s = 4 * sg + q;
@@ -227,20 +218,20 @@ __global__ __launch_bounds__(256, 2) void qkv_front_kernel(const float* __restri
                     }
                 }
             }
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(P + KG * 256 + 4 * kq);
-            const f32x4 sh = *reinterpret_cast<const f32x4*>(P + KG * 256 + 16 + 4 * kq);
+            const otp_f32x4 sc = *reinterpret_cast<const otp_f32x4*>(P + KG * 256 + 4 * kq);
+            const otp_f32x4 sh = *reinterpret_cast<const otp_f32x4*>(P + KG * 256 + 16 + 4 * kq);
             if (valid) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int c = 16 * mt + 4 * kq + i;
                     if (c < C) {
-                        const f32x2 v = {acc0[i] * sc[i] + sh[i], acc1[i] * sc[i] + sh[i]};
-                        *reinterpret_cast<f32x2*>(out + base + (size_t)c * T + tok) = v;
+                        const otp_f32x2 v = {acc0[i] * sc[i] + sh[i], acc1[i] * sc[i] + sh[i]};
+                        *reinterpret_cast<otp_f32x2*>(out + base + (size_t)c * T + tok) = v;
                     }
                 }
             }
             if (mt + 1 < MT) {
-                f32x4* dst = reinterpret_cast<f32x4*>(lds + ((mt + 1) & 1) * BLK);
+                otp_f32x4* dst = reinterpret_cast<otp_f32x4*>(lds + ((mt + 1) & 1) * BLK);
 #pragma unroll
                 for (int i = 0; i < NST; ++i) dst[tid + i * 256] = stage[i];
             }

@@ -13,38 +13,12 @@
 // (densex_grad.hip: -DOTP_X3_BF16, entry points suffixed _bf16p): bfloat16 pieces for operands whose magnitude is not known -
 // the GRADIENTS the training backward sends through the same projection (dx = W^T dy, otpose_amd/train_ops.py): a half piece
 // flushes 1e-8 to zero and holds 1e-5 to 8 bits, a bfloat16 pair keeps 16-17 bits at any magnitude.
-#include "common.h"
+#include "x3.h"
 #ifndef OTP_ENTRY
 #define OTP_ENTRY(name) name
 #endif
 
 namespace {
-
-typedef otp_x3x8 h16x8;              // 8 operand pieces of the split products (common.h: IEEE half since round 4)
-typedef otp_x3x2 h16x2;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void dx_split8(const float (&v)[8], h16x8& hi, h16x8& lo) {
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x2 a = {v[2 * i], v[2 * i + 1]};
-        const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, h16x2));
-        const f32x2 af = otp_x3_widen(hb);
-        h[i] = hb;
-        l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a - af, h16x2));
-    }
-    hi = __builtin_bit_cast(h16x8, (u32x4){h[0], h[1], h[2], h[3]});
-    lo = __builtin_bit_cast(h16x8, (u32x4){l[0], l[1], l[2], l[3]});
-}
-
-__device__ __forceinline__ float dx_kslot_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
 
 constexpr int dx_ks(int C) { return (C + 31) / 32; }
 // bytes of one 16-row output block: A fragments [ks][hi, lo][1 KB], scale[16], shift[16]; whole 4 KB (256 x 16 B) passes
@@ -56,7 +30,7 @@ __global__ void densex_pack_kernel(const float* __restrict__ w, const float* __r
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= MT * units) return;
     const int mt = idx / units, u = idx - mt * units;
-    u32x4 o = {0u, 0u, 0u, 0u};
+    otp_u32x4 o = {0u, 0u, 0u, 0u};
     if (u < KS * 2 * 64) {
         const int frag = u >> 6, lane = u & 63, row = 16 * mt + (lane & 15), kq = lane >> 4, ks = frag >> 1;
         float v[8];
@@ -65,9 +39,9 @@ __global__ void densex_pack_kernel(const float* __restrict__ w, const float* __r
             const int c = 32 * ks + 8 * kq + j;
             v[j] = (row < C && c < C) ? w[(size_t)row * C + c] : 0.f;
         }
-        h16x8 hi, lo;
-        dx_split8(v, hi, lo);
-        o = __builtin_bit_cast(u32x4, (frag & 1) ? lo : hi);
+        otp_x3x8 hi, lo;
+        otp_x3_split8(v, hi, lo);
+        o = __builtin_bit_cast(otp_u32x4, (frag & 1) ? lo : hi);
     } else if (u < KS * 2 * 64 + 8) {
         const int k = (u - KS * 2 * 64) * 4;                       // floats 0..15: scale, 16..31: shift
         float v[4];
@@ -76,23 +50,10 @@ __global__ void densex_pack_kernel(const float* __restrict__ w, const float* __r
             const int e = k + i, c = 16 * mt + (e & 15);
             v[i] = c < C ? (e < 16 ? (scale ? scale[c] : 1.f) : (shift ? shift[c] : 0.f)) : 0.f;
         }
-        o = (u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]), __builtin_bit_cast(uint32_t, v[2]),
+        o = (otp_u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]), __builtin_bit_cast(uint32_t, v[2]),
                     __builtin_bit_cast(uint32_t, v[3])};
     }
-    reinterpret_cast<u32x4*>(packed)[idx] = o;
-}
-
-// copy one weight block global -> LDS with the LDS-DMA (256 threads): unit u (16 bytes) lands at lds + 16 u
-template <int BLKB>
-__device__ __forceinline__ void dx_stage(const unsigned char* __restrict__ src, unsigned char* lds) {
-    constexpr int NST = BLKB / 16 / 256;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-#pragma unroll
-    for (int i = 0; i < NST; ++i) {
-        const int u0 = i * 256 + wave * 64;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)(u0 + lane) * 16),
-                                         (__attribute__((address_space(3))) void*)(lds + u0 * 16), 16, 0, 0);
-    }
+    reinterpret_cast<otp_u32x4*>(packed)[idx] = o;
 }
 
 // all MT output blocks of one problem for the wave's 32 tokens: X (split fragments) x streamed weight blocks -> out.
@@ -100,10 +61,9 @@ __device__ __forceinline__ void dx_stage(const unsigned char* __restrict__ src, 
 // lanes without a token or channel masked by an out-of-range buffer offset - so the barrier at the end of a block can wait for
 // the DMA alone (`s_waitcnt vmcnt(4)`: all but the four stores, which stay in flight under the next block's MFMAs) instead of
 // the `vmcnt(0)` of __syncthreads(), which made every block pay a store round trip.
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 // H1: the fp16 engine's arithmetic - the hi pieces only (operands rounded to half once), one MFMA per product
 template <int C, bool RES, bool H1 = false>
-__device__ __forceinline__ void dx_project(const h16x8 (&Xh)[dx_ks(C)][2], const h16x8 (&Xl)[dx_ks(C)][2],
+__device__ __forceinline__ void dx_project(const otp_x3x8 (&Xh)[dx_ks(C)][2], const otp_x3x8 (&Xl)[dx_ks(C)][2],
                                            const unsigned char* __restrict__ packed, unsigned char* lds,
                                            const float* __restrict__ res, float* __restrict__ out, size_t base, int T, int tok,
                                            bool valid, unsigned* rflag) {
@@ -116,23 +76,23 @@ __device__ __forceinline__ void dx_project(const h16x8 (&Xh)[dx_ks(C)][2], const
 #pragma unroll 1
     for (int mt = 0; mt < MT; ++mt) {
         int voff[4];
-        f32x2 r[4];
+        otp_f32x2 r[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int c = 16 * mt + 4 * kq + i;
             voff[i] = (valid && c < C) ? (c * T + tok) * 4 : -16;                // masked lanes: past the descriptor
-            if (RES) r[i] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rr, voff[i], 0, 0));
+            if (RES) r[i] = __builtin_bit_cast(otp_f32x2, __builtin_amdgcn_raw_buffer_load_b64(rr, voff[i], 0, 0));
         }
         asm volatile("" ::: "memory");
-        if (mt + 1 < MT) dx_stage<BLKB>(packed + (size_t)(mt + 1) * BLKB, lds + ((mt + 1) & 1) * BLKB);
+        if (mt + 1 < MT) otp_lds_stage<256, BLKB>(packed + (size_t)(mt + 1) * BLKB, lds + ((mt + 1) & 1) * BLKB);
         asm volatile("" ::: "memory");
         const unsigned char* P = lds + (mt & 1) * BLKB;
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+        otp_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            const h16x8 ah = *reinterpret_cast<const h16x8*>(P + (ks * 2) * 1024 + lane * 16);
+            const otp_x3x8 ah = *reinterpret_cast<const otp_x3x8*>(P + (ks * 2) * 1024 + lane * 16);
             if constexpr (!H1) {
-                const h16x8 al = *reinterpret_cast<const h16x8*>(P + (ks * 2 + 1) * 1024 + lane * 16);
+                const otp_x3x8 al = *reinterpret_cast<const otp_x3x8*>(P + (ks * 2 + 1) * 1024 + lane * 16);
                 acc0 = OTP_X3_MFMA(al, Xh[ks][0], acc0, 0, 0, 0);
                 acc1 = OTP_X3_MFMA(al, Xh[ks][1], acc1, 0, 0, 0);
                 acc0 = OTP_X3_MFMA(ah, Xl[ks][0], acc0, 0, 0, 0);
@@ -141,15 +101,15 @@ __device__ __forceinline__ void dx_project(const h16x8 (&Xh)[dx_ks(C)][2], const
             acc0 = OTP_X3_MFMA(ah, Xh[ks][0], acc0, 0, 0, 0);
             acc1 = OTP_X3_MFMA(ah, Xh[ks][1], acc1, 0, 0, 0);
         }
-        const f32x4 sc = *reinterpret_cast<const f32x4*>(P + KS * 2048 + 16 * kq);
-        const f32x4 sh = *reinterpret_cast<const f32x4*>(P + KS * 2048 + 64 + 16 * kq);
+        const otp_f32x4 sc = *reinterpret_cast<const otp_f32x4*>(P + KS * 2048 + 16 * kq);
+        const otp_f32x4 sh = *reinterpret_cast<const otp_f32x4*>(P + KS * 2048 + 64 + 16 * kq);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            f32x2 v = {acc0[i] * sc[i] + sh[i], acc1[i] * sc[i] + sh[i]};
+            otp_f32x2 v = {acc0[i] * sc[i] + sh[i], acc1[i] * sc[i] + sh[i]};
             if (RES) v += r[i];
             bad |= otp_out_of_range(v.x);
                 bad |= otp_out_of_range(v.y);
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), ro, voff[i], 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(otp_u32x2, v), ro, voff[i], 0, 0);
         }
         if (mt + 1 < MT) {
             asm volatile("s_waitcnt vmcnt(4)" ::: "memory");      // this wave's part of block mt + 1 has landed; the stores fly on
@@ -177,8 +137,8 @@ __global__ __launch_bounds__(256, 2) void densex_cc_kernel(DxArgs A, int T, int 
     const bool valid = tok < T;
     const size_t base = (size_t)b * C * T;
     const float* __restrict__ x = A.x[blockIdx.y];
-    dx_stage<BLKB>(A.packed[blockIdx.y], lds);
-    h16x8 Xh[KS][2], Xl[KS][2];
+    otp_lds_stage<256, BLKB>(A.packed[blockIdx.y], lds);
+    otp_x3x8 Xh[KS][2], Xl[KS][2];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         float v0[8], v1[8];
@@ -186,12 +146,12 @@ __global__ __launch_bounds__(256, 2) void densex_cc_kernel(DxArgs A, int T, int 
         for (int j = 0; j < 8; ++j) {
             const int c = 32 * ks + 8 * kq + j;
             const bool live = 32 * ks + 24 + j < C || c < C;
-            const f32x2 v = *reinterpret_cast<const f32x2*>(x + base + (size_t)(live ? c : 0) * T + (valid ? tok : T - 2));
+            const otp_f32x2 v = *reinterpret_cast<const otp_f32x2*>(x + base + (size_t)(live ? c : 0) * T + (valid ? tok : T - 2));
             v0[j] = live ? v.x : 0.f;
             v1[j] = live ? v.y : 0.f;
         }
-        dx_split8(v0, Xh[ks][0], Xl[ks][0]);
-        dx_split8(v1, Xh[ks][1], Xl[ks][1]);
+        otp_x3_split8(v0, Xh[ks][0], Xl[ks][0]);
+        otp_x3_split8(v1, Xh[ks][1], Xl[ks][1]);
     }
     __syncthreads();
     dx_project<C, true, H1>(Xh, Xl, A.packed[blockIdx.y], lds, A.res[blockIdx.y], A.out[blockIdx.y], base, T, tok, valid, rflag);
@@ -221,12 +181,12 @@ __global__ __launch_bounds__(256, C <= 136 ? 3 : 1) void qkvx_front_kernel(const
     constexpr float inv_c = 1.f / (float)C;
     const int vb0 = (8 * kq * T + tokc) * 4;
     for (int i = tid; i < TAB / 4; i += 256)
-        reinterpret_cast<f32x4*>(tab)[i] = reinterpret_cast<const f32x4*>(table)[i];
+        reinterpret_cast<otp_f32x4*>(tab)[i] = reinterpret_cast<const otp_f32x4*>(table)[i];
     __syncthreads();
 
     // one problem (q, k or v) per workgroup: blockIdx.y (three times the workgroups, a third of the serial work each)
     for (int p = (int)blockIdx.y; p <= (int)blockIdx.y; ++p) {
-        dx_stage<BLKB>(A.packed[p], lds);
+        otp_lds_stage<256, BLKB>(A.packed[p], lds);
         const float* tp = tab + p * C * 8;
         // depthwise k = 3 over the wave's token pair and its two neighbours (re-read per problem: L1 / L2 hits), per channel
         float X0[KS][8], X1[KS][8];
@@ -240,17 +200,17 @@ __global__ __launch_bounds__(256, C <= 136 ? 3 : 1) void qkvx_front_kernel(const
                 // lane part of the address in one VGPR (masked lanes point past the descriptor: zeros), the channel's uniform
                 // part in the scalar offset - 120 distinct vector addresses would otherwise be hoisted out of the problem loop
                 const int so = (32 * ks + j) * T * 4;
-                const f32x2 m = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rx, live ? vb0 : -16, so, 0));
+                const otp_f32x2 m = __builtin_bit_cast(otp_f32x2, __builtin_amdgcn_raw_buffer_load_b64(rx, live ? vb0 : -16, so, 0));
                 const float la = bload(rx, live ? vb0 - 4 : -16, so), ld = bload(rx, live ? vb0 + 8 : -16, so);
                 const float a = l_ok ? la : 0.f, d = r_ok ? ld : 0.f;
-                const f32x4 w = *reinterpret_cast<const f32x4*>(tp + (live ? c : 0) * 8);
+                const otp_f32x4 w = *reinterpret_cast<const otp_f32x4*>(tp + (live ? c : 0) * 8);
                 X0[ks][j] = live ? w[0] * a + w[1] * m.x + w[2] * m.y : 0.f;
                 X1[ks][j] = live ? w[0] * m.x + w[1] * m.y + w[2] * d : 0.f;
                 s0 += X0[ks][j];
                 s1 += X1[ks][j];
             }
         }
-        const float m0 = dx_kslot_sum(s0) * inv_c, m1 = dx_kslot_sum(s1) * inv_c;
+        const float m0 = otp_kslot_sum(s0) * inv_c, m1 = otp_kslot_sum(s1) * inv_c;
         float v0 = 0.f, v1 = 0.f;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
@@ -262,8 +222,8 @@ __global__ __launch_bounds__(256, C <= 136 ? 3 : 1) void qkvx_front_kernel(const
                 v0 += X0[ks][j] * X0[ks][j];
                 v1 += X1[ks][j] * X1[ks][j];
             }
-        const float r0 = 1.f / sqrtf(dx_kslot_sum(v0) * inv_c + eps), r1 = 1.f / sqrtf(dx_kslot_sum(v1) * inv_c + eps);
-        h16x8 Xh[KS][2], Xl[KS][2];
+        const float r0 = 1.f / sqrtf(otp_kslot_sum(v0) * inv_c + eps), r1 = 1.f / sqrtf(otp_kslot_sum(v1) * inv_c + eps);
+        otp_x3x8 Xh[KS][2], Xl[KS][2];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
 #pragma unroll
@@ -274,8 +234,8 @@ __global__ __launch_bounds__(256, C <= 136 ? 3 : 1) void qkvx_front_kernel(const
                 X0[ks][j] = live ? X0[ks][j] * r0 * g + be : 0.f;
                 X1[ks][j] = live ? X1[ks][j] * r1 * g + be : 0.f;
             }
-            dx_split8(X0[ks], Xh[ks][0], Xl[ks][0]);
-            dx_split8(X1[ks], Xh[ks][1], Xl[ks][1]);
+            otp_x3_split8(X0[ks], Xh[ks][0], Xl[ks][0]);
+            otp_x3_split8(X1[ks], Xh[ks][1], Xl[ks][1]);
         }
         __syncthreads();                              // weight block 0 of this problem landed
         dx_project<C, false, H1>(Xh, Xl, A.packed[p], lds, nullptr, A.out[p], base, T, tok, valid, rflag);

@@ -20,8 +20,6 @@
 
 namespace {
 
-__device__ __forceinline__ float fe_gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
-
 template <int C>
 __device__ __forceinline__ void fe_layer_norm(float (&v)[C], const float* __restrict__ g, const float* __restrict__ b, float eps) {
     float s = 0.f;
@@ -129,7 +127,7 @@ __global__ __launch_bounds__(256) void flow_back_kernel(const float* __restrict_
         float h = b1[m];
 #pragma unroll
         for (int c = 0; c < C; ++c) h = fmaf(W1[m * C + c], nn[c], h);
-        h = fe_gelu(h);
+        h = otp_gelu_erf(h);
 #pragma unroll
         for (int o = 0; o < C; ++o) acc[o] = fmaf(W2t[m * C + o], h, acc[o]);
     }

@@ -38,10 +38,6 @@ typedef _Float16 h16;
 #endif
 typedef h16 h16x8 __attribute__((ext_vector_type(8)));
 typedef h16 h16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 #ifdef OTP_H16_TIMING
 // development build only (tools/h16_timing.sh): per-workgroup phase stamps, never in libotpose_hip.so
@@ -54,8 +50,6 @@ __device__ unsigned long long otp_h16_stamps[8192 * 32];
 #define HSTAMP(slot)
 #endif
 
-constexpr int HKS = OTP_HB_KS;            // k-steps per 16-channel chunk: 18 (tap, group) slots of 8 channels in 5 x 4 (2 empty)
-constexpr int HOOB = -16;                 // buffer offset outside every descriptor: loads return / the LDS-DMA writes zeros
 // packed weights of a (cout block, 16-channel chunk): 4 full k-steps x NTW tiles x 1 KB, then the half-filled fifth (k-slots 16, 17
 // on lanes 0 .. 31: 512 bytes per tile)
 __host__ __device__ constexpr int hwb(int ntw) { return otp_hb_wb(ntw); }
@@ -67,47 +61,22 @@ __host__ __device__ constexpr int hsred(int ntw) { return 4 * 2 * ntw * 16 * 4; 
 __host__ __device__ constexpr int hsred(int) { return 0; }
 #endif
 
-__device__ __forceinline__ uint32_t hdiv(uint32_t i, uint32_t magic) { return magic ? __umulhi(i, magic) : i; }
-// a * b for per-lane index arithmetic whose operands stay below 2^24 (checked by the plan): v_mul_u32_u24 runs at full rate,
-// v_mul_lo_u32 at a quarter - 40 of them sat in the set-up of every tile
-__device__ __forceinline__ int hmul(int a, int b) { return (int)__umul24((unsigned)a, (unsigned)b); }
-uint32_t hmagic(uint32_t d) { return d <= 1 ? 0u : (uint32_t)((1ull << 32) / d) + 1u; }   // exact while i * d < 2^32
-
-__device__ __forceinline__ u32x4 hpack8(const float (&v)[8]) {
+__device__ __forceinline__ otp_u32x4 hpack8(const float (&v)[8]) {
     uint32_t h[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) h[i] = __builtin_bit_cast(uint32_t, (h16x2){(h16)v[2 * i], (h16)v[2 * i + 1]});
-    return (u32x4){h[0], h[1], h[2], h[3]};
+    return (otp_u32x4){h[0], h[1], h[2], h[3]};
 }
 #ifdef OTP_H16_BF16
-__device__ __forceinline__ f32x2 hwiden(uint32_t pair) {
-    return (f32x2){__builtin_bit_cast(float, pair << 16), __builtin_bit_cast(float, pair & 0xffff0000u)};
+__device__ __forceinline__ otp_f32x2 hwiden(uint32_t pair) {
+    return (otp_f32x2){__builtin_bit_cast(float, pair << 16), __builtin_bit_cast(float, pair & 0xffff0000u)};
 }
 #else
-__device__ __forceinline__ f32x2 hwiden(uint32_t pair) { return __builtin_convertvector(__builtin_bit_cast(h16x2, pair), f32x2); }
+__device__ __forceinline__ otp_f32x2 hwiden(uint32_t pair) { return __builtin_convertvector(__builtin_bit_cast(h16x2, pair), otp_f32x2); }
 #endif
 
-// sum over the 16 lanes of a DPP row (one MFMA pixel column group), every lane ends with the total (csrc/nhwc.hip: row16_sum)
-template <int CTRL>
-__device__ __forceinline__ float hdpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float hrow16_sum(float v) {
-    v += hdpp<0xB1>(v);           // quad_perm [1,0,3,2]
-    v += hdpp<0x4E>(v);           // quad_perm [2,3,0,1]
-    v += hdpp<0x124>(v);          // row_ror:4
-    v += hdpp<0x128>(v);          // row_ror:8
-    return v;
-}
-
-// Output-channel row of an MFMA tile <-> channel (the convention of csrc/convs.hip): cout tiles go in pairs (2 tp, 2 tp + 1) whose
-// rows are permuted so that lane (pixel, kl) ends up with 8 CONSECUTIVE channels 32 tp + 8 kl .. + 7 of its pixel = one H8 record;
-// a tile without a partner keeps the identity (4 consecutive channels per lane = half a record).
-// (the definitions live in csrc/hb.h: the bf16 build's weight packer is csrc/nhwc.hip's)
-__host__ __device__ inline bool hpaired(int co_blk, int t, int ntw, int Cout) { return otp_hb_paired(co_blk, t, ntw, Cout); }
-__host__ __device__ inline int hrow2ch(int co_blk, int t, int row, int ntw, int Cout) { return otp_hb_row2ch(co_blk, t, row, ntw, Cout); }
-
-// instruction order of one (k-step, pixel tile) block: NM MFMAs and NR LDS reads interleaved (csrc/convs.hip: sblock_sched)
+// instruction order of one (k-step, pixel tile) block: NM MFMAs and NR LDS reads interleaved (another order than
+// csrc/x3.h: otp_s8_block_sched - with one product per multiply there are fewer MFMAs per read)
 template <int NM, int NR>
 __device__ __forceinline__ void hblock_sched() {
     if constexpr (NR == 0) {
@@ -172,7 +141,7 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
                                                                                 const float* __restrict__ shift,
                                                                                 const unsigned char* res, unsigned char* out,
                                                                                 const HPlan P) {
-    constexpr int BM = 64 * NPT, WB = hwb(NTW), WU = WB / 16, NWJ = (WU + 255) / 256, NBLK = HKS * NPT, MAXJ = STRIDE == 1 ? 2 : 4;
+    constexpr int BM = 64 * NPT, WB = hwb(NTW), WU = WB / 16, NWJ = (WU + 255) / 256, NBLK = OTP_S8_KS * NPT, MAXJ = STRIDE == 1 ? 2 : 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int PL = P.pl, NPL = P.CK >> 3, SUB = P.CK >> 4;          // bytes of a window plane, planes / weight chunks per stage
     unsigned char* const wl = smem + NPL * PL;
@@ -192,7 +161,7 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
 #endif
     const int P0 = tile * BM;
     const int n0 = P0 / P.HWo, p0 = P0 - n0 * P.HWo;               // (uniform, once per workgroup)
-    const int y0 = (int)hdiv((uint32_t)p0, P.mWo);
+    const int y0 = (int)otp_magic_div((uint32_t)p0, P.mWo);
     const int x0 = STRIDE == 1 ? p0 - y0 * P.Wo : 0;               // stride 1: the window starts at record x0 of its first row
     const int Vf = n0 * P.VR + STRIDE * y0;                        // first virtual row of the window
     const int imgB = P.in_imgB;                                    // bytes of one image of the input tensor
@@ -207,12 +176,12 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
         const int v = 64 * (wave + 4 * j) + lane;
         vlive[j] = v < P.NV;
         const int vv = v + x0;
-        const int r = (int)hdiv((uint32_t)vv, P.mW1), i = vv - hmul(r, P.W1);
+        const int r = (int)otp_magic_div((uint32_t)vv, P.mW1), i = vv - otp_mul24(r, P.W1);
         const int V = Vf + r;
-        const int n = (int)hdiv((uint32_t)V, P.mVR), yy = V - hmul(n, P.VR);
+        const int n = (int)otp_magic_div((uint32_t)V, P.mVR), yy = V - otp_mul24(n, P.VR);
         const int col = STRIDE == 1 ? i - 1 : (i <= P.Wo ? 2 * (i - 1) + 1 : 2 * (i - P.Wo - 1));   // stride 2: odd columns, then even
         const bool ok = i >= 1 && yy >= 1 && n < P.N;
-        voff[j] = ok ? (n - n0) * imgB + hmul(hmul(yy - 1, P.W) + col, P.in_pS) : HOOB;    // (imgB may pass 2^24: a full multiply)
+        voff[j] = ok ? (n - n0) * imgB + otp_mul24(otp_mul24(yy - 1, P.W) + col, P.in_pS) : OTP_OOB;    // (imgB may pass 2^24: a full multiply)
     }
     const size_t left = (size_t)(P.N - n0) * imgB - P.in_base;
     const otp_rsrc rin = make_rsrc32(xs + (size_t)n0 * imgB + P.in_base, left > 0x7fffff00ull ? 0x7fffff00u : (unsigned)left);
@@ -234,18 +203,18 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
         }
     };
     // the weights of 16-channel chunk c: global -> registers (under the previous chunk's MFMAs) -> LDS; unit u = tid + 256 j
-    u32x4 wr[4];                                                   // (fixed bound, NWJ <= 4: see voff above)
+    otp_u32x4 wr[4];                                                   // (fixed bound, NWJ <= 4: see voff above)
     static_assert(NWJ <= 4, "weight units per thread");
     auto wload = [&](int c) __attribute__((always_inline)) {
         const int wb = (cb * P.nChunks + c) * WB;
 #pragma unroll
         for (int j = 0; j < NWJ; ++j)
-            wr[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, tid + 256 * j < WU ? (tid + 256 * j) * 16 : HOOB, wb, 0));
+            wr[j] = __builtin_bit_cast(otp_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, tid + 256 * j < WU ? (tid + 256 * j) * 16 : OTP_OOB, wb, 0));
     };
     auto wstore = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < NWJ; ++j)
-            if (tid + 256 * j < WU) *reinterpret_cast<u32x4*>(wl + (tid + 256 * j) * 16) = wr[j];
+            if (tid + 256 * j < WU) *reinterpret_cast<otp_u32x4*>(wl + (tid + 256 * j) * 16) = wr[j];
     };
     stage_window(0);
     wload(0);
@@ -256,24 +225,24 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
     const otp_rsrc ro = make_rsrc32(out + P.out_base, obytes);
     const otp_rsrc rr = make_rsrc32(res ? res + P.res_base : xs, res ? (unsigned)((size_t)P.N * P.res_imgB - P.res_base) : 0u);
     const otp_rsrc rsh = make_rsrc32(shift ? shift : reinterpret_cast<const float*>(xs), shift ? (unsigned)(P.Cout * 4) : 0u);
-    int pb[NPT], toff[HKS], offO[NPT], offR[NPT], ch0[NTW];
-    f32x4 acc[NTW][NPT];
+    int pb[NPT], toff[OTP_S8_KS], offO[NPT], offR[NPT], ch0[NTW];
+    otp_f32x4 acc[NTW][NPT];
     {
 #pragma unroll
-        for (int s = 0; s < HKS; ++s) {
+        for (int s = 0; s < OTP_S8_KS; ++s) {
             const int q = 4 * s + kl;
             int tap = q >> 1;
             if (tap > 8) tap = 8;                                  // zero weights: any finite data
             const int dy = tap / 3, dx = tap - dy * 3;
             // record of the tap relative to the pixel's record of tap row dy = 0 (stride 2: parity de-interleaved virtual rows)
             const int rx = STRIDE == 1 ? dx - x0 : (dx == 0 ? 0 : (dx == 1 ? P.Wo + 1 : 1));
-            toff[s] = (hmul(dy, P.W1) + rx) * 16 + (q & 1) * PL;
+            toff[s] = (otp_mul24(dy, P.W1) + rx) * 16 + (q & 1) * PL;
         }
-        f32x4 sh[NTW];
+        otp_f32x4 sh[NTW];
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
-            ch0[t] = hrow2ch(co_blk, t, 4 * kl, NTW, P.Cout);
-            sh[t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsh, co_blk + 16 * t < P.Cout ? ch0[t] * 4 : HOOB, 0, 0));
+            ch0[t] = otp_row2ch(co_blk, t, 4 * kl, NTW, P.Cout);
+            sh[t] = __builtin_bit_cast(otp_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsh, co_blk + 16 * t < P.Cout ? ch0[t] * 4 : OTP_OOB, 0, 0));
         }
 #pragma unroll
         for (int p = 0; p < NPT; ++p) {
@@ -281,11 +250,11 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
             const bool pv = P0 + m < P.total;
             if (!pv) m = P.total - 1 - P0;                         // tail tile: a finite address, the result is dropped
             const int q = p0 + m;
-            const int dn = (int)hdiv((uint32_t)q, P.mHWo), pi = q - hmul(dn, P.HWo);
-            const int y = (int)hdiv((uint32_t)pi, P.mWo), x = pi - hmul(y, P.Wo);
-            pb[p] = (hmul(hmul(n0 + dn, P.VR) + STRIDE * y - Vf, P.W1) + x) * 16;
-            offO[p] = pv ? (n0 + dn) * P.out_imgB + hmul(pi, P.out_pS) : HOOB;
-            offR[p] = (pv && res) ? (n0 + dn) * P.res_imgB + hmul(pi, P.res_pS) : HOOB;
+            const int dn = (int)otp_magic_div((uint32_t)q, P.mHWo), pi = q - otp_mul24(dn, P.HWo);
+            const int y = (int)otp_magic_div((uint32_t)pi, P.mWo), x = pi - otp_mul24(y, P.Wo);
+            pb[p] = (otp_mul24(otp_mul24(n0 + dn, P.VR) + STRIDE * y - Vf, P.W1) + x) * 16;
+            offO[p] = pv ? (n0 + dn) * P.out_imgB + otp_mul24(pi, P.out_pS) : OTP_OOB;
+            offR[p] = (pv && res) ? (n0 + dn) * P.res_imgB + otp_mul24(pi, P.res_pS) : OTP_OOB;
 #pragma unroll
             for (int t = 0; t < NTW; ++t) acc[t][p] = sh[t] * P.pre;
         }
@@ -299,12 +268,12 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
         auto load_a = [&](int ab, int s) __attribute__((always_inline)) {
 #pragma unroll
             for (int t = 0; t < NTW; ++t) {
-                if (s < HKS - 1) {
+                if (s < OTP_S8_KS - 1) {
                     a[ab][t] = *reinterpret_cast<const h16x8*>(wl + (s * NTW + t) * 1024 + lane * 16);
                 } else {
                     // last k-step: k-slots 16, 17 (tap 8) on the lanes kl = 0, 1; kl = 2, 3 multiply zeros (not stored)
-                    const h16x8 h = *reinterpret_cast<const h16x8*>(wl + (HKS - 1) * NTW * 1024 + t * 512 + (lane & 31) * 16);
-                    const h16x8 z = __builtin_bit_cast(h16x8, (u32x4){0u, 0u, 0u, 0u});
+                    const h16x8 h = *reinterpret_cast<const h16x8*>(wl + (OTP_S8_KS - 1) * NTW * 1024 + t * 512 + (lane & 31) * 16);
+                    const h16x8 z = __builtin_bit_cast(h16x8, (otp_u32x4){0u, 0u, 0u, 0u});
                     a[ab][t] = upper ? z : h;
                 }
             }
@@ -319,7 +288,7 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
         for (int blk = 0; blk < NBLK; ++blk) {
             const int s = blk / NPT, p = blk % NPT, cur = blk % 3, sa = s & 1;
             const bool nb = blk + 2 < NBLK;
-            const bool na = (NPT >= 2 ? p == NPT - 2 : true) && s + 1 < HKS;
+            const bool na = (NPT >= 2 ? p == NPT - 2 : true) && s + 1 < OTP_S8_KS;
             if (nb) load_b((blk + 2) % 3, blk + 2);
             if (na) load_a(sa ^ 1, s + 1);
 #pragma unroll
@@ -367,24 +336,24 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
     // ---- epilogue: post scale, residual, range guard, ReLU, one rounding to half, 16-byte record stores ------------------------
     // (the residual records are loaded here, not held across the chunk loop: 24 registers less is a fourth workgroup per CU, and
     //  another workgroup's MFMAs cover the round trip)
-    u32x4 rres[(NTW + 1) / 2][NPT];
+    otp_u32x4 rres[(NTW + 1) / 2][NPT];
     constexpr bool load_res = MODE == 2;                           // (a template variant: the plain form carries no residual loads / adds)
 #pragma unroll
     for (int t = 0; load_res && t < NTW; t += 2) {
         const bool tav = ch0[t] < P.Cout;                          // (per lane: Cout % 8 == 0, a lane's record exists or does not)
-        const int go = hmul(ch0[t] >> 3, P.res_gS);
-        if (hpaired(co_blk, t, NTW, P.Cout)) {
+        const int go = otp_mul24(ch0[t] >> 3, P.res_gS);
+        if (otp_tile_paired(co_blk, t, NTW, P.Cout)) {
 #pragma unroll
             for (int p = 0; p < NPT; ++p)
-                rres[t >> 1][p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                    rr, (tav && offR[p] != HOOB) ? offR[p] + go : HOOB, 0, 0));
+                rres[t >> 1][p] = __builtin_bit_cast(otp_u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                    rr, (tav && offR[p] != OTP_OOB) ? offR[p] + go : OTP_OOB, 0, 0));
         } else {
             const int half = (ch0[t] >> 2) & 1;
 #pragma unroll
             for (int p = 0; p < NPT; ++p) {
-                const u32x2 h = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(
-                    rr, (tav && offR[p] != HOOB) ? offR[p] + go + 8 * half : HOOB, 0, 0));
-                rres[t >> 1][p] = (u32x4){h[0], h[1], 0u, 0u};
+                const otp_u32x2 h = __builtin_bit_cast(otp_u32x2, __builtin_amdgcn_raw_buffer_load_b64(
+                    rr, (tav && offR[p] != OTP_OOB) ? offR[p] + go + 8 * half : OTP_OOB, 0, 0));
+                rres[t >> 1][p] = (otp_u32x4){h[0], h[1], 0u, 0u};
             }
         }
     }
@@ -398,19 +367,19 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
     float* sred = reinterpret_cast<float*>(wl + WB);               // [4 waves][2][CB]
 #pragma unroll
     for (int t = 0; t < NTW; t += 2) {
-        const bool paired = hpaired(co_blk, t, NTW, P.Cout);       // (uniform)
+        const bool paired = otp_tile_paired(co_blk, t, NTW, P.Cout);       // (uniform)
         const int t1 = t + 1 < NTW ? t + 1 : t;
         const bool tav = ch0[t] < P.Cout;                          // (per lane)
-        const int go = hmul(ch0[t] >> 3, P.out_gS);
+        const int go = otp_mul24(ch0[t] >> 3, P.out_gS);
         float s1[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, s2[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int p = 0; p < NPT; ++p) {
             float f[8] = {acc[t][p][0], acc[t][p][1], acc[t][p][2], acc[t][p][3], paired ? acc[t1][p][0] : 0.f,
                           paired ? acc[t1][p][1] : 0.f, paired ? acc[t1][p][2] : 0.f, paired ? acc[t1][p][3] : 0.f};
-            u32x4 rec = hpack8(f);
-            const bool pv = offO[p] != HOOB;
+            otp_u32x4 rec = hpack8(f);
+            const bool pv = offO[p] != OTP_OOB;
             if constexpr (MODE != 0) {
-                const f32x2 w0 = hwiden(rec[0]), w1 = hwiden(rec[1]), w2 = hwiden(rec[2]), w3 = hwiden(rec[3]);
+                const otp_f32x2 w0 = hwiden(rec[0]), w1 = hwiden(rec[1]), w2 = hwiden(rec[2]), w3 = hwiden(rec[3]);
                 float fr[8] = {w0.x, w0.y, w1.x, w1.y, w2.x, w2.y, w3.x, w3.y};
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
@@ -419,17 +388,17 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
                     s2[e] += v * v;
                 }
                 if constexpr (MODE == 2) {
-                    const u32x4 rq = rres[t >> 1][p];
-                    const f32x2 r0 = hwiden(rq[0]), r1 = hwiden(rq[1]), r2 = hwiden(rq[2]), r3 = hwiden(rq[3]);
+                    const otp_u32x4 rq = rres[t >> 1][p];
+                    const otp_f32x2 r0 = hwiden(rq[0]), r1 = hwiden(rq[1]), r2 = hwiden(rq[2]), r3 = hwiden(rq[3]);
                     float g[8] = {fr[0] + r0.x, fr[1] + r0.y, fr[2] + r1.x, fr[3] + r1.y, fr[4] + r2.x, fr[5] + r2.y, fr[6] + r3.x, fr[7] + r3.y};
                     rec = hpack8(g);
                 }
             }
             if (paired) {
-                __builtin_amdgcn_raw_buffer_store_b128(rec, ro, (tav && pv) ? offO[p] + go : HOOB, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(rec, ro, (tav && pv) ? offO[p] + go : OTP_OOB, 0, 0);
             } else {
                 const int half = (ch0[t] >> 2) & 1;
-                __builtin_amdgcn_raw_buffer_store_b64((u32x2){rec[0], rec[1]}, ro, (tav && pv) ? offO[p] + go + 8 * half : HOOB, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b64((otp_u32x2){rec[0], rec[1]}, ro, (tav && pv) ? offO[p] + go + 8 * half : OTP_OOB, 0, 0);
             }
         }
         if constexpr (MODE == 1) {
@@ -437,7 +406,7 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 if (e < 4 || paired) {
-                    const float a = hrow16_sum(s1[e]), b = hrow16_sum(s2[e]);
+                    const float a = otp_row16_sum(s1[e]), b = otp_row16_sum(s2[e]);
                     if (i16 == 0) {
                         sred[(wave * 2 + 0) * CB + cl + e] = a;
                         sred[(wave * 2 + 1) * CB + cl + e] = b;
@@ -462,14 +431,14 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
     bool bad = false;
 #pragma unroll
     for (int t = 0; t < NTW; t += 2) {
-        const bool paired = hpaired(co_blk, t, NTW, P.Cout);       // (uniform)
+        const bool paired = otp_tile_paired(co_blk, t, NTW, P.Cout);       // (uniform)
         const int t1 = t + 1 < NTW ? t + 1 : t;
         const bool tav = ch0[t] < P.Cout;                          // (per lane)
-        const int go = hmul(ch0[t] >> 3, P.out_gS);
+        const int go = otp_mul24(ch0[t] >> 3, P.out_gS);
 #pragma unroll
         for (int p = 0; p < NPT; ++p) {
-            const u32x4 rq = load_res ? rres[t >> 1][p] : (u32x4){0u, 0u, 0u, 0u};
-            const f32x2 r0 = hwiden(rq[0]), r1 = hwiden(rq[1]), r2 = hwiden(rq[2]), r3 = hwiden(rq[3]);
+            const otp_u32x4 rq = load_res ? rres[t >> 1][p] : (otp_u32x4){0u, 0u, 0u, 0u};
+            const otp_f32x2 r0 = hwiden(rq[0]), r1 = hwiden(rq[1]), r2 = hwiden(rq[2]), r3 = hwiden(rq[3]);
             float f[8] = {acc[t][p][0] * P.post + r0.x, acc[t][p][1] * P.post + r0.y, acc[t][p][2] * P.post + r1.x,
                           acc[t][p][3] * P.post + r1.y,
                           paired ? acc[t1][p][0] * P.post + r2.x : 0.f, paired ? acc[t1][p][1] * P.post + r2.y : 0.f,
@@ -480,12 +449,12 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
 #pragma unroll
                 for (int e = 0; e < 8; ++e) f[e] = otp_relu(f[e]);
             }
-            const u32x4 rec = hpack8(f);
+            const otp_u32x4 rec = hpack8(f);
             if (paired) {
-                __builtin_amdgcn_raw_buffer_store_b128(rec, ro, (tav && offO[p] != HOOB) ? offO[p] + go : HOOB, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(rec, ro, (tav && offO[p] != OTP_OOB) ? offO[p] + go : OTP_OOB, 0, 0);
             } else {
                 const int half = (ch0[t] >> 2) & 1;
-                __builtin_amdgcn_raw_buffer_store_b64((u32x2){rec[0], rec[1]}, ro, (tav && offO[p] != HOOB) ? offO[p] + go + 8 * half : HOOB,
+                __builtin_amdgcn_raw_buffer_store_b64((otp_u32x2){rec[0], rec[1]}, ro, (tav && offO[p] != OTP_OOB) ? offO[p] + go + 8 * half : OTP_OOB,
                                                       0, 0);
             }
         }
@@ -604,7 +573,7 @@ bool h16_conv_plan(const otp_h16_conv_desc& d, HPlan& P, bool nhwc = false) {
     }
     P.tpx = (P.nTiles + 7) / 8;
     P.NIW = (P.NV + 63) / 64;
-    P.mHWo = hmagic(P.HWo); P.mWo = hmagic(Wo); P.mW1 = hmagic(P.W1); P.mVR = hmagic(P.VR);
+    P.mHWo = otp_magic(P.HWo); P.mWo = otp_magic(Wo); P.mW1 = otp_magic(P.W1); P.mVR = otp_magic(P.VR);
     // exactness of the magic divisions (numerator * divisor < 2^32) and 31-bit byte offsets
     if ((long)(P.HWo + 256) * P.HWo >= (1l << 32) || (long)P.HWo * Wo >= (1l << 32)) return false;
     if ((long)(d.N + 2) * P.VR * P.VR >= (1l << 32) || (long)(maxrec + d.W + 2) * P.W1 >= (1l << 32)) return false;
@@ -612,7 +581,7 @@ bool h16_conv_plan(const otp_h16_conv_desc& d, HPlan& P, bool nhwc = false) {
     if ((size_t)d.N * P.out_imgB >= (1ull << 31) || (size_t)d.N * P.res_imgB >= (1ull << 31)) return false;
     if ((size_t)P.nN * P.nChunks * hwb(P.NTW) >= (1ull << 31)) return false;
     if (P.HWo < 16) return false;
-    // operands of the 24-bit multiplies of the kernel's index arithmetic (hmul)
+    // operands of the 24-bit multiplies of the kernel's index arithmetic (otp_mul24)
     if (P.HW >= (1 << 24) || (long)(d.N + 2) * P.VR >= (1l << 24) || (long)(maxrec + 2 * d.W + 8) >= (1l << 24) ||
         (long)(d.N + 2) * P.VR * 2 + 2 * d.H >= (1l << 24) || P.in_pS >= (1 << 24) || P.out_pS >= (1 << 24) || P.in_gS >= (1 << 24) ||
         P.out_gS >= (1 << 24) || d.Cout / 8 >= (1 << 24))
@@ -669,19 +638,19 @@ int h16_conv_dispatch(const void* xs, const void* wpk, const float* fs, const vo
 
 #ifndef OTP_H16_BF16
 // packed weights: [cout block][chunk][k-step][cout tile][lane] 16-byte A fragments, lane (i16, kl): row i16 of the tile = channel
-// hrow2ch(block, tile, i16), k-slot q = 4 s + kl -> tap q / 2, input channels 16 chunk + 8 (q % 2) .. + 7; the fifth k-step holds
+// otp_row2ch(block, tile, i16), k-slot q = 4 s + kl -> tap q / 2, input channels 16 chunk + 8 (q % 2) .. + 7; the fifth k-step holds
 // k-slots 16, 17 only (32 lanes per tile)
-__global__ void h16_wpack_kernel(const float* __restrict__ w, const float* __restrict__ scale, u32x4* __restrict__ out, int Cout,
+__global__ void h16_wpack_kernel(const float* __restrict__ w, const float* __restrict__ scale, otp_u32x4* __restrict__ out, int Cout,
                                  int Cin, int NTW, int nN, int nChunks, float pre) {
-    const int total = nN * nChunks * HKS * NTW * 64;
+    const int total = nN * nChunks * OTP_S8_KS * NTW * 64;
     const int WU = hwb(NTW) / 16;                                   // 16-byte units of one (cout block, chunk) image
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int lane = idx & 63;
         int r = idx >> 6;
         const int t = r % NTW; r /= NTW;
-        const int s = r % HKS; r /= HKS;
+        const int s = r % OTP_S8_KS; r /= OTP_S8_KS;
         const int chunk = r % nChunks, cb = r / nChunks;
-        const int cout = hrow2ch(cb * NTW * 16, t, lane & 15, NTW, Cout), kl = lane >> 4;
+        const int cout = otp_row2ch(cb * NTW * 16, t, lane & 15, NTW, Cout), kl = lane >> 4;
         const int q = 4 * s + kl, tap = q >> 1, ci0 = chunk * 16 + 8 * (q & 1);
         if (tap > 8) continue;
         float v[8];
@@ -691,7 +660,7 @@ __global__ void h16_wpack_kernel(const float* __restrict__ w, const float* __res
             v[j] = (cout < Cout && ci < Cin) ? w[((size_t)cout * Cin + ci) * 9 + tap] * (scale ? scale[cout] : 1.f) * pre : 0.f;
         }
         const size_t base = (size_t)(cb * nChunks + chunk) * WU;
-        const size_t o = s < HKS - 1 ? base + (s * NTW + t) * 64 + lane : base + (HKS - 1) * NTW * 64 + t * 32 + lane;
+        const size_t o = s < OTP_S8_KS - 1 ? base + (s * NTW + t) * 64 + lane : base + (OTP_S8_KS - 1) * NTW * 64 + t * 32 + lane;
         out[o] = hpack8(v);
     }
 }
@@ -723,19 +692,6 @@ struct HPw {
     otp_hbpw_epi epi;                                             // bf16 build: the MLP epilogues (csrc/hb.h); mode 0: none
 };
 
-template <int BLKB>
-__device__ __forceinline__ void hpw_stage(const unsigned char* __restrict__ src, unsigned char* lds) {
-    constexpr int NST = BLKB / 16 / 256;
-    static_assert(NST * 256 * 16 == BLKB, "whole passes");
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-#pragma unroll
-    for (int i = 0; i < NST; ++i) {
-        const int u0 = i * 256 + wave * 64;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)(u0 + lane) * 16),
-                                         (__attribute__((address_space(3))) void*)(lds + u0 * 16), 16, 0, 0);
-    }
-}
-
 constexpr int HPW_MAXC = 1024;            // shift table: output channels
 // KS k-steps of 32 input channels (Cin padded with zero weights and masked loads); a weight block = one tile pair x KS x 1 KB each
 // = 2 KS KB, rounded up to whole 4 KB passes of the 256 threads
@@ -752,7 +708,7 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : (KS <= 8 ? 3 : 2)) void h16_poin
     float* sred = shl + HPW_MAXC;                                            // [2 buffers][4 waves][2][32]
 #endif
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, n16 = lane & 15;
-    hpw_stage<BLKB>(A.packed, lds);
+    otp_lds_stage<256, BLKB>(A.packed, lds);
     for (int i = tid; i < HPW_MAXC; i += 256) shl[i] = (A.shift && i < A.Cout) ? A.shift[i] : 0.f;
     // the lane's two pixels (tile h: flattened pixel base + 16 h + n16), their image and in-image index
     int img[2], pix[2];
@@ -766,16 +722,16 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : (KS <= 8 ? 3 : 2)) void h16_poin
         pix[h] = P - img[h] * A.HW;
     }
     const int Gin = A.Cin >> 3;
-    u32x4 X[KS][2];
+    otp_u32x4 X[KS][2];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int g = 4 * ks + kq;
             const bool live = g < Gin;                                         // groups past Cin: zero operands (and zero weights)
-            const u32x4* src = reinterpret_cast<const u32x4*>(A.x + A.x_base + img[h] * A.x_imgB + (live ? g : 0) * A.x_gS + pix[h] * A.x_pS);
-            const u32x4 v = *src;
-            X[ks][h] = live ? v : (u32x4){0u, 0u, 0u, 0u};
+            const otp_u32x4* src = reinterpret_cast<const otp_u32x4*>(A.x + A.x_base + img[h] * A.x_imgB + (live ? g : 0) * A.x_gS + pix[h] * A.x_pS);
+            const otp_u32x4 v = *src;
+            X[ks][h] = live ? v : (otp_u32x4){0u, 0u, 0u, 0u};
         }
     const float lo_clamp = A.relu ? 0.f : -__builtin_inff();
     bool bad = false;
@@ -783,22 +739,22 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : (KS <= 8 ? 3 : 2)) void h16_poin
 #pragma unroll 1
     for (int blk = 0; blk < A.nblk; ++blk) {
         // (the last trip re-stages block 0, which nobody reads: every wave issues the same instructions on every trip)
-        hpw_stage<BLKB>(A.packed + (size_t)(blk + 1 < A.nblk ? blk + 1 : 0) * BLKB, lds + ((blk + 1) & 1) * BLKB);
+        otp_lds_stage<256, BLKB>(A.packed + (size_t)(blk + 1 < A.nblk ? blk + 1 : 0) * BLKB, lds + ((blk + 1) & 1) * BLKB);
         asm volatile("" ::: "memory");
         const unsigned char* Pw = lds + (blk & 1) * BLKB;
         const int c8 = 32 * blk + 8 * kq;                                     // the lane's 8 output channels of this block
         const bool cl = c8 < A.Cout;
-        u32x4 rq[2];
+        otp_u32x4 rq[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            rq[h] = (u32x4){0u, 0u, 0u, 0u};
+            rq[h] = (otp_u32x4){0u, 0u, 0u, 0u};
             if (A.res && cl && pv[h])
-                rq[h] = *reinterpret_cast<const u32x4*>(A.res + A.r_base + img[h] * A.r_imgB + (c8 >> 3) * A.r_gS + pix[h] * A.r_pS);
+                rq[h] = *reinterpret_cast<const otp_u32x4*>(A.res + A.r_base + img[h] * A.r_imgB + (c8 >> 3) * A.r_gS + pix[h] * A.r_pS);
         }
-        f32x4 acc[2][2];                                                       // [tile of the pair][pixel tile]
+        otp_f32x4 acc[2][2];                                                       // [tile of the pair][pixel tile]
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
-            f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+            otp_f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const h16x8 aw = *reinterpret_cast<const h16x8*>(Pw + (m * KS + ks) * 1024 + lane * 16);
@@ -808,14 +764,14 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : (KS <= 8 ? 3 : 2)) void h16_poin
             acc[m][0] = a0;
             acc[m][1] = a1;
         }
-        const f32x4 sh0 = *reinterpret_cast<const f32x4*>(shl + (c8 & (HPW_MAXC - 1)));
-        const f32x4 sh1 = *reinterpret_cast<const f32x4*>(shl + ((c8 + 4) & (HPW_MAXC - 1)));
+        const otp_f32x4 sh0 = *reinterpret_cast<const otp_f32x4*>(shl + (c8 & (HPW_MAXC - 1)));
+        const otp_f32x4 sh1 = *reinterpret_cast<const otp_f32x4*>(shl + ((c8 + 4) & (HPW_MAXC - 1)));
 #ifdef OTP_H16_BF16
         float st1[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, st2[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #endif
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const f32x2 r0 = hwiden(rq[h][0]), r1 = hwiden(rq[h][1]), r2 = hwiden(rq[h][2]), r3 = hwiden(rq[h][3]);
+            const otp_f32x2 r0 = hwiden(rq[h][0]), r1 = hwiden(rq[h][1]), r2 = hwiden(rq[h][2]), r3 = hwiden(rq[h][3]);
 #ifdef OTP_H16_BF16
             float f[8] = {acc[0][h][0] + sh0[0], acc[0][h][1] + sh0[1], acc[0][h][2] + sh0[2], acc[0][h][3] + sh0[3],
                           acc[1][h][0] + sh1[0], acc[1][h][1] + sh1[1], acc[1][h][2] + sh1[2], acc[1][h][3] + sh1[3]};
@@ -828,8 +784,8 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : (KS <= 8 ? 3 : 2)) void h16_poin
 #ifdef OTP_H16_BF16
             if (A.res) {
                 // csrc/nhwc.hip's contract: the residual is added to the ROUNDED result and the sum rounded again (a separate bf16 add)
-                const u32x4 q = hpack8((const float(&)[8])f);
-                const f32x2 w0 = hwiden(q[0]), w1 = hwiden(q[1]), w2 = hwiden(q[2]), w3 = hwiden(q[3]);
+                const otp_u32x4 q = hpack8((const float(&)[8])f);
+                const otp_f32x2 w0 = hwiden(q[0]), w1 = hwiden(q[1]), w2 = hwiden(q[2]), w3 = hwiden(q[3]);
                 const float g[8] = {w0.x, w0.y, w1.x, w1.y, w2.x, w2.y, w3.x, w3.y};
                 const float rr[8] = {r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, r3.x, r3.y};
 #pragma unroll
@@ -846,9 +802,9 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : (KS <= 8 ? 3 : 2)) void h16_poin
                 // input gradient of the MLP's down-projection: times gelu'(pre-activation) and the dropout factor of the forward
                 const size_t eo = A.o_base + img[h] * A.o_imgB + (c8 >> 3) * A.o_gS + pix[h] * A.o_pS;
                 const bool lv = cl && pv[h];
-                const u32x4 hq = lv ? *reinterpret_cast<const u32x4*>(static_cast<const unsigned char*>(A.epi.aux) + eo) : (u32x4){0u, 0u, 0u, 0u};
+                const otp_u32x4 hq = lv ? *reinterpret_cast<const otp_u32x4*>(static_cast<const unsigned char*>(A.epi.aux) + eo) : (otp_u32x4){0u, 0u, 0u, 0u};
                 const unsigned bits = lv ? A.epi.keep[eo >> 4] : 0u;
-                const f32x2 h0 = hwiden(hq[0]), h1 = hwiden(hq[1]), h2 = hwiden(hq[2]), h3 = hwiden(hq[3]);
+                const otp_f32x2 h0 = hwiden(hq[0]), h1 = hwiden(hq[1]), h2 = hwiden(hq[2]), h3 = hwiden(hq[3]);
                 const float hv[8] = {h0.x, h0.y, h1.x, h1.y, h2.x, h2.y, h3.x, h3.y};
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
@@ -860,8 +816,8 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : (KS <= 8 ? 3 : 2)) void h16_poin
             if constexpr (EPI == 1) {
                 // per-tile channel sums of the ROUNDED values (csrc/nhwc.hip's contract: what BatchNorm will normalise): the 16 lanes of
                 // a DPP row hold 16 pixels of the lane's 8 channels
-                const u32x4 qv = hpack8((const float(&)[8])f);
-                const f32x2 w0 = hwiden(qv[0]), w1 = hwiden(qv[1]), w2 = hwiden(qv[2]), w3 = hwiden(qv[3]);
+                const otp_u32x4 qv = hpack8((const float(&)[8])f);
+                const otp_f32x2 w0 = hwiden(qv[0]), w1 = hwiden(qv[1]), w2 = hwiden(qv[2]), w3 = hwiden(qv[3]);
                 const float g[8] = {w0.x, w0.y, w1.x, w1.y, w2.x, w2.y, w3.x, w3.y};
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
@@ -879,18 +835,18 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : (KS <= 8 ? 3 : 2)) void h16_poin
                         if (c8 + e < A.Cout) o[(size_t)e * A.HW] = f[e];
                 } else {
                     const size_t eo = A.o_base + img[h] * A.o_imgB + (c8 >> 3) * A.o_gS + pix[h] * A.o_pS;
-                    const u32x4 rec = hpack8(f);
-                    *reinterpret_cast<u32x4*>(A.out + eo) = rec;
+                    const otp_u32x4 rec = hpack8(f);
+                    *reinterpret_cast<otp_u32x4*>(A.out + eo) = rec;
 #ifdef OTP_H16_BF16
                     if constexpr (EPI == 2) {
                         // dropout(gelu(.)) of the ROUNDED result (what a separate pass over the stored tensor computes), one rounding
-                        const f32x2 w0 = hwiden(rec[0]), w1 = hwiden(rec[1]), w2 = hwiden(rec[2]), w3 = hwiden(rec[3]);
+                        const otp_f32x2 w0 = hwiden(rec[0]), w1 = hwiden(rec[1]), w2 = hwiden(rec[2]), w3 = hwiden(rec[3]);
                         const float hv[8] = {w0.x, w0.y, w1.x, w1.y, w2.x, w2.y, w3.x, w3.y};
                         const unsigned bits = otp_drop_keep8(eo >> 4, A.epi.s0, A.epi.s1, A.epi.thr);
                         float g[8];
 #pragma unroll
                         for (int e = 0; e < 8; ++e) g[e] = ((bits >> e) & 1u) ? hv[e] * otp_phi_fast(hv[e]) * A.epi.scale : 0.f;
-                        *reinterpret_cast<u32x4*>(static_cast<unsigned char*>(A.epi.out2) + eo) = hpack8(g);
+                        *reinterpret_cast<otp_u32x4*>(static_cast<unsigned char*>(A.epi.out2) + eo) = hpack8(g);
                         A.epi.keep[eo >> 4] = (unsigned char)bits;
                     }
 #endif
@@ -902,7 +858,7 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : (KS <= 8 ? 3 : 2)) void h16_poin
             float* sr = sred + (blk & 1) * 256;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float a = hrow16_sum(st1[e]), b = hrow16_sum(st2[e]);
+                const float a = otp_row16_sum(st1[e]), b = otp_row16_sum(st2[e]);
                 if (n16 == 0) {
                     sr[(wave * 2 + 0) * 32 + 8 * kq + e] = a;
                     sr[(wave * 2 + 1) * 32 + 8 * kq + e] = b;
@@ -957,7 +913,7 @@ __global__ void h16_pw_pack_kernel(const float* __restrict__ w, const float* __r
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < nblk * units) {
         const int blk = idx / units, u = idx - blk * units;
-        u32x4 o = {0u, 0u, 0u, 0u};
+        otp_u32x4 o = {0u, 0u, 0u, 0u};
         if (u < 2 * KS * 64) {
             const int frag = u >> 6, lane = u & 63, m = frag / KS, ks = frag - m * KS, r16 = lane & 15, kq = lane >> 4;
             const int row = 32 * blk + 8 * (r16 >> 2) + 4 * m + (r16 & 3);
@@ -969,7 +925,7 @@ __global__ void h16_pw_pack_kernel(const float* __restrict__ w, const float* __r
             }
             o = hpack8(v);
         }
-        reinterpret_cast<u32x4*>(packed)[idx] = o;
+        reinterpret_cast<otp_u32x4*>(packed)[idx] = o;
     } else if (idx < nblk * units + HPW_MAXC / 4 + 1) {
         const int q = idx - nblk * units;
         float v[4] = {0.f, 0.f, 0.f, 0.f};
@@ -979,7 +935,7 @@ __global__ void h16_pw_pack_kernel(const float* __restrict__ w, const float* __r
         } else {
             v[0] = 1.f / pre;
         }
-        reinterpret_cast<u32x4*>(packed)[idx] = (u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]),
+        reinterpret_cast<otp_u32x4*>(packed)[idx] = (otp_u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]),
                                                         __builtin_bit_cast(uint32_t, v[2]), __builtin_bit_cast(uint32_t, v[3])};
     }
 }
@@ -995,8 +951,8 @@ int hpw_ks(int Cin) {
 constexpr int HST_CT = 4;                 // 16-channel output tiles (Cout <= 64)
 struct HSt {
     const float* in;
-    const u32x4* packed;
-    u32x4* out;
+    const otp_u32x4* packed;
+    otp_u32x4* out;
     int B, F, H, W, Ho, Wo, HoWo, Cout, total;
     uint32_t mWo;
     unsigned* rflag;
@@ -1005,7 +961,7 @@ struct HSt {
 // packed: [cout tile][64 lanes] A fragments (lane (row i16, kq): k slots 8 kq .. 8 kq + 7, k = 3 tap + channel; rows of a tile pair
 // permuted like everywhere in this file), then shift[64], then {post, 0, 0, 0}
 __global__ void h16_stem_pack_kernel(const float* __restrict__ w, const float* __restrict__ scale, const float* __restrict__ shift,
-                                     u32x4* __restrict__ packed, int Cout) {
+                                     otp_u32x4* __restrict__ packed, int Cout) {
     __shared__ float wmax[4];
     float m = 0.f;
     for (int i = threadIdx.x; i < Cout * 27; i += blockDim.x) m = fmaxf(m, fabsf(w[i] * (scale ? scale[i / 27] : 1.f)));
@@ -1018,7 +974,7 @@ __global__ void h16_stem_pack_kernel(const float* __restrict__ w, const float* _
     const int kx = (m > 0.f && m < 3e38f) ? min(40, max(-40, 14 - e)) : 0;
     const float pre = ldexpf(1.f, kx), post = ldexpf(1.f, -kx);
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx == HST_CT * 64 + 16) packed[idx] = (u32x4){__builtin_bit_cast(uint32_t, post), 0u, 0u, 0u};
+    if (idx == HST_CT * 64 + 16) packed[idx] = (otp_u32x4){__builtin_bit_cast(uint32_t, post), 0u, 0u, 0u};
     if (idx < HST_CT * 64) {
         const int t = idx >> 6, lane = idx & 63, r16 = lane & 15, kq = lane >> 4;
         const int co = 32 * (t >> 1) + 8 * (r16 >> 2) + 4 * (t & 1) + (r16 & 3);
@@ -1034,7 +990,7 @@ __global__ void h16_stem_pack_kernel(const float* __restrict__ w, const float* _
         float v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = (4 * q + i < Cout && shift) ? shift[4 * q + i] : 0.f;
-        packed[idx] = (u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]), __builtin_bit_cast(uint32_t, v[2]),
+        packed[idx] = (otp_u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]), __builtin_bit_cast(uint32_t, v[2]),
                               __builtin_bit_cast(uint32_t, v[3])};
     }
 }
@@ -1048,9 +1004,9 @@ __global__ __launch_bounds__(256) void h16_stem_kernel(HSt A) {
 #pragma unroll
     for (int t = 0; t < HST_CT; ++t) Wf[t] = __builtin_bit_cast(h16x8, A.packed[t * 64 + lane]);
     const float* shp = reinterpret_cast<const float*>(A.packed + HST_CT * 64);
-    f32x4 sh[HST_CT];                                               // shift of the lane's channels: pair tp, tile m: 32 tp + 8 kq + 4 m ..
+    otp_f32x4 sh[HST_CT];                                               // shift of the lane's channels: pair tp, tile m: 32 tp + 8 kq + 4 m ..
 #pragma unroll
-    for (int t = 0; t < HST_CT; ++t) sh[t] = *reinterpret_cast<const f32x4*>(shp + 32 * (t >> 1) + 8 * kq + 4 * (t & 1));
+    for (int t = 0; t < HST_CT; ++t) sh[t] = *reinterpret_cast<const otp_f32x4*>(shp + 32 * (t >> 1) + 8 * kq + 4 * (t & 1));
     const float post = reinterpret_cast<const float*>(A.packed + HST_CT * 64 + 16)[0];
     const size_t clip = (size_t)3 * A.F * A.H * A.W;
     const otp_rsrc rin = make_rsrc(A.in, (size_t)A.B * clip * sizeof(float));
@@ -1062,7 +1018,7 @@ __global__ __launch_bounds__(256) void h16_stem_kernel(HSt A) {
         const bool pv = px < A.total;
         if (!pv) px = A.total - 1;
         const int n = px / A.HoWo, pi = px - n * A.HoWo;                         // (exact division: px * HoWo passes 2^32 at cfg2)
-        const int yo = (int)hdiv((uint32_t)pi, A.mWo), xo = pi - yo * A.Wo;
+        const int yo = (int)otp_magic_div((uint32_t)pi, A.mWo), xo = pi - yo * A.Wo;
         const int b = n % A.B, f = n / A.B;                                   // frame n = f B + b (model/OTPose.py:317)
         const int base = (b * 3 * A.F + 3 * f) * A.H * A.W;
         float v[8];
@@ -1076,7 +1032,7 @@ __global__ __launch_bounds__(256) void h16_stem_kernel(HSt A) {
         const h16x8 bx = __builtin_bit_cast(h16x8, hpack8(v));
 #pragma unroll
         for (int tp = 0; tp < HST_CT / 2; ++tp) {
-            f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+            otp_f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
             a0 = H_MFMA(Wf[2 * tp], bx, a0, 0, 0, 0);
             a1 = H_MFMA(Wf[2 * tp + 1], bx, a1, 0, 0, 0);
             float o[8];
@@ -1101,7 +1057,7 @@ __global__ __launch_bounds__(256) void h16_stem_kernel(HSt A) {
 // element-wise passes on H8 images
 // ================================================================================================================================
 // fp32 NCHW channel slice -> H8 (one rounding); a thread owns one pixel of one 8-channel group (1 KB store runs per wave)
-__global__ __launch_bounds__(256) void h8_pack_kernel(const float* __restrict__ in, u32x4* __restrict__ out, int N, int C, int HW,
+__global__ __launch_bounds__(256) void h8_pack_kernel(const float* __restrict__ in, otp_u32x4* __restrict__ out, int N, int C, int HW,
                                                        int ctot, int coff, int gtot, int goff, unsigned* rflag) {
     const int G8 = C >> 3;
     const size_t items = (size_t)N * G8 * HW;
@@ -1121,7 +1077,7 @@ __global__ __launch_bounds__(256) void h8_pack_kernel(const float* __restrict__ 
     otp_range_report(rflag, bad, OTP_RANGE_H16);
 }
 
-__global__ __launch_bounds__(256) void h8_unpack_kernel(const u32x4* __restrict__ in, float* __restrict__ out, int N, int C, int HW,
+__global__ __launch_bounds__(256) void h8_unpack_kernel(const otp_u32x4* __restrict__ in, float* __restrict__ out, int N, int C, int HW,
                                                          int gtot, int goff) {
     const int G8 = C >> 3;
     const size_t items = (size_t)N * G8 * HW;
@@ -1129,10 +1085,10 @@ __global__ __launch_bounds__(256) void h8_unpack_kernel(const u32x4* __restrict_
         const int p = (int)(i % HW);
         const size_t r = i / HW;
         const int g = (int)(r % G8), n = (int)(r / G8);
-        const u32x4 v = in[((size_t)n * gtot + goff + g) * HW + p];
+        const otp_u32x4 v = in[((size_t)n * gtot + goff + g) * HW + p];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const f32x2 a = hwiden(v[e]);
+            const otp_f32x2 a = hwiden(v[e]);
             out[((size_t)n * C + 8 * g + 2 * e) * HW + p] = a.x;
             out[((size_t)n * C + 8 * g + 2 * e + 1) * HW + p] = a.y;
         }
@@ -1142,11 +1098,11 @@ __global__ __launch_bounds__(256) void h8_unpack_kernel(const u32x4* __restrict_
 // a fuse row's tail (model/HRNet.py:487-494): out = act(res + up_f0(low0) + up_f1(low1) + ...), nearest up-sampling, all H8; the
 // terms are added in fp32 in that order and rounded once
 struct H8Up {
-    const u32x4* low[3];
+    const otp_u32x4* low[3];
     int f[3];
     int n;
 };
-__global__ __launch_bounds__(256) void h8_upsample_add_kernel(H8Up U, const u32x4* __restrict__ res, u32x4* __restrict__ out, int N,
+__global__ __launch_bounds__(256) void h8_upsample_add_kernel(H8Up U, const otp_u32x4* __restrict__ res, otp_u32x4* __restrict__ out, int N,
                                                                int G8, int Hh, int Wh, int relu, unsigned* rflag) {
     const int HW = Hh * Wh;
     const size_t items = (size_t)N * G8 * HW;
@@ -1155,11 +1111,11 @@ __global__ __launch_bounds__(256) void h8_upsample_add_kernel(H8Up U, const u32x
         const int p = (int)(i % HW);
         const size_t r = i / HW;                                    // (n, g) plane
         const int y = p / Wh, x = p - y * Wh;
-        const u32x4 rv = res[i];
+        const otp_u32x4 rv = res[i];
         float f[8];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const f32x2 a = hwiden(rv[e]);
+            const otp_f32x2 a = hwiden(rv[e]);
             f[2 * e] = a.x;
             f[2 * e + 1] = a.y;
         }
@@ -1167,10 +1123,10 @@ __global__ __launch_bounds__(256) void h8_upsample_add_kernel(H8Up U, const u32x
         for (int k = 0; k < 3; ++k) {
             if (k < U.n) {
                 const int fk = U.f[k], Wl = Wh / fk, Hl = Hh / fk;
-                const u32x4 lv = U.low[k][r * (size_t)(Hl * Wl) + (y / fk) * Wl + x / fk];
+                const otp_u32x4 lv = U.low[k][r * (size_t)(Hl * Wl) + (y / fk) * Wl + x / fk];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const f32x2 a = hwiden(lv[e]);
+                    const otp_f32x2 a = hwiden(lv[e]);
                     f[2 * e] += a.x;
                     f[2 * e + 1] += a.y;
                 }
@@ -1208,7 +1164,7 @@ extern "C" int otp_h8_pack(const void* in, void* out, int N, int C, int H, int W
     const size_t items = (size_t)N * (C / 8) * (H * W);
     const int grid = (int)((items + 255) / 256 > 16384 ? 16384 : (items + 255) / 256);
     hipLaunchKernelGGL(h8_pack_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const float*>(in),
-                       static_cast<u32x4*>(out), N, C, H * W, in_ctot, in_coff, out_gtot, out_goff, otp_range_word());
+                       static_cast<otp_u32x4*>(out), N, C, H * W, in_ctot, in_coff, out_gtot, out_goff, otp_range_word());
     return otp_launch_status();
 }
 
@@ -1219,7 +1175,7 @@ extern "C" int otp_h8_unpack(const void* in, void* out, int N, int C, int H, int
     if (in_goff < 0 || in_goff + C / 8 > in_gtot) return OTP_ERR_BAD_ARG;
     const size_t items = (size_t)N * (C / 8) * (H * W);
     const int grid = (int)((items + 255) / 256 > 16384 ? 16384 : (items + 255) / 256);
-    hipLaunchKernelGGL(h8_unpack_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const u32x4*>(in),
+    hipLaunchKernelGGL(h8_unpack_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const otp_u32x4*>(in),
                        static_cast<float*>(out), N, C, H * W, in_gtot, in_goff);
     return otp_launch_status();
 }
@@ -1235,14 +1191,14 @@ extern "C" int otp_h16_upsample_add(const void* const* lows, const int* factors,
         if (!lows[k]) return OTP_ERR_BAD_ARG;
         if (f < 2 || (f & (f - 1)) || Hh % f || Wh % f) return OTP_ERR_UNSUPPORTED;
         if (reinterpret_cast<uintptr_t>(lows[k]) & 15) return OTP_ERR_UNSUPPORTED;
-        U.low[k] = static_cast<const u32x4*>(lows[k]);
+        U.low[k] = static_cast<const otp_u32x4*>(lows[k]);
         U.f[k] = f;
     }
     if ((reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(out)) & 15) return OTP_ERR_UNSUPPORTED;
     const size_t items = (size_t)N * (C / 8) * (Hh * Wh);
     const int grid = (int)((items + 255) / 256 > 16384 ? 16384 : (items + 255) / 256);
     hipLaunchKernelGGL(h8_upsample_add_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), U,
-                       static_cast<const u32x4*>(res), static_cast<u32x4*>(out), N, C / 8, Hh, Wh, relu, otp_range_word());
+                       static_cast<const otp_u32x4*>(res), static_cast<otp_u32x4*>(out), N, C / 8, Hh, Wh, relu, otp_range_word());
     return otp_launch_status();
 }
 
@@ -1263,10 +1219,10 @@ extern "C" int otp_h16_conv3x3_pack_weight(const void* weight, const void* scale
     if (!weight || !wpacked || Cout <= 0 || Cin <= 0 || !(pre > 0.f)) return OTP_ERR_BAD_ARG;
     if (!otp_h16_conv3x3_weight_bytes(Cout, Cin)) return OTP_ERR_UNSUPPORTED;
     const int NTW = h16_ntw(Cout), nN = ((Cout + 15) / 16 + NTW - 1) / NTW, nChunks = Cin / 16;
-    const int total = nN * nChunks * HKS * NTW * 64;
+    const int total = nN * nChunks * OTP_S8_KS * NTW * 64;
     hipLaunchKernelGGL(h16_wpack_kernel, dim3(otp_ceil_div(total, 256) > 2048 ? 2048 : otp_ceil_div(total, 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), static_cast<const float*>(weight), static_cast<const float*>(scale),
-                       static_cast<u32x4*>(wpacked), Cout, Cin, NTW, nN, nChunks, pre);
+                       static_cast<otp_u32x4*>(wpacked), Cout, Cin, NTW, nN, nChunks, pre);
     return otp_launch_status();
 }
 
@@ -1360,7 +1316,7 @@ extern "C" int otp_h16_stem_pack(const void* w, const void* scale, const void* s
     if (!otp_h16_stem_weight_bytes(Cout)) return OTP_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(h16_stem_pack_kernel, dim3(otp_ceil_div(HST_CT * 64 + 17, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const float*>(w), static_cast<const float*>(scale), static_cast<const float*>(shift),
-                       static_cast<u32x4*>(packed), Cout);
+                       static_cast<otp_u32x4*>(packed), Cout);
     return otp_launch_status();
 }
 
@@ -1372,11 +1328,11 @@ extern "C" int otp_h16_stem(const void* in, const void* packed, void* out_h8, in
         return OTP_ERR_BAD_ARG;
     HSt a{};
     a.in = static_cast<const float*>(in);
-    a.packed = static_cast<const u32x4*>(packed);
-    a.out = static_cast<u32x4*>(out_h8);
+    a.packed = static_cast<const otp_u32x4*>(packed);
+    a.out = static_cast<otp_u32x4*>(out_h8);
     a.B = B, a.F = F, a.H = H, a.W = W, a.Ho = (H - 1) / 2 + 1, a.Wo = (W - 1) / 2 + 1, a.HoWo = a.Ho * a.Wo, a.Cout = Cout;
     a.total = B * F * a.HoWo;
-    a.mWo = hmagic((uint32_t)a.Wo);
+    a.mWo = otp_magic((uint32_t)a.Wo);
     a.rflag = otp_range_word();
     constexpr int NPT = 4;
     hipLaunchKernelGGL(h16_stem_kernel<NPT>, dim3((unsigned)((a.total + 64 * NPT - 1) / (64 * NPT))), dim3(256), 0,

@@ -2,22 +2,12 @@
 // weight-stream kernel of the fp16 engine.  Internal interface between csrc/nhwc.hip (which owns the C ABI: otp_nhwc_conv_*)
 // and that translation unit, plus the layout of the packed weights both sides must agree on.
 #pragma once
-#include "common.h"
+#include "x3.h"
 
-constexpr int OTP_HB_KS = 5;              // k-steps per 16-channel chunk: 18 (tap, channel group) slots of 8 channels in 5 x 4 (2 empty)
+// (k-steps per chunk OTP_S8_KS, the tile-pair row order otp_tile_paired / otp_row2ch: csrc/x3.h, shared with the S8 kernels)
 // packed weights of a (cout block, 16-channel chunk): 4 full k-steps x NTW tiles x 1 KB, then the half-filled fifth (k-slots 16, 17
 // on lanes 0 .. 31: 512 bytes per tile)
 __host__ __device__ constexpr int otp_hb_wb(int ntw) { return ntw * 4608; }
-// Output-channel row of an MFMA tile <-> channel: cout tiles go in pairs (2 tp, 2 tp + 1) whose rows are permuted so that lane
-// (pixel, kl) ends up with 8 CONSECUTIVE channels 32 tp + 8 kl .. + 7 of its pixel = one 16-byte record; a tile without a partner
-// keeps the identity (4 consecutive channels per lane = half a record).
-__host__ __device__ inline bool otp_hb_paired(int co_blk, int t, int ntw, int Cout) {
-    const int tb = t | 1;
-    return tb < ntw && co_blk + 16 * tb < Cout;
-}
-__host__ __device__ inline int otp_hb_row2ch(int co_blk, int t, int row, int ntw, int Cout) {
-    return otp_hb_paired(co_blk, t, ntw, Cout) ? co_blk + 32 * (t >> 1) + 8 * (row >> 2) + 4 * (t & 1) + (row & 3) : co_blk + 16 * t + row;
-}
 inline int otp_hb_ntw(int Cout) {
     const int c16 = (Cout + 15) / 16;
     return (c16 % 3 == 0) ? 3 : (c16 % 2 == 0 || c16 <= 2 ? 2 : 3);
@@ -25,12 +15,12 @@ inline int otp_hb_ntw(int Cout) {
 // 16-byte unit u of a (cout block, chunk) image -> (k-step, tile, lane); lane = (row i16 = lane & 15, k-group kl = lane >> 4),
 // k-slot q = 4 s + kl: tap q / 2, input channels 16 chunk + 8 (q % 2) .. + 7
 __host__ __device__ inline void otp_hb_unit(int u, int ntw, int* s, int* t, int* lane) {
-    const int full = (OTP_HB_KS - 1) * ntw * 64;
+    const int full = (OTP_S8_KS - 1) * ntw * 64;
     if (u < full) {
         *s = u / (ntw * 64), *t = (u >> 6) % ntw, *lane = u & 63;
     } else {
         u -= full;
-        *s = OTP_HB_KS - 1, *t = u >> 5, *lane = u & 31;
+        *s = OTP_S8_KS - 1, *t = u >> 5, *lane = u & 31;
     }
 }
 

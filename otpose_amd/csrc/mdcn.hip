@@ -242,12 +242,11 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void mdcn_fwd_kernel(
                                                          (float)(win[v] + j * g.dil) + cur[3 * j + 1][v], g) *
                                       cur[3 * j + 2][v];
                     // packed f32 FMAs (v_pk_fma_f32): two output channels per instruction
-                    typedef float f32x2 __attribute__((ext_vector_type(2)));
-                    const f32x2 col2 = {col, col};
+                    const otp_f32x2 col2 = {col, col};
 #pragma unroll
                     for (int o = 0; o + 1 < CO_T; o += 2) {
-                        f32x2 a2 = {acc[v][o], acc[v][o + 1]};
-                        const f32x2 w2 = {wr[o], wr[o + 1]};
+                        otp_f32x2 a2 = {acc[v][o], acc[v][o + 1]};
+                        const otp_f32x2 w2 = {wr[o], wr[o + 1]};
                         a2 = __builtin_elementwise_fma(w2, col2, a2);
                         acc[v][o] = a2.x;
                         acc[v][o + 1] = a2.y;

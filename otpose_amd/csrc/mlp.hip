@@ -20,42 +20,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// erf-GELU on a pair of accumulator values, branch-free and in packed-f32 form (v_pk_fma_f32): erf(t) = t P(t^2) / Q(t^2)
-// on |t| <= 4 (the classic single-precision rational fit; erf is 1 - 1.5e-8 beyond), max abs error 4.2e-7 on erf and
-// 7e-7 on gelu(x) over the whole real line - checked against fp64 in tests/test_gpu_ops.py.  The libm erff the other
-// epilogues call has two data-dependent paths, and both would run for every accumulator register of a wave here.
-__device__ __forceinline__ f32x2 mlp_gelu2(f32x2 x) {
-    f32x2 t = x * 0.70710678118654752440f;
-    t.x = __builtin_amdgcn_fmed3f(t.x, -4.f, 4.f);
-    t.y = __builtin_amdgcn_fmed3f(t.y, -4.f, 4.f);
-    const f32x2 t2 = t * t;
-    f32x2 p = t2 * -2.72614225801306e-10f + 2.77068142495902e-08f;
-    p = p * t2 + -2.10102402082508e-06f;
-    p = p * t2 + -5.69250639462346e-05f;
-    p = p * t2 + -7.34990630326855e-04f;
-    p = p * t2 + -2.95459980854025e-03f;
-    p = p * t2 + -1.60960333262415e-02f;
-    p = p * t;
-    f32x2 q = t2 * -1.45660718464996e-05f + -2.13374055278905e-04f;
-    q = q * t2 + -1.68282697438203e-03f;
-    q = q * t2 + -7.37332916720468e-03f;
-    q = q * t2 + -1.42647390514189e-02f;
-    f32x2 r;
-    r.x = __builtin_amdgcn_rcpf(q.x);
-    r.y = __builtin_amdgcn_rcpf(q.y);
-    const f32x2 e = p * r, hx = x * 0.5f;
-    return hx * e + hx;
-}
-
-__device__ __forceinline__ float kslot_sum(float v) {      // sum over the four k-slot lane groups (lanes n, n+16, n+32, n+48)
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
 // floats per hidden block (a multiple of 4: the block is copied as 16-byte pieces)
 constexpr int mlp_block_floats(int C) { return ((C / 4 + 3) / 4 + (C + 15) / 16) * 256 + 16; }
 
@@ -96,8 +60,8 @@ __device__ __forceinline__ void mlp_pass(const float* __restrict__ x, const floa
     const bool valid = tok < T;                       // NT == 2: T is even, a token pair is inside or outside together
 
     // weights of hidden block 0 -> LDS buffer 0 (every wave is past the previous pass: the barrier that ended its loop)
-    const f32x4* pk = reinterpret_cast<const f32x4*>(packed);
-    f32x4* l4 = reinterpret_cast<f32x4*>(lds);
+    const otp_f32x4* pk = reinterpret_cast<const otp_f32x4*>(packed);
+    otp_f32x4* l4 = reinterpret_cast<otp_f32x4*>(lds);
 #pragma unroll
     for (int i = 0; i < NST; ++i)
         if (BLK4 % NTHR == 0 || tid + i * NTHR < BLK4) l4[tid + i * NTHR] = pk[tid + i * NTHR];
@@ -108,7 +72,7 @@ __device__ __forceinline__ void mlp_pass(const float* __restrict__ x, const floa
     for (int s = 0; s < KS; ++s) {     // columns past T read the last ones instead (their results are never stored)
         const float* src = x + base + (size_t)(4 * s + kq) * T + (valid ? tok : T - NT);
         if (NT == 2) {
-            const f32x2 v = *reinterpret_cast<const f32x2*>(src);
+            const otp_f32x2 v = *reinterpret_cast<const otp_f32x2*>(src);
             X[s][0] = v.x;
             X[s][NT - 1] = v.y;
         } else {
@@ -122,30 +86,30 @@ __device__ __forceinline__ void mlp_pass(const float* __restrict__ x, const floa
             float s0 = 0.f;
 #pragma unroll
             for (int s = 0; s < KS; ++s) s0 += X[s][j];
-            const float m0 = kslot_sum(s0) * inv_c;
+            const float m0 = otp_kslot_sum(s0) * inv_c;
             float v0 = 0.f;
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 X[s][j] -= m0;
                 v0 += X[s][j] * X[s][j];
             }
-            const float r0 = 1.f / sqrtf(kslot_sum(v0) * inv_c + ln_eps);
+            const float r0 = 1.f / sqrtf(otp_kslot_sum(v0) * inv_c + ln_eps);
 #pragma unroll
             for (int s = 0; s < KS; ++s) X[s][j] = X[s][j] * r0 * ln_gamma[4 * s + kq] + ln_beta[4 * s + kq];
         }
     }
-    f32x4 Y[MT][NT];
+    otp_f32x4 Y[MT][NT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int j = 0; j < NT; ++j) Y[mt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < NT; ++j) Y[mt][j] = otp_f32x4{0.f, 0.f, 0.f, 0.f};
     __syncthreads();
 
     for (int h = 0; h < HT; ++h) {
         // next block's weights on their way while this one is consumed
-        f32x4 stage[NST];
+        otp_f32x4 stage[NST];
         if (h + 1 < HT) {
-            const f32x4* src = pk + (size_t)(h + 1) * BLK4;
+            const otp_f32x4* src = pk + (size_t)(h + 1) * BLK4;
 #pragma unroll
             for (int i = 0; i < NST; ++i)
                 if (BLK4 % NTHR == 0 || tid + i * NTHR < BLK4) stage[i] = src[tid + i * NTHR];
@@ -155,12 +119,12 @@ __device__ __forceinline__ void mlp_pass(const float* __restrict__ x, const floa
         const float* PB = P2 + MT * 256;
         // phase 1: hidden tile (16 channels x 16 NT tokens) = W1[16h .. 16h+15][:] . X
         // (the accumulators start from b1: register i of lane group kq is hidden channel 16h + 4 kq + i)
-        f32x4 H[NT];
+        otp_f32x4 H[NT];
 #pragma unroll
-        for (int j = 0; j < NT; ++j) H[j] = *reinterpret_cast<const f32x4*>(PB + 4 * kq);
+        for (int j = 0; j < NT; ++j) H[j] = *reinterpret_cast<const otp_f32x4*>(PB + 4 * kq);
 #pragma unroll
         for (int sg = 0; sg < KG; ++sg) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(P1 + (sg * 64 + lane) * 4);
+            const otp_f32x4 a = *reinterpret_cast<const otp_f32x4*>(P1 + (sg * 64 + lane) * 4);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int s = 4 * sg + q;
@@ -172,20 +136,20 @@ __device__ __forceinline__ void mlp_pass(const float* __restrict__ x, const floa
         }
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            const f32x2 g0 = mlp_gelu2(f32x2{H[j][0], H[j][1]}), g1 = mlp_gelu2(f32x2{H[j][2], H[j][3]});
-            H[j] = f32x4{g0.x, g0.y, g1.x, g1.y};
+            const otp_f32x2 g0 = otp_gelu2(otp_f32x2{H[j][0], H[j][1]}), g1 = otp_gelu2(otp_f32x2{H[j][2], H[j][3]});
+            H[j] = otp_f32x4{g0.x, g0.y, g1.x, g1.y};
         }
         // phase 2: Y += W2[:, 16h .. 16h+15] . hidden tile, contraction step i over the hidden channels {4g + i}
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(P2 + (mt * 64 + lane) * 4);
+            const otp_f32x4 a = *reinterpret_cast<const otp_f32x4*>(P2 + (mt * 64 + lane) * 4);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < NT; ++j) Y[mt][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], H[j][i], Y[mt][j], 0, 0, 0);
         }
         if (h + 1 < HT) {
-            f32x4* dst = reinterpret_cast<f32x4*>(lds + ((h + 1) & 1) * BLK);
+            otp_f32x4* dst = reinterpret_cast<otp_f32x4*>(lds + ((h + 1) & 1) * BLK);
 #pragma unroll
             for (int i = 0; i < NST; ++i)
                 if (BLK4 % NTHR == 0 || tid + i * NTHR < BLK4) dst[tid + i * NTHR] = stage[i];
@@ -203,11 +167,11 @@ __device__ __forceinline__ void mlp_pass(const float* __restrict__ x, const floa
                 const size_t o = base + (size_t)c * T + tok;
                 const float sc = scale[c], sh = shift[c];
                 if (NT == 2) {
-                    const f32x2 r = *reinterpret_cast<const f32x2*>(res + o);
-                    f32x2 v;
+                    const otp_f32x2 r = *reinterpret_cast<const otp_f32x2*>(res + o);
+                    otp_f32x2 v;
                     v.x = r.x + Y[mt][0][i] * sc + sh;
                     v.y = r.y + Y[mt][NT - 1][i] * sc + sh;
-                    *reinterpret_cast<f32x2*>(out + o) = v;
+                    *reinterpret_cast<otp_f32x2*>(out + o) = v;
                 } else {
                     out[o] = res[o] + Y[mt][0][i] * sc + sh;
                 }

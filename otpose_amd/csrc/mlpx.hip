@@ -16,43 +16,13 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "x3.h"
 
 namespace {
 
-typedef otp_x3x8 h16x8;              // 8 operand pieces of the split products (common.h: IEEE half since round 4)
-typedef otp_x3x2 h16x2;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// erf-GELU on a pair of values, branch-free, packed f32 (the rational fit of csrc/mlp.hip: 7e-7 max abs error)
-__device__ __forceinline__ f32x2 mx_gelu2(f32x2 x) {
-    f32x2 t = x * 0.70710678118654752440f;
-    t.x = __builtin_amdgcn_fmed3f(t.x, -4.f, 4.f);
-    t.y = __builtin_amdgcn_fmed3f(t.y, -4.f, 4.f);
-    const f32x2 t2 = t * t;
-    f32x2 p = t2 * -2.72614225801306e-10f + 2.77068142495902e-08f;
-    p = p * t2 + -2.10102402082508e-06f;
-    p = p * t2 + -5.69250639462346e-05f;
-    p = p * t2 + -7.34990630326855e-04f;
-    p = p * t2 + -2.95459980854025e-03f;
-    p = p * t2 + -1.60960333262415e-02f;
-    p = p * t;
-    f32x2 q = t2 * -1.45660718464996e-05f + -2.13374055278905e-04f;
-    q = q * t2 + -1.68282697438203e-03f;
-    q = q * t2 + -7.37332916720468e-03f;
-    q = q * t2 + -1.42647390514189e-02f;
-    f32x2 r;
-    r.x = __builtin_amdgcn_rcpf(q.x);
-    r.y = __builtin_amdgcn_rcpf(q.y);
-    const f32x2 e = p * r, hx = x * 0.5f;
-    return hx * e + hx;
-}
-
 // erf-GELU for the HALF-operand form (H1 below): the result is rounded to half (2^-11 relative) on its way into the second GEMM,
 // so 6e-5 absolute is enough: x * (0.5 + xc R(xc^2)), xc = clamp(x, +-4.2), R = a degree-8 fit of erf(sqrt(s / 2)) / (2 sqrt(s)) -
-// 12 plain vector instructions, no reciprocal (the fp32 form above: 18 + v_rcp_f32)
+// 12 plain vector instructions, no reciprocal (the fp32 form, common.h: otp_gelu2: 18 + v_rcp_f32)
 __device__ __forceinline__ float mx_gelu_h(float x) {
     const float xc = __builtin_amdgcn_fmed3f(x, -4.2f, 4.2f), s2 = xc * xc;
     float r = 4.711542158e-11f;
@@ -67,32 +37,12 @@ __device__ __forceinline__ float mx_gelu_h(float x) {
     return x * (xc * r + 0.5f);
 }
 
-__device__ __forceinline__ float mx_kslot_sum(float v) {   // sum over the four k-slot lane groups (lanes n, n+16, n+32, n+48)
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
-// 8 floats -> bf16 hi / lo vectors (hi = rne(a), lo = rne(a - hi))
-__device__ __forceinline__ void mx_split8(const float (&v)[8], h16x8& hi, h16x8& lo) {
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x2 a = {v[2 * i], v[2 * i + 1]};
-        const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, h16x2));
-        const f32x2 af = otp_x3_widen(hb);
-        h[i] = hb;
-        l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a - af, h16x2));
-    }
-    hi = __builtin_bit_cast(h16x8, (u32x4){h[0], h[1], h[2], h[3]});
-    lo = __builtin_bit_cast(h16x8, (u32x4){l[0], l[1], l[2], l[3]});
-}
 // 8 floats -> halves, rounded once (the fp16 engine's operands)
-__device__ __forceinline__ h16x8 mx_half8(const float (&v)[8]) {
+__device__ __forceinline__ otp_x3x8 mx_half8(const float (&v)[8]) {
     uint32_t h[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) h[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v[2 * i], v[2 * i + 1]}, h16x2));
-    return __builtin_bit_cast(h16x8, (u32x4){h[0], h[1], h[2], h[3]});
+    for (int i = 0; i < 4; ++i) h[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector((otp_f32x2){v[2 * i], v[2 * i + 1]}, otp_x3x2));
+    return __builtin_bit_cast(otp_x3x8, (otp_u32x4){h[0], h[1], h[2], h[3]});
 }
 
 constexpr int mx_ks1(int C) { return (C + 31) / 32; }
@@ -112,7 +62,7 @@ __global__ void mlpx_pack_kernel(const float* __restrict__ w1, const float* __re
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= ((HID + 31) / 32) * units) return;                  // (a ragged last block - HID = 816 - is padded with zero weights)
     const int hb = idx / units, u = idx - hb * units;
-    u32x4 o = {0u, 0u, 0u, 0u};
+    otp_u32x4 o = {0u, 0u, 0u, 0u};
     float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (u < (W1B + W2B) / 16) {
         const int frag = u >> 6, lane = u & 63, row = lane & 15, kq = lane >> 4;
@@ -133,31 +83,17 @@ __global__ void mlpx_pack_kernel(const float* __restrict__ w1, const float* __re
                 if (c < C && hid < HID) v[j] = w2[(size_t)c * HID + hid];
             }
         }
-        h16x8 hi, lo;
-        mx_split8(v, hi, lo);
-        o = __builtin_bit_cast(u32x4, lo_part ? lo : hi);
+        otp_x3x8 hi, lo;
+        otp_x3_split8(v, hi, lo);
+        o = __builtin_bit_cast(otp_u32x4, lo_part ? lo : hi);
     } else if (u < (W1B + W2B) / 16 + 8) {
         const int k = (u - (W1B + W2B) / 16) * 4;
         const bool in = 32 * hb + k < HID;                         // (HID % 4 == 0)
-        o = in ? (u32x4){__builtin_bit_cast(uint32_t, b1[32 * hb + k]), __builtin_bit_cast(uint32_t, b1[32 * hb + k + 1]),
+        o = in ? (otp_u32x4){__builtin_bit_cast(uint32_t, b1[32 * hb + k]), __builtin_bit_cast(uint32_t, b1[32 * hb + k + 1]),
                          __builtin_bit_cast(uint32_t, b1[32 * hb + k + 2]), __builtin_bit_cast(uint32_t, b1[32 * hb + k + 3])}
-               : (u32x4){0u, 0u, 0u, 0u};
+               : (otp_u32x4){0u, 0u, 0u, 0u};
     }
-    reinterpret_cast<u32x4*>(packed)[idx] = o;
-}
-
-// copy one weight block global -> LDS with the LDS-DMA: unit u (16 bytes) of the block lands at lds + 16 u
-template <int NTHR, int BLKB>
-__device__ __forceinline__ void mx_stage(const unsigned char* __restrict__ src, unsigned char* lds) {
-    constexpr int NST = (BLKB / 16 + NTHR - 1) / NTHR;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-#pragma unroll
-    for (int i = 0; i < NST; ++i) {
-        const int u0 = i * NTHR + wave * 64;                       // wave-uniform first unit of this wave-instruction
-        if (u0 * 16 >= BLKB) break;                                // (whole KB: a wave-instruction is inside the block or past it)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)(u0 + lane) * 16),
-                                         (__attribute__((address_space(3))) void*)(lds + u0 * 16), 16, 0, 0);
-    }
+    reinterpret_cast<otp_u32x4*>(packed)[idx] = o;
 }
 
 // One pass of a wave over NT (1 or 2) column tiles of 16 tokens starting at token tok0, all HID / 32 hidden blocks; every wave
@@ -178,7 +114,7 @@ __device__ __forceinline__ void mlpx_pass(const float* __restrict__ x, const uns
     const bool valid = tok < T;                       // NT == 2: T is even, a token pair is inside or outside together
 
     // weights of hidden block 0 -> LDS buffer 0 (every wave is past the previous pass: the barrier that ended its loop)
-    mx_stage<NTHR, BLKB>(packed, lds);
+    otp_lds_stage<NTHR, BLKB>(packed, lds);
 
     // the wave's input columns: X[ks][j][t] = x[32 ks + 8 kq + j][token of column n of tile t] (0 past C)
     float X[KS1][8][NT];
@@ -190,7 +126,7 @@ __device__ __forceinline__ void mlpx_pass(const float* __restrict__ x, const uns
             const bool live = 32 * ks + 24 + j < C || c < C;       // compile-time true except in the last k-step
             const float* src = x + base + (size_t)(live ? c : 0) * T + (valid ? tok : T - NT);
             if (NT == 2) {
-                const f32x2 v = *reinterpret_cast<const f32x2*>(src);
+                const otp_f32x2 v = *reinterpret_cast<const otp_f32x2*>(src);
                 X[ks][j][0] = live ? v.x : 0.f;
                 X[ks][j][NT - 1] = live ? v.y : 0.f;
             } else {
@@ -206,7 +142,7 @@ __device__ __forceinline__ void mlpx_pass(const float* __restrict__ x, const uns
             for (int ks = 0; ks < KS1; ++ks)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) s0 += X[ks][j][t];
-            const float m0 = mx_kslot_sum(s0) * inv_c;
+            const float m0 = otp_kslot_sum(s0) * inv_c;
             float v0 = 0.f;
 #pragma unroll
             for (int ks = 0; ks < KS1; ++ks)
@@ -216,7 +152,7 @@ __device__ __forceinline__ void mlpx_pass(const float* __restrict__ x, const uns
                     X[ks][j][t] = live ? X[ks][j][t] - m0 : 0.f;
                     v0 += X[ks][j][t] * X[ks][j][t];
                 }
-            const float r0 = 1.f / sqrtf(mx_kslot_sum(v0) * inv_c + ln_eps);
+            const float r0 = 1.f / sqrtf(otp_kslot_sum(v0) * inv_c + ln_eps);
 #pragma unroll
             for (int ks = 0; ks < KS1; ++ks)
 #pragma unroll
@@ -227,7 +163,7 @@ __device__ __forceinline__ void mlpx_pass(const float* __restrict__ x, const uns
                 }
         }
     }
-    h16x8 Xh[KS1][NT], Xl[H1 ? 1 : KS1][NT];
+    otp_x3x8 Xh[KS1][NT], Xl[H1 ? 1 : KS1][NT];
 #pragma unroll
     for (int ks = 0; ks < KS1; ++ks)
 #pragma unroll
@@ -236,35 +172,35 @@ __device__ __forceinline__ void mlpx_pass(const float* __restrict__ x, const uns
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = X[ks][j][t];
             if constexpr (H1) Xh[ks][t] = mx_half8(v);
-            else mx_split8(v, Xh[ks][t], Xl[H1 ? 0 : ks][t]);
+            else otp_x3_split8(v, Xh[ks][t], Xl[H1 ? 0 : ks][t]);
         }
-    f32x4 Y[MT][NT];
+    otp_f32x4 Y[MT][NT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int t = 0; t < NT; ++t) Y[mt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < NT; ++t) Y[mt][t] = otp_f32x4{0.f, 0.f, 0.f, 0.f};
     __syncthreads();                                  // (drains the LDS-DMA of block 0)
 
     for (int hb = 0; hb < HB; ++hb) {
         // next block's weights on their way (LDS-DMA into the other buffer) while this one is consumed
-        if (hb + 1 < HB) mx_stage<NTHR, BLKB>(packed + (size_t)(hb + 1) * BLKB, lds + ((hb + 1) & 1) * BLKB);
+        if (hb + 1 < HB) otp_lds_stage<NTHR, BLKB>(packed + (size_t)(hb + 1) * BLKB, lds + ((hb + 1) & 1) * BLKB);
         const unsigned char* P1 = lds + (hb & 1) * BLKB + lane * 16;
         const unsigned char* P2 = P1 + W1B;
         const float* PB = reinterpret_cast<const float*>(lds + (hb & 1) * BLKB + W1B + W2B);
         // phase 1: two hidden tiles (16 channels x 16 NT tokens) = W1[32 hb + 16 tile ..][:] . X, accumulators start from b1
-        f32x4 H[2][NT];
+        otp_f32x4 H[2][NT];
 #pragma unroll
         for (int tile = 0; tile < 2; ++tile) {
 #pragma unroll
-            for (int t = 0; t < NT; ++t) H[tile][t] = *reinterpret_cast<const f32x4*>(PB + 16 * tile + 4 * kq);
+            for (int t = 0; t < NT; ++t) H[tile][t] = *reinterpret_cast<const otp_f32x4*>(PB + 16 * tile + 4 * kq);
 #pragma unroll
             for (int ks = 0; ks < KS1; ++ks) {
-                const h16x8 ah = *reinterpret_cast<const h16x8*>(P1 + ((tile * KS1 + ks) * PS) * 1024);
+                const otp_x3x8 ah = *reinterpret_cast<const otp_x3x8*>(P1 + ((tile * KS1 + ks) * PS) * 1024);
                 if constexpr (H1) {
 #pragma unroll
                     for (int t = 0; t < NT; ++t) H[tile][t] = OTP_X3_MFMA(ah, Xh[ks][t], H[tile][t], 0, 0, 0);
                 } else {
-                    const h16x8 al = *reinterpret_cast<const h16x8*>(P1 + ((tile * KS1 + ks) * 2 + 1) * 1024);
+                    const otp_x3x8 al = *reinterpret_cast<const otp_x3x8*>(P1 + ((tile * KS1 + ks) * 2 + 1) * 1024);
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
                         H[tile][t] = OTP_X3_MFMA(al, Xh[ks][t], H[tile][t], 0, 0, 0);
@@ -274,7 +210,7 @@ __device__ __forceinline__ void mlpx_pass(const float* __restrict__ x, const uns
                 }
             }
         }
-        h16x8 Gh[NT], Gl[NT];
+        otp_x3x8 Gh[NT], Gl[NT];
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             if constexpr (H1) {
@@ -282,21 +218,21 @@ __device__ __forceinline__ void mlpx_pass(const float* __restrict__ x, const uns
                                     mx_gelu_h(H[1][t][0]), mx_gelu_h(H[1][t][1]), mx_gelu_h(H[1][t][2]), mx_gelu_h(H[1][t][3])};
                 Gh[t] = mx_half8(v);
             } else {
-                const f32x2 g0 = mx_gelu2(f32x2{H[0][t][0], H[0][t][1]}), g1 = mx_gelu2(f32x2{H[0][t][2], H[0][t][3]});
-                const f32x2 g2 = mx_gelu2(f32x2{H[1][t][0], H[1][t][1]}), g3 = mx_gelu2(f32x2{H[1][t][2], H[1][t][3]});
+                const otp_f32x2 g0 = otp_gelu2(otp_f32x2{H[0][t][0], H[0][t][1]}), g1 = otp_gelu2(otp_f32x2{H[0][t][2], H[0][t][3]});
+                const otp_f32x2 g2 = otp_gelu2(otp_f32x2{H[1][t][0], H[1][t][1]}), g3 = otp_gelu2(otp_f32x2{H[1][t][2], H[1][t][3]});
                 const float v[8] = {g0.x, g0.y, g1.x, g1.y, g2.x, g2.y, g3.x, g3.y};
-                mx_split8(v, Gh[t], Gl[t]);
+                otp_x3_split8(v, Gh[t], Gl[t]);
             }
         }
         // phase 2: Y += W2[:, 32 hb ..] . hidden tiles (k-slot (kq, j) = hidden channel 4 kq + j / 16 + 4 kq + j - 4)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            const h16x8 ah = *reinterpret_cast<const h16x8*>(P2 + (mt * PS) * 1024);
+            const otp_x3x8 ah = *reinterpret_cast<const otp_x3x8*>(P2 + (mt * PS) * 1024);
             if constexpr (H1) {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) Y[mt][t] = OTP_X3_MFMA(ah, Gh[t], Y[mt][t], 0, 0, 0);
             } else {
-                const h16x8 al = *reinterpret_cast<const h16x8*>(P2 + (mt * 2 + 1) * 1024);
+                const otp_x3x8 al = *reinterpret_cast<const otp_x3x8*>(P2 + (mt * 2 + 1) * 1024);
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     Y[mt][t] = OTP_X3_MFMA(al, Gh[t], Y[mt][t], 0, 0, 0);
@@ -328,11 +264,11 @@ __device__ __forceinline__ void mlpx_pass(const float* __restrict__ x, const uns
                 const size_t o = base + (size_t)c * T + tok;
                 const float sc = scale[c], sh = shift[c];
                 if (NT == 2) {
-                    const f32x2 r = *reinterpret_cast<const f32x2*>(res + o);
-                    f32x2 v;
+                    const otp_f32x2 r = *reinterpret_cast<const otp_f32x2*>(res + o);
+                    otp_f32x2 v;
                     v.x = r.x + Y[mt][0][i] * sc + sh;
                     v.y = r.y + Y[mt][NT - 1][i] * sc + sh;
-                    *reinterpret_cast<f32x2*>(out + o) = v;
+                    *reinterpret_cast<otp_f32x2*>(out + o) = v;
                 } else {
                     out[o] = res[o] + Y[mt][0][i] * sc + sh;
                 }

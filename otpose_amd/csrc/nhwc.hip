@@ -25,9 +25,6 @@ namespace {
 typedef __bf16 bf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float bf2f(bf16 v) { return (float)v; }
 
@@ -46,8 +43,8 @@ __device__ unsigned long long otp_nhwc_stamps[8192 * 8];
 #else
 #define OTP_STAMP(slot)
 #endif
-__device__ __forceinline__ u32x4 bload16(otp_rsrc r, int voff_bytes) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff_bytes, 0, 0));
+__device__ __forceinline__ otp_u32x4 bload16(otp_rsrc r, int voff_bytes) {
+    return __builtin_bit_cast(otp_u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff_bytes, 0, 0));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -221,7 +218,7 @@ __device__ __forceinline__ float pack_hb_value(const float* __restrict__ w, cons
     const int chunk = (int)(r % jb.hbChunks), cb = (int)(r / jb.hbChunks);
     int s, t, lane;
     otp_hb_unit(u, jb.hbNTW, &s, &t, &lane);
-    const int o = otp_hb_row2ch(cb * jb.hbNTW * 16, t, lane & 15, jb.hbNTW, jb.p.Cout);
+    const int o = otp_row2ch(cb * jb.hbNTW * 16, t, lane & 15, jb.hbNTW, jb.p.Cout);
     const int q = 4 * s + (lane >> 4), tap = q >> 1, ci = chunk * 16 + 8 * (q & 1) + j;
     if (tap > 8 || o >= jb.p.Cout || ci >= jb.p.Cin) return 0.f;
     return w[jb.base + o * jb.so + ci * jb.si + (tap / 3) * jb.sdy + (tap % 3) * jb.sdx];
@@ -261,7 +258,7 @@ __device__ __forceinline__ void pack_unit(const PackJob& jb, size_t unit) {
         const int chunk = (int)(r % jb.hbChunks), cb = (int)(r / jb.hbChunks);
         int s_, t, lane;
         otp_hb_unit(u, jb.hbNTW, &s_, &t, &lane);
-        const int o = otp_hb_row2ch(cb * jb.hbNTW * 16, t, lane & 15, jb.hbNTW, jb.p.Cout);
+        const int o = otp_row2ch(cb * jb.hbNTW * 16, t, lane & 15, jb.hbNTW, jb.p.Cout);
         const int q = 4 * s_ + (lane >> 4), tap = q >> 1;
         ci0 = chunk * 16 + 8 * (q & 1);
         if (tap <= 8 && o < jb.p.Cout) off = jb.base + o * jb.so + (tap / 3) * jb.sdy + (tap % 3) * jb.sdx;
@@ -318,29 +315,13 @@ __global__ void nhwc_pack_batch_kernel(const PackJob* __restrict__ jobs) {
 // ---------------------------------------------------------------------------------------------------------------------
 // implicit-GEMM convolution
 // ---------------------------------------------------------------------------------------------------------------------
-// bias, rounding, store; per-tile channel sums of the ROUNDED values (what BatchNorm will normalise).  Contains one
-// workgroup barrier when statistics are requested.
-// sum over the 16 lanes of a DPP row (one MFMA pixel column group) with four VALU adds; every lane ends with the total.
-// (__shfl_xor with offsets 4 and 8 lowers to ds_bpermute on gfx950: 96 LDS round trips in the old epilogue)
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float row16_sum(float v) {
-    v += dpp_mov<0xB1>(v);        // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);        // quad_perm [2,3,0,1]
-    v += dpp_mov<0x124>(v);       // row_ror:4
-    v += dpp_mov<0x128>(v);       // row_ror:8
-    return v;
-}
-
 // bias, rounding, store; per-tile channel sums of the ROUNDED values (what BatchNorm will normalise).
 // NHWC output: the tile is transposed through LDS (smem is free once every wave has left the MFMA loop) so that it leaves as
 // 16-byte stores of whole pixel rows - the accumulator layout (4 channels x 1 pixel per lane) would otherwise issue MB*NB
 // 8-byte stores per lane in 32-byte runs, which is store-issue bound (10-16k cycles per workgroup, measured with
 // tools/nhwc_timing.py).  Contains workgroup barriers; every thread of the workgroup must call it.
 template <int MB, int NB>
-__device__ __forceinline__ void conv_epilogue(f32x4 (&acc)[MB][NB], const bool (&valid)[NB], const ConvPlan& p,
+__device__ __forceinline__ void conv_epilogue(otp_f32x4 (&acc)[MB][NB], const bool (&valid)[NB], const ConvPlan& p,
                                               const float* __restrict__ bias, const bf16* __restrict__ res,
                                               bf16* __restrict__ out, float* __restrict__ out_f32, float* __restrict__ stats,
                                               unsigned char* smem, float* sRed, int n, int tile, int mt, int p0, int npx) {
@@ -390,7 +371,7 @@ __device__ __forceinline__ void conv_epilogue(f32x4 (&acc)[MB][NB], const bool (
         if (stats) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float a = row16_sum(s1[r]), b = row16_sum(s2[r]);
+                const float a = otp_row16_sum(s1[r]), b = otp_row16_sum(s2[r]);
                 if (l15 == 0) {
                     sRed[(wave * 2 + 0) * BM + m * 16 + lg * 4 + r] = a;
                     sRed[(wave * 2 + 1) * BM + m * 16 + lg * 4 + r] = b;
@@ -473,11 +454,11 @@ __global__ __launch_bounds__(256) void nhwc_conv_kernel(const bf16* __restrict__
         const int oy = pc / p.Wo, ox = pc - oy * p.Wo;
         boff[nb] = (((oy - oy0) * p.stride) * p.RW + ox * p.stride) * p.CKp;
     }
-    f32x4 acc[MB][NB];
+    otp_f32x4 acc[MB][NB];
 #pragma unroll
     for (int m = 0; m < MB; ++m)
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) acc[m][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int nb = 0; nb < NB; ++nb) acc[m][nb] = otp_f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int wunits = p.ldsW / 16;
     const int rowUnits = p.RW * p.CK8;
@@ -497,7 +478,7 @@ __global__ __launch_bounds__(256) void nhwc_conv_kernel(const bf16* __restrict__
             const bool colIn = grp < G && ix >= 0 && ix < p.W;
             const int ldst = col * p.CKp + cgi * 8;
             const otp_rsrc wres = make_rsrc(wpk, p.wbytes);
-            u32x4 xv[8], wv[WU];
+            otp_u32x4 xv[8], wv[WU];
             auto issue = [&](int ch) __attribute__((always_inline)) {
                 const int c = ch * p.CK + cgi * 8;
                 const bool colOK = colIn && ch < p.nChunks && c < p.CinS;
@@ -520,10 +501,10 @@ __global__ __launch_bounds__(256) void nhwc_conv_kernel(const bf16* __restrict__
                 if (ch) __syncthreads();                                  // every wave has left the previous chunk's images
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
-                    if (grp < G && grp * 8 + j < nrows) *reinterpret_cast<u32x4*>(sX + (grp * 8 + j) * (p.RW * p.CKp) + ldst) = xv[j];
+                    if (grp < G && grp * 8 + j < nrows) *reinterpret_cast<otp_u32x4*>(sX + (grp * 8 + j) * (p.RW * p.CKp) + ldst) = xv[j];
 #pragma unroll
                 for (int i = 0; i < WU; ++i)
-                    if (tid + 256 * i < wunits) *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned char*>(sW) + (tid + 256 * i) * 16) = wv[i];
+                    if (tid + 256 * i < wunits) *reinterpret_cast<otp_u32x4*>(reinterpret_cast<unsigned char*>(sW) + (tid + 256 * i) * 16) = wv[i];
                 __syncthreads();
                 if (ch == 0) OTP_STAMP(2);
                 issue(ch + 1);                                            // in flight under this chunk's MFMAs
@@ -556,7 +537,7 @@ __global__ __launch_bounds__(256) void nhwc_conv_kernel(const bf16* __restrict__
         // (column, channel group) and walks the rows, so the column arithmetic is done once per chunk).
         const int wbase = (ch * p.nM + mt) * wunits * 16;
         const int c0 = ch * p.CK;
-        u32x4 xv[8];
+        otp_u32x4 xv[8];
         // weight slab of this (chunk, m-tile): global -> LDS by the LDS-DMA (the packed slab IS the LDS image: unit i lands at
         // sW + 16 i), no staging registers, no ds_write pass
         for (int u0 = wave * 64; u0 < wunits; u0 += 256)
@@ -576,7 +557,7 @@ __global__ __launch_bounds__(256) void nhwc_conv_kernel(const bf16* __restrict__
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-            if (tid < rowUnits && j < nrows) *reinterpret_cast<u32x4*>(sX + j * (p.RW * p.CKp) + ldst0) = xv[j];
+            if (tid < rowUnits && j < nrows) *reinterpret_cast<otp_u32x4*>(sX + j * (p.RW * p.CKp) + ldst0) = xv[j];
         // the rest (rows past 8, rows wider than 256 units)
         for (int sub = 0; sub * 256 < rowUnits; ++sub) {
             const int cu = sub * 256 + tid;
@@ -585,7 +566,7 @@ __global__ __launch_bounds__(256) void nhwc_conv_kernel(const bf16* __restrict__
             const bool colOK = cu < rowUnits && ix >= 0 && ix < p.W && c < p.CinS;
             const int gcol = (ix * p.CinS + c) * 2, ldst = col * p.CKp + cgi * 8;
             for (int r0 = sub ? 0 : 8; r0 < nrows; r0 += 8) {
-                u32x4 v[8];
+                otp_u32x4 v[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const int iy = rowLo + r0 + j;
@@ -595,7 +576,7 @@ __global__ __launch_bounds__(256) void nhwc_conv_kernel(const bf16* __restrict__
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
                     if (cu < rowUnits && r0 + j < nrows)
-                        *reinterpret_cast<u32x4*>(sX + (r0 + j) * (p.RW * p.CKp) + ldst) = v[j];
+                        *reinterpret_cast<otp_u32x4*>(sX + (r0 + j) * (p.RW * p.CKp) + ldst) = v[j];
             }
         }
         __syncthreads();
@@ -703,11 +684,11 @@ __global__ __launch_bounds__(256) void nhwc_wgrad_kernel(const bf16* __restrict_
         const int dy = tap / p.kw, dx = tap - dy * p.kw;
         xoff[i] = (p.tapmode ? tap * p.TPX : (dy * p.dil) * p.RW + dx * p.dil) * p.XC + cb * 16;
     }
-    f32x4 acc[3][WG_NBW];
+    otp_f32x4 acc[3][WG_NBW];
 #pragma unroll
     for (int m = 0; m < 3; ++m)
 #pragma unroll
-        for (int i = 0; i < WG_NBW; ++i) acc[m][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < WG_NBW; ++i) acc[m][i] = otp_f32x4{0.f, 0.f, 0.f, 0.f};
 
     // transpose-read addressing: within a 16-lane group, lane 4q+pp supplies row q (pixel), columns 4pp..4pp+3 (channels)
     const int q = l15 >> 2, pp = l15 & 3;
@@ -719,7 +700,7 @@ __global__ __launch_bounds__(256) void nhwc_wgrad_kernel(const bf16* __restrict_
 
     // the padding channel group of every window pixel is zero for the whole kernel
     for (int i = tid; i < (p.tapmode ? p.kh * p.kw * p.TPX : p.rowsMax * p.RW); i += 256)
-        *reinterpret_cast<u32x4*>(sX + (size_t)i * p.XC + xcu * 8) = u32x4{0u, 0u, 0u, 0u};
+        *reinterpret_cast<otp_u32x4*>(sX + (size_t)i * p.XC + xcu * 8) = otp_u32x4{0u, 0u, 0u, 0u};
 
     struct Geom {
         int n, p0, p1, oy0, rowLo, nrows;
@@ -755,7 +736,7 @@ __global__ __launch_bounds__(256) void nhwc_wgrad_kernel(const bf16* __restrict_
             xu[j] = (r << 24) | (col << 8) | cg;
         }
     }
-    u32x4 gv[WG_GU], xv[PF ? WG_XU : 1];
+    otp_u32x4 gv[WG_GU], xv[PF ? WG_XU : 1];
     auto load_g = [&](const Geom& g) {
 #pragma unroll
         for (int j = 0; j < WG_GU; ++j) {
@@ -785,12 +766,12 @@ __global__ __launch_bounds__(256) void nhwc_wgrad_kernel(const bf16* __restrict_
         if (t == t0) OTP_STAMP(1);
 #pragma unroll
         for (int j = 0; j < WG_GU; ++j)
-            if (j * 256 + tid < gunits) *reinterpret_cast<u32x4*>(sG + gpx[j] * 56 + gcg[j] * 8) = gv[j];
+            if (j * 256 + tid < gunits) *reinterpret_cast<otp_u32x4*>(sG + gpx[j] * 56 + gcg[j] * 8) = gv[j];
         if constexpr (PF) {
 #pragma unroll
             for (int j = 0; j < WG_XU; ++j) {
                 const int r = xu[j] >> 24, col = (xu[j] >> 8) & 0xffff, cg = xu[j] & 255;
-                if (r < g.nrows) *reinterpret_cast<u32x4*>(sX + (r * p.RW + col) * p.XC + cg * 8) = xv[j];
+                if (r < g.nrows) *reinterpret_cast<otp_u32x4*>(sX + (r * p.RW + col) * p.XC + cg * 8) = xv[j];
             }
         } else {
             // general form: flat (row, column, channel group) units - or, in tap mode, (tap, tile pixel, channel group) units:
@@ -799,7 +780,7 @@ __global__ __launch_bounds__(256) void nhwc_wgrad_kernel(const bf16* __restrict_
             if (p.tapmode) {
                 const int tunits = p.kh * p.kw * TPX * xcu;
                 for (int base = 0; base < tunits; base += 256 * 8) {
-                    u32x4 v[8];
+                    otp_u32x4 v[8];
                     int dst[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
@@ -816,12 +797,12 @@ __global__ __launch_bounds__(256) void nhwc_wgrad_kernel(const bf16* __restrict_
                     }
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
-                        if (dst[j] >= 0) *reinterpret_cast<u32x4*>(sX + dst[j]) = v[j];
+                        if (dst[j] >= 0) *reinterpret_cast<otp_u32x4*>(sX + dst[j]) = v[j];
                 }
             }
             const int xunits = p.tapmode ? 0 : g.nrows * rowUnits;
             for (int base = 0; base < xunits; base += 256 * 8) {
-                u32x4 v[8];
+                otp_u32x4 v[8];
                 int dst[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
@@ -835,7 +816,7 @@ __global__ __launch_bounds__(256) void nhwc_wgrad_kernel(const bf16* __restrict_
                 }
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
-                    if (dst[j] >= 0) *reinterpret_cast<u32x4*>(sX + dst[j]) = v[j];
+                    if (dst[j] >= 0) *reinterpret_cast<otp_u32x4*>(sX + dst[j]) = v[j];
             }
         }
         __syncthreads();
@@ -878,7 +859,7 @@ __global__ __launch_bounds__(256) void nhwc_wgrad_kernel(const bf16* __restrict_
     OTP_STAMP(4);
     // partial sums in FRAGMENT order, one 16-byte store per lane and accumulator tile (1 KB per wave instruction):
     // part[split][block][wave][i][m][lane][4]; nhwc_wgrad_reduce_kernel maps them to (Cout, Cin, kh, kw)
-    f32x4* dst = reinterpret_cast<f32x4*>(part) + ((size_t)(split * p.nCo * p.nCi + blk) * 4 + wave) * (WG_NBW * 3 * 64);
+    otp_f32x4* dst = reinterpret_cast<otp_f32x4*>(part) + ((size_t)(split * p.nCo * p.nCi + blk) * 4 + wave) * (WG_NBW * 3 * 64);
 #pragma unroll
     for (int i = 0; i < WG_NBW; ++i)
 #pragma unroll
@@ -909,26 +890,26 @@ __global__ __launch_bounds__(256) void nhwc_wgrad1x1_kernel(const bf16* __restri
     const int cib = bid % p.nCi, cob = bid / p.nCi;
     const int co0 = cob * 48 * CG, ci0 = cib * 16 * p.cbw;
     const int npx = p.Ho * p.Wo, TPX = p.TPX;
-    f32x4 acc[3][NS];
+    otp_f32x4 acc[3][NS];
 #pragma unroll
     for (int m = 0; m < 3; ++m)
 #pragma unroll
-        for (int i = 0; i < NS; ++i) acc[m][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < NS; ++i) acc[m][i] = otp_f32x4{0.f, 0.f, 0.f, 0.f};
     const int q = l15 >> 2, pp = l15 & 3;
     const int xcu = p.XC / 8 - 1, gcu = 6 * CG;
     const int gunits = TPX * gcu, xunits = TPX * xcu;
     const otp_rsrc xres = make_rsrc(x, (size_t)p.N * npx * p.CinS * 2);
     const otp_rsrc gres = make_rsrc(gy, (size_t)p.N * npx * p.CoutS * 2);
     for (int i = tid; i < TPX; i += 256) {                     // padding channel groups: zero for the whole kernel
-        *reinterpret_cast<u32x4*>(sX + (size_t)i * p.XC + xcu * 8) = u32x4{0u, 0u, 0u, 0u};
-        *reinterpret_cast<u32x4*>(sG + (size_t)i * GC + 48 * CG) = u32x4{0u, 0u, 0u, 0u};
+        *reinterpret_cast<otp_u32x4*>(sX + (size_t)i * p.XC + xcu * 8) = otp_u32x4{0u, 0u, 0u, 0u};
+        *reinterpret_cast<otp_u32x4*>(sG + (size_t)i * GC + 48 * CG) = otp_u32x4{0u, 0u, 0u, 0u};
     }
     const int t0 = split * p.tilesPerSplit, t1 = min(t0 + p.tilesPerSplit, p.tilesTotal);
     for (int t = t0; t < t1; ++t) {
         const int n = t / p.tilesPerImg, p0 = (t - n * p.tilesPerImg) * TPX, p1 = min(p0 + TPX, npx);
         __syncthreads();                                        // the previous tile's fragments have been read
         for (int base = 0; base < gunits; base += 256 * 8) {
-            u32x4 v[8];
+            otp_u32x4 v[8];
             int dst[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -940,10 +921,10 @@ __global__ __launch_bounds__(256) void nhwc_wgrad1x1_kernel(const bf16* __restri
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                if (dst[j] >= 0) *reinterpret_cast<u32x4*>(sG + dst[j]) = v[j];
+                if (dst[j] >= 0) *reinterpret_cast<otp_u32x4*>(sG + dst[j]) = v[j];
         }
         for (int base = 0; base < xunits; base += 256 * 8) {
-            u32x4 v[8];
+            otp_u32x4 v[8];
             int dst[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -955,7 +936,7 @@ __global__ __launch_bounds__(256) void nhwc_wgrad1x1_kernel(const bf16* __restri
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                if (dst[j] >= 0) *reinterpret_cast<u32x4*>(sX + dst[j]) = v[j];
+                if (dst[j] >= 0) *reinterpret_cast<otp_u32x4*>(sX + dst[j]) = v[j];
         }
         __syncthreads();
         for (int k0 = 0; k0 < TPX; k0 += 32) {
@@ -984,7 +965,7 @@ __global__ __launch_bounds__(256) void nhwc_wgrad1x1_kernel(const bf16* __restri
             }
         }
     }
-    f32x4* dst = reinterpret_cast<f32x4*>(part) + ((size_t)(split * p.nCo * p.nCi + blk) * 4 + wave) * (WG_NBW * 3 * 64);
+    otp_f32x4* dst = reinterpret_cast<otp_f32x4*>(part) + ((size_t)(split * p.nCo * p.nCi + blk) * 4 + wave) * (WG_NBW * 3 * 64);
 #pragma unroll
     for (int i = 0; i < NS; ++i)
 #pragma unroll
@@ -1184,8 +1165,8 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const bf16* __restrict__ 
         const bf16x8 v = *reinterpret_cast<const bf16x8*>(x + u * 8);
         bf16x8 r8;
         if constexpr (HAS_RES) r8 = *reinterpret_cast<const bf16x8*>(res + u * 8);
-        const f32x4 sa = *reinterpret_cast<const f32x4*>(scale + c), sb = *reinterpret_cast<const f32x4*>(scale + c + 4);
-        const f32x4 ha = *reinterpret_cast<const f32x4*>(shift + c), hb = *reinterpret_cast<const f32x4*>(shift + c + 4);
+        const otp_f32x4 sa = *reinterpret_cast<const otp_f32x4*>(scale + c), sb = *reinterpret_cast<const otp_f32x4*>(scale + c + 4);
+        const otp_f32x4 ha = *reinterpret_cast<const otp_f32x4*>(shift + c), hb = *reinterpret_cast<const otp_f32x4*>(shift + c + 4);
         bf16x8 o;
         unsigned bits = 0;                                     // ReLU mask of the 8 channels (1 bit each): what backward needs of y
 #pragma unroll
@@ -1463,9 +1444,9 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const bf16* __restric
     const int npx = min(64, HW - p0);
     for (int u = threadIdx.x; u < 64 * C8; u += 256) {
         const int px = u / C8, cg = u - px * C8;
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (px < npx) v = *reinterpret_cast<const u32x4*>(in + ((size_t)n * HW + p0 + px) * CS + cg * 8);
-        *reinterpret_cast<u32x4*>(sT + px * CP + cg * 8) = v;
+        otp_u32x4 v = {0u, 0u, 0u, 0u};
+        if (px < npx) v = *reinterpret_cast<const otp_u32x4*>(in + ((size_t)n * HW + p0 + px) * CS + cg * 8);
+        *reinterpret_cast<otp_u32x4*>(sT + px * CP + cg * 8) = v;
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1485,10 +1466,10 @@ __global__ __launch_bounds__(256) void dilate_nhwc_kernel(const bf16* __restrict
         const int xx = r % W; r /= W;
         const int yy = r % H;
         const int n = (int)(r / H);
-        u32x4 v = {0u, 0u, 0u, 0u};
+        otp_u32x4 v = {0u, 0u, 0u, 0u};
         if (yy % s == 0 && xx % s == 0 && yy / s < Hi && xx / s < Wi)
-            v = *reinterpret_cast<const u32x4*>(in + ((((size_t)n * Hi + yy / s) * Wi + xx / s) * C8 + cg) * 8);
-        *reinterpret_cast<u32x4*>(out + u * 8) = v;
+            v = *reinterpret_cast<const otp_u32x4*>(in + ((((size_t)n * Hi + yy / s) * Wi + xx / s) * C8 + cg) * 8);
+        *reinterpret_cast<otp_u32x4*>(out + u * 8) = v;
     }
 }
 

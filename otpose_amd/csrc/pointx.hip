@@ -9,30 +9,9 @@
 // tiles (16 KB: LDS-DMA, double buffered, one barrier per block that waits for the DMA alone - the result stores stay in flight);
 // a tile's 16 x 32 result is scaled, shifted, added to the residual, clamped and stored as soon as its 6 KS MFMAs are done.
 // Tensors are fp32 NCHW channel slices: (ctot, coff) per operand, as everywhere in the engine.
-#include "common.h"
+#include "x3.h"
 
 namespace {
-
-typedef otp_x3x8 h16x8;              // 8 operand pieces of the split products (common.h: IEEE half since round 4)
-typedef otp_x3x2 h16x2;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void px_split8(const float (&v)[8], h16x8& hi, h16x8& lo) {
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x2 a = {v[2 * i], v[2 * i + 1]};
-        const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, h16x2));
-        const f32x2 af = otp_x3_widen(hb);
-        h[i] = hb;
-        l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a - af, h16x2));
-    }
-    hi = __builtin_bit_cast(h16x8, (u32x4){h[0], h[1], h[2], h[3]});
-    lo = __builtin_bit_cast(h16x8, (u32x4){l[0], l[1], l[2], l[3]});
-}
 
 constexpr int px_ks(int CIN) { return CIN / 32; }
 constexpr int px_mpb(int CIN) { return 8 / px_ks(CIN); }                // 16-row output tiles per weight block
@@ -60,9 +39,9 @@ __global__ void pointx_pack_kernel(const float* __restrict__ w, const float* __r
             const int c = 32 * ks + 8 * kq + j;
             v[j] = (row < Cout && c < Cin) ? w[(size_t)row * Cin + c] : 0.f;
         }
-        h16x8 hi, lo;
-        px_split8(v, hi, lo);
-        reinterpret_cast<u32x4*>(packed)[idx] = __builtin_bit_cast(u32x4, (f2 & 1) ? lo : hi);
+        otp_x3x8 hi, lo;
+        otp_x3_split8(v, hi, lo);
+        reinterpret_cast<otp_u32x4*>(packed)[idx] = __builtin_bit_cast(otp_u32x4, (f2 & 1) ? lo : hi);
     } else if (idx < nblk * units + 2 * PX_MAX_COUT / 4) {                  // [scale 256][shift 256] floats, by channel
         const int q = idx - nblk * units;
         float v[4];
@@ -71,22 +50,8 @@ __global__ void pointx_pack_kernel(const float* __restrict__ w, const float* __r
             const int e = 4 * q + i, c = e & (PX_MAX_COUT - 1);
             v[i] = c < Cout ? (e < PX_MAX_COUT ? (scale ? scale[c] : 1.f) : (shift ? shift[c] : 0.f)) : 0.f;
         }
-        reinterpret_cast<u32x4*>(packed)[idx] = (u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]),
+        reinterpret_cast<otp_u32x4*>(packed)[idx] = (otp_u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]),
                                                         __builtin_bit_cast(uint32_t, v[2]), __builtin_bit_cast(uint32_t, v[3])};
-    }
-}
-
-// one weight block global -> LDS with the LDS-DMA (256 threads, four passes): unit u (16 bytes) lands at lds + 16 u
-template <int BLKB>
-__device__ __forceinline__ void px_stage(const unsigned char* __restrict__ src, unsigned char* lds) {
-    constexpr int NST = BLKB / 16 / 256;
-    static_assert(NST * 256 * 16 == BLKB, "whole passes");
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-#pragma unroll
-    for (int i = 0; i < NST; ++i) {
-        const int u0 = i * 256 + wave * 64;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)(u0 + lane) * 16),
-                                         (__attribute__((address_space(3))) void*)(lds + u0 * 16), 16, 0, 0);
     }
 }
 
@@ -111,11 +76,11 @@ __global__ __launch_bounds__(256, CIN <= 128 ? 3 : 2) void pointx_kernel(PxArgs 
     const int b = blockIdx.x / A.tiles_per_b, tile = blockIdx.x - b * A.tiles_per_b;
     const int T = A.T, tok = tile * 128 + wave * 32 + 2 * n;
     const bool valid = tok < T;
-    px_stage<BLKB>(A.packed, lds);
+    otp_lds_stage<256, BLKB>(A.packed, lds);
     if (tid < 2 * PX_MAX_COUT / 4)
-        reinterpret_cast<f32x4*>(ss)[tid] = reinterpret_cast<const f32x4*>(A.packed + (size_t)A.nblk * BLKB)[tid];
+        reinterpret_cast<otp_f32x4*>(ss)[tid] = reinterpret_cast<const otp_f32x4*>(A.packed + (size_t)A.nblk * BLKB)[tid];
     const float* __restrict__ x = A.x + ((size_t)b * A.x_ctot + A.x_coff) * T + (valid ? tok : T - 2);
-    h16x8 Xh[KS][2], Xl[KS][2];
+    otp_x3x8 Xh[KS][2], Xl[KS][2];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         float v0[8], v1[8];
@@ -123,12 +88,12 @@ __global__ __launch_bounds__(256, CIN <= 128 ? 3 : 2) void pointx_kernel(PxArgs 
         for (int j = 0; j < 8; ++j) {
             const int c = 32 * ks + 8 * kq + j;                              // channels past Cin (Cin padded to the template's CIN):
             const bool live = c < A.Cin;                                     // zero weights, and nothing is read
-            const f32x2 v = *reinterpret_cast<const f32x2*>(x + (size_t)(live ? c : 0) * T);
+            const otp_f32x2 v = *reinterpret_cast<const otp_f32x2*>(x + (size_t)(live ? c : 0) * T);
             v0[j] = live ? v.x : 0.f;
             v1[j] = live ? v.y : 0.f;
         }
-        px_split8(v0, Xh[ks][0], Xl[ks][0]);
-        px_split8(v1, Xh[ks][1], Xl[ks][1]);
+        otp_x3_split8(v0, Xh[ks][0], Xl[ks][0]);
+        otp_x3_split8(v1, Xh[ks][1], Xl[ks][1]);
     }
     const unsigned plane = (unsigned)((size_t)A.Cout * T * sizeof(float));
     const otp_rsrc ro = make_rsrc32(A.out + ((size_t)b * A.o_ctot + A.o_coff) * T, plane);
@@ -143,28 +108,28 @@ __global__ __launch_bounds__(256, CIN <= 128 ? 3 : 2) void pointx_kernel(PxArgs 
 #pragma unroll 1
     for (int blk = 0; blk < A.nblk; ++blk) {
         int voff[MPB][4];
-        f32x2 r[MPB][4];
+        otp_f32x2 r[MPB][4];
 #pragma unroll
         for (int m = 0; m < MPB; ++m)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int c = 16 * (blk * MPB + m) + 4 * kq + i;
                 voff[m][i] = (valid && c < A.Cout) ? (c * T + tok) * 4 : -16;
-                if (RES) r[m][i] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rr, voff[m][i], 0, 0));
+                if (RES) r[m][i] = __builtin_bit_cast(otp_f32x2, __builtin_amdgcn_raw_buffer_load_b64(rr, voff[m][i], 0, 0));
             }
         asm volatile("" ::: "memory");
         // (the last trip re-stages block 0, which nobody reads: every wave issues the same instructions on every trip)
-        px_stage<BLKB>(A.packed + (size_t)(blk + 1 < A.nblk ? blk + 1 : 0) * BLKB, lds + ((blk + 1) & 1) * BLKB);
+        otp_lds_stage<256, BLKB>(A.packed + (size_t)(blk + 1 < A.nblk ? blk + 1 : 0) * BLKB, lds + ((blk + 1) & 1) * BLKB);
         asm volatile("" ::: "memory");
         const unsigned char* P = lds + (blk & 1) * BLKB;
-        f32x4 acc[MPB][2];
+        otp_f32x4 acc[MPB][2];
 #pragma unroll
         for (int m = 0; m < MPB; ++m) {
-            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+            otp_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                const h16x8 ah = *reinterpret_cast<const h16x8*>(P + ((m * KS + ks) * 2) * 1024 + lane * 16);
-                const h16x8 al = *reinterpret_cast<const h16x8*>(P + ((m * KS + ks) * 2 + 1) * 1024 + lane * 16);
+                const otp_x3x8 ah = *reinterpret_cast<const otp_x3x8*>(P + ((m * KS + ks) * 2) * 1024 + lane * 16);
+                const otp_x3x8 al = *reinterpret_cast<const otp_x3x8*>(P + ((m * KS + ks) * 2 + 1) * 1024 + lane * 16);
                 acc0 = OTP_X3_MFMA(al, Xh[ks][0], acc0, 0, 0, 0);
                 acc1 = OTP_X3_MFMA(al, Xh[ks][1], acc1, 0, 0, 0);
                 acc0 = OTP_X3_MFMA(ah, Xl[ks][0], acc0, 0, 0, 0);
@@ -179,17 +144,17 @@ __global__ __launch_bounds__(256, CIN <= 128 ? 3 : 2) void pointx_kernel(PxArgs 
 #pragma unroll
         for (int m = 0; m < MPB; ++m) {
             const int c0 = (16 * (blk * MPB + m) + 4 * kq) & (PX_MAX_COUT - 1);
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(ss + c0);
-            const f32x4 sh = *reinterpret_cast<const f32x4*>(ss + PX_MAX_COUT + c0);
+            const otp_f32x4 sc = *reinterpret_cast<const otp_f32x4*>(ss + c0);
+            const otp_f32x4 sh = *reinterpret_cast<const otp_f32x4*>(ss + PX_MAX_COUT + c0);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                f32x2 v = {acc[m][0][i] * sc[i] + sh[i], acc[m][1][i] * sc[i] + sh[i]};
+                otp_f32x2 v = {acc[m][0][i] * sc[i] + sh[i], acc[m][1][i] * sc[i] + sh[i]};
                 if (RES) v += r[m][i];
                 bad |= otp_out_of_range(v.x);
                 bad |= otp_out_of_range(v.y);
                 v.x = fmaxf(v.x, lo_clamp);
                 v.y = fmaxf(v.y, lo_clamp);
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), ro, voff[m][i], 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(otp_u32x2, v), ro, voff[m][i], 0, 0);
             }
         }
         static_assert(4 * MPB <= 16, "stores after the DMA");
@@ -217,22 +182,22 @@ __global__ __launch_bounds__(256, CIN <= 128 ? 3 : 2) void pointx_s8_kernel(PxAr
     const int b = blockIdx.x / A.tiles_per_b, tile = blockIdx.x - b * A.tiles_per_b;
     const int T = A.T, tok = tile * 128 + wave * 32 + 2 * n;
     const bool valid = tok < T;
-    px_stage<BLKB>(A.packed, lds);
+    otp_lds_stage<256, BLKB>(A.packed, lds);
     if (tid < 2 * PX_MAX_COUT / 4)
-        reinterpret_cast<f32x4*>(ss)[tid] = reinterpret_cast<const f32x4*>(A.packed + (size_t)A.nblk * BLKB)[tid];
+        reinterpret_cast<otp_f32x4*>(ss)[tid] = reinterpret_cast<const otp_f32x4*>(A.packed + (size_t)A.nblk * BLKB)[tid];
     const float* __restrict__ x = A.x + ((size_t)b * A.x_ctot + A.x_coff) * T + (valid ? tok : T - 2);
-    h16x8 Xh[KS][2], Xl[KS][2];
+    otp_x3x8 Xh[KS][2], Xl[KS][2];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         float v0[8], v1[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const f32x2 v = *reinterpret_cast<const f32x2*>(x + (size_t)(32 * ks + 8 * kq + j) * T);
+            const otp_f32x2 v = *reinterpret_cast<const otp_f32x2*>(x + (size_t)(32 * ks + 8 * kq + j) * T);
             v0[j] = v.x;
             v1[j] = v.y;
         }
-        px_split8(v0, Xh[ks][0], Xl[ks][0]);
-        px_split8(v1, Xh[ks][1], Xl[ks][1]);
+        otp_x3_split8(v0, Xh[ks][0], Xl[ks][0]);
+        otp_x3_split8(v1, Xh[ks][1], Xl[ks][1]);
     }
     const unsigned plane = (unsigned)((size_t)A.Cout * T * sizeof(float));         // an S8 image is 4 bytes per element too
     const otp_rsrc ro = make_rsrc32(A.out + (size_t)b * A.Cout * T, plane);
@@ -242,29 +207,29 @@ __global__ __launch_bounds__(256, CIN <= 128 ? 3 : 2) void pointx_s8_kernel(PxAr
     __syncthreads();
 #pragma unroll 1
     for (int blk = 0; blk < A.nblk; ++blk) {
-        px_stage<BLKB>(A.packed + (size_t)(blk + 1 < A.nblk ? blk + 1 : 0) * BLKB, lds + ((blk + 1) & 1) * BLKB);
+        otp_lds_stage<256, BLKB>(A.packed + (size_t)(blk + 1 < A.nblk ? blk + 1 : 0) * BLKB, lds + ((blk + 1) & 1) * BLKB);
         asm volatile("" ::: "memory");
         const unsigned char* P = lds + (blk & 1) * BLKB;
-        f32x4 acc[MPB][2];
+        otp_f32x4 acc[MPB][2];
         // residual of the lane's two pixels, 8 channels per tile pair: in flight under the MFMAs of the block
-        f32x2 rv[RES ? MPB / 2 : 1][8];
+        otp_f32x2 rv[RES ? MPB / 2 : 1][8];
         if constexpr (RES) {
 #pragma unroll
             for (int m = 0; m < MPB; m += 2) {
                 const int pr = (blk * MPB + m) >> 1, c8 = 32 * pr + 8 * kq;
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
-                    rv[m >> 1][e] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(
+                    rv[m >> 1][e] = __builtin_bit_cast(otp_f32x2, __builtin_amdgcn_raw_buffer_load_b64(
                         rr, (valid && c8 < A.Cout) ? ((c8 + e) * T + tok) * 4 : -16, 0, 0));
             }
         }
 #pragma unroll
         for (int m = 0; m < MPB; ++m) {
-            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+            otp_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                const h16x8 ah = *reinterpret_cast<const h16x8*>(P + ((m * KS + ks) * 2) * 1024 + lane * 16);
-                const h16x8 al = *reinterpret_cast<const h16x8*>(P + ((m * KS + ks) * 2 + 1) * 1024 + lane * 16);
+                const otp_x3x8 ah = *reinterpret_cast<const otp_x3x8*>(P + ((m * KS + ks) * 2) * 1024 + lane * 16);
+                const otp_x3x8 al = *reinterpret_cast<const otp_x3x8*>(P + ((m * KS + ks) * 2 + 1) * 1024 + lane * 16);
                 acc0 = OTP_X3_MFMA(al, Xh[ks][0], acc0, 0, 0, 0);
                 acc1 = OTP_X3_MFMA(al, Xh[ks][1], acc1, 0, 0, 0);
                 acc0 = OTP_X3_MFMA(ah, Xl[ks][0], acc0, 0, 0, 0);
@@ -278,10 +243,10 @@ __global__ __launch_bounds__(256, CIN <= 128 ? 3 : 2) void pointx_s8_kernel(PxAr
 #pragma unroll
         for (int m = 0; m < MPB; m += 2) {
             const int pr = (blk * MPB + m) >> 1, c8 = 32 * pr + 8 * kq, g = 4 * pr + kq;        // channel group of this lane
-            const f32x4 sc0 = *reinterpret_cast<const f32x4*>(ss + (c8 & (PX_MAX_COUT - 1)));
-            const f32x4 sc1 = *reinterpret_cast<const f32x4*>(ss + ((c8 + 4) & (PX_MAX_COUT - 1)));
-            const f32x4 sh0 = *reinterpret_cast<const f32x4*>(ss + PX_MAX_COUT + (c8 & (PX_MAX_COUT - 1)));
-            const f32x4 sh1 = *reinterpret_cast<const f32x4*>(ss + PX_MAX_COUT + ((c8 + 4) & (PX_MAX_COUT - 1)));
+            const otp_f32x4 sc0 = *reinterpret_cast<const otp_f32x4*>(ss + (c8 & (PX_MAX_COUT - 1)));
+            const otp_f32x4 sc1 = *reinterpret_cast<const otp_f32x4*>(ss + ((c8 + 4) & (PX_MAX_COUT - 1)));
+            const otp_f32x4 sh0 = *reinterpret_cast<const otp_f32x4*>(ss + PX_MAX_COUT + (c8 & (PX_MAX_COUT - 1)));
+            const otp_f32x4 sh1 = *reinterpret_cast<const otp_f32x4*>(ss + PX_MAX_COUT + ((c8 + 4) & (PX_MAX_COUT - 1)));
             const bool live = valid && c8 < A.Cout;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -295,11 +260,11 @@ __global__ __launch_bounds__(256, CIN <= 128 ? 3 : 2) void pointx_s8_kernel(PxAr
                     v[i] = fmaxf(u0, lo_clamp);
                     v[4 + i] = fmaxf(u1, lo_clamp);
                 }
-                h16x8 hi, lo;
-                px_split8(v, hi, lo);
+                otp_x3x8 hi, lo;
+                otp_x3_split8(v, hi, lo);
                 const int o = live ? ((g * 2) * T + tok + h) * 16 : -16;
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), ro, o, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), ro, live ? o + T * 16 : -16, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(otp_u32x4, hi), ro, o, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(otp_u32x4, lo), ro, live ? o + T * 16 : -16, 0, 0);
             }
         }
         static_assert(2 * MPB == 4 || 2 * MPB == 8, "stores after the DMA");
@@ -358,41 +323,41 @@ __global__ __launch_bounds__(256, CIN <= 64 ? 3 : 2) void pointx_pair_kernel(PxP
     const int b = blockIdx.x / A.tiles_per_b, tile = blockIdx.x - b * A.tiles_per_b;
     const int T = A.T, tok = tile * 128 + wave * 32 + 2 * n;
     const bool valid = tok < T;
-    px_stage<W1B>(A.w1, lds);
+    otp_lds_stage<256, W1B>(A.w1, lds);
     {
         const unsigned char* tail = tid < 128 ? A.w1 + (size_t)PXP_PAIRS * W1B : A.w2 + (size_t)NT2 * (PXP_CMID / 32) * 2048;
-        reinterpret_cast<f32x4*>(ss1)[tid] = reinterpret_cast<const f32x4*>(tail)[tid & 127];
+        reinterpret_cast<otp_f32x4*>(ss1)[tid] = reinterpret_cast<const otp_f32x4*>(tail)[tid & 127];
     }
     const float* __restrict__ x = A.x + ((size_t)b * A.x_ctot + A.x_coff) * T + (valid ? tok : T - 2);
-    h16x8 Xh[KS][2], Xl[KS][2];
+    otp_x3x8 Xh[KS][2], Xl[KS][2];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         float v0[8], v1[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const f32x2 v = *reinterpret_cast<const f32x2*>(x + (size_t)(32 * ks + 8 * kq + j) * T);
+            const otp_f32x2 v = *reinterpret_cast<const otp_f32x2*>(x + (size_t)(32 * ks + 8 * kq + j) * T);
             v0[j] = v.x;
             v1[j] = v.y;
         }
-        px_split8(v0, Xh[ks][0], Xl[ks][0]);
-        px_split8(v1, Xh[ks][1], Xl[ks][1]);
+        otp_x3_split8(v0, Xh[ks][0], Xl[ks][0]);
+        otp_x3_split8(v1, Xh[ks][1], Xl[ks][1]);
     }
     const unsigned plane = (unsigned)((size_t)PXP_CMID * T * sizeof(float));
     const otp_rsrc ro = make_rsrc32(A.out + ((size_t)b * A.o_ctot + A.o_coff) * T, plane);
     const otp_rsrc rr = make_rsrc32(RES ? A.res + ((size_t)b * A.r_ctot + A.r_coff) * T : A.out, RES ? plane : 0u);
     const float lo1 = A.relu1 ? 0.f : -__builtin_inff(), lo2 = A.relu2 ? 0.f : -__builtin_inff();
     bool bad = false;                                  // range guard (common.h), both outputs, before the clamps
-    f32x4 acc2[NT2][2];
+    otp_f32x4 acc2[NT2][2];
 #pragma unroll
-    for (int t = 0; t < NT2; ++t) acc2[t][0] = acc2[t][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    h16x8 Yh[2] = {}, Yl[2] = {};                      // the previous pair's results: B fragments of GEMM 2's k-step pr - 1
+    for (int t = 0; t < NT2; ++t) acc2[t][0] = acc2[t][1] = (otp_f32x4){0.f, 0.f, 0.f, 0.f};
+    otp_x3x8 Yh[2] = {}, Yl[2] = {};                      // the previous pair's results: B fragments of GEMM 2's k-step pr - 1
     __syncthreads();                                   // pair 0 and the scale / shift vectors landed
     // k-step ks of GEMM 2 from the slice at W (a trip's buffer behind GEMM 1's pair)
     auto gemm2 = [&](const unsigned char* W) {
 #pragma unroll
         for (int t = 0; t < NT2; ++t) {
-            const h16x8 ah = *reinterpret_cast<const h16x8*>(W + (t * 2) * 1024 + lane * 16);
-            const h16x8 al = *reinterpret_cast<const h16x8*>(W + (t * 2 + 1) * 1024 + lane * 16);
+            const otp_x3x8 ah = *reinterpret_cast<const otp_x3x8*>(W + (t * 2) * 1024 + lane * 16);
+            const otp_x3x8 al = *reinterpret_cast<const otp_x3x8*>(W + (t * 2 + 1) * 1024 + lane * 16);
             acc2[t][0] = OTP_X3_MFMA(al, Yh[0], acc2[t][0], 0, 0, 0);
             acc2[t][1] = OTP_X3_MFMA(al, Yh[1], acc2[t][1], 0, 0, 0);
             acc2[t][0] = OTP_X3_MFMA(ah, Yl[0], acc2[t][0], 0, 0, 0);
@@ -407,27 +372,27 @@ __global__ __launch_bounds__(256, CIN <= 64 ? 3 : 2) void pointx_pair_kernel(PxP
     for (int pr = 0; pr < PXP_PAIRS; ++pr) {
         const int c8 = 32 * pr + 8 * kq;                                     // the lane's 8 channels of this pair
         int voff[8];
-        f32x2 rv[8];
+        otp_f32x2 rv[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             voff[e] = valid ? ((c8 + e) * T + tok) * 4 : -16;
-            if (RES) rv[e] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rr, voff[e], 0, 0));
+            if (RES) rv[e] = __builtin_bit_cast(otp_f32x2, __builtin_amdgcn_raw_buffer_load_b64(rr, voff[e], 0, 0));
         }
         asm volatile("" ::: "memory");
         // (the last trip re-stages pair 0, which nobody reads, next to k-slice 7, which the step behind the loop reads)
         unsigned char* nxt = lds + ((pr + 1) & 1) * BUFB;
-        px_stage<W1B>(A.w1 + (size_t)((pr + 1) & (PXP_PAIRS - 1)) * W1B, nxt);
+        otp_lds_stage<256, W1B>(A.w1 + (size_t)((pr + 1) & (PXP_PAIRS - 1)) * W1B, nxt);
         pxp_stage_w2(A.w2, pr, nxt + W1B);
         asm volatile("" ::: "memory");
         const unsigned char* P = lds + (pr & 1) * BUFB;
-        f32x4 acc[2][2];
+        otp_f32x4 acc[2][2];
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
-            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+            otp_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                const h16x8 ah = *reinterpret_cast<const h16x8*>(P + ((m * KS + ks) * 2) * 1024 + lane * 16);
-                const h16x8 al = *reinterpret_cast<const h16x8*>(P + ((m * KS + ks) * 2 + 1) * 1024 + lane * 16);
+                const otp_x3x8 ah = *reinterpret_cast<const otp_x3x8*>(P + ((m * KS + ks) * 2) * 1024 + lane * 16);
+                const otp_x3x8 al = *reinterpret_cast<const otp_x3x8*>(P + ((m * KS + ks) * 2 + 1) * 1024 + lane * 16);
                 acc0 = OTP_X3_MFMA(al, Xh[ks][0], acc0, 0, 0, 0);
                 acc1 = OTP_X3_MFMA(al, Xh[ks][1], acc1, 0, 0, 0);
                 acc0 = OTP_X3_MFMA(ah, Xl[ks][0], acc0, 0, 0, 0);
@@ -440,9 +405,9 @@ __global__ __launch_bounds__(256, CIN <= 64 ? 3 : 2) void pointx_pair_kernel(PxP
         }
         if (pr > 0) gemm2(P + W1B);
         asm volatile("" ::: "memory");
-        const f32x4 sc0 = *reinterpret_cast<const f32x4*>(ss1 + c8), sc1 = *reinterpret_cast<const f32x4*>(ss1 + c8 + 4);
-        const f32x4 sh0 = *reinterpret_cast<const f32x4*>(ss1 + PX_MAX_COUT + c8);
-        const f32x4 sh1 = *reinterpret_cast<const f32x4*>(ss1 + PX_MAX_COUT + c8 + 4);
+        const otp_f32x4 sc0 = *reinterpret_cast<const otp_f32x4*>(ss1 + c8), sc1 = *reinterpret_cast<const otp_f32x4*>(ss1 + c8 + 4);
+        const otp_f32x4 sh0 = *reinterpret_cast<const otp_f32x4*>(ss1 + PX_MAX_COUT + c8);
+        const otp_f32x4 sh1 = *reinterpret_cast<const otp_f32x4*>(ss1 + PX_MAX_COUT + c8 + 4);
         float v[2][8];
 #pragma unroll
         for (int h = 0; h < 2; ++h)
@@ -457,9 +422,9 @@ __global__ __launch_bounds__(256, CIN <= 64 ? 3 : 2) void pointx_pair_kernel(PxP
             }
 #pragma unroll
         for (int e = 0; e < 8; ++e)
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, (f32x2){v[0][e], v[1][e]}), ro, voff[e], 0, 0);
-        px_split8(v[0], Yh[0], Yl[0]);
-        px_split8(v[1], Yh[1], Yl[1]);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(otp_u32x2, (otp_f32x2){v[0][e], v[1][e]}), ro, voff[e], 0, 0);
+        otp_x3_split8(v[0], Yh[0], Yl[0]);
+        otp_x3_split8(v[1], Yh[1], Yl[1]);
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // this wave's part of the next trip's weights has landed (after the last
         __builtin_amdgcn_s_barrier();                      // trip: nothing may land in the LDS once the wave has ended); stores fly on
         asm volatile("" ::: "memory");
@@ -470,9 +435,9 @@ __global__ __launch_bounds__(256, CIN <= 64 ? 3 : 2) void pointx_pair_kernel(PxP
 #pragma unroll
     for (int m = 0; m < NT2; m += 2) {
         const int p = m >> 1, c8 = 32 * p + 8 * kq, g = 4 * p + kq;                              // channel group of this lane
-        const f32x4 sc0 = *reinterpret_cast<const f32x4*>(ss2 + c8), sc1 = *reinterpret_cast<const f32x4*>(ss2 + c8 + 4);
-        const f32x4 sh0 = *reinterpret_cast<const f32x4*>(ss2 + PX_MAX_COUT + c8);
-        const f32x4 sh1 = *reinterpret_cast<const f32x4*>(ss2 + PX_MAX_COUT + c8 + 4);
+        const otp_f32x4 sc0 = *reinterpret_cast<const otp_f32x4*>(ss2 + c8), sc1 = *reinterpret_cast<const otp_f32x4*>(ss2 + c8 + 4);
+        const otp_f32x4 sh0 = *reinterpret_cast<const otp_f32x4*>(ss2 + PX_MAX_COUT + c8);
+        const otp_f32x4 sh1 = *reinterpret_cast<const otp_f32x4*>(ss2 + PX_MAX_COUT + c8 + 4);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             float v[8];
@@ -484,11 +449,11 @@ __global__ __launch_bounds__(256, CIN <= 64 ? 3 : 2) void pointx_pair_kernel(PxP
                 v[i] = fmaxf(u0, lo2);
                 v[4 + i] = fmaxf(u1, lo2);
             }
-            h16x8 hi, lo;
-            px_split8(v, hi, lo);
+            otp_x3x8 hi, lo;
+            otp_x3_split8(v, hi, lo);
             const int o = valid ? ((g * 2) * T + tok + h) * 16 : -16;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), r8, o, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), r8, valid ? o + T * 16 : -16, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(otp_u32x4, hi), r8, o, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(otp_u32x4, lo), r8, valid ? o + T * 16 : -16, 0, 0);
         }
     }
     otp_range_report(A.rflag, bad, OTP_RANGE_POINTX);

@@ -5,29 +5,9 @@
 // split-bf16 MFMAs per 16 pixels x 16 channels: the A operand is gathered straight from the image (stride-2 taps, padding = loads
 // past the buffer descriptor), the weights (BatchNorm scale folded in) sit in registers for the whole kernel, and a lane's
 // accumulator registers are 4 consecutive pixels of one channel: one 16-byte store each.
-#include "common.h"
+#include "x3.h"
 
 namespace {
-
-typedef otp_x3x8 h16x8;              // 8 operand pieces of the split products (common.h: IEEE half since round 4)
-typedef otp_x3x2 h16x2;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void st_split8(const float (&v)[8], h16x8& hi, h16x8& lo) {
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x2 a = {v[2 * i], v[2 * i + 1]};
-        const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, h16x2));
-        const f32x2 af = otp_x3_widen(hb);
-        h[i] = hb;
-        l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a - af, h16x2));
-    }
-    hi = __builtin_bit_cast(h16x8, (u32x4){h[0], h[1], h[2], h[3]});
-    lo = __builtin_bit_cast(h16x8, (u32x4){l[0], l[1], l[2], l[3]});
-}
 
 constexpr int ST_CT = 4;          // 16-channel output tiles (Cout = 64)
 // ST_LDS 1: a wave's 64 pixels x 64 channels pass through its LDS slab so that every store instruction covers 256 contiguous bytes
@@ -42,7 +22,7 @@ constexpr int ST_ROW = 68;        // floats per channel row of a wave's LDS slab
 // [2^13, 2^14), so both half pieces of every weight are normal numbers (otp_conv_desc.out_scale in include/otpose_hip.h is the
 // same device for the descriptor-driven kernels); every workgroup of the pack finds the maximum itself (27 Cout values).
 __global__ void stem_pack_kernel(const float* __restrict__ w, const float* __restrict__ scale, const float* __restrict__ shift,
-                                 u32x4* __restrict__ packed, int Cout) {
+                                 otp_u32x4* __restrict__ packed, int Cout) {
     __shared__ float wmax[4];
     float m = 0.f;
     for (int i = threadIdx.x; i < Cout * 27; i += blockDim.x) m = fmaxf(m, fabsf(w[i] * (scale ? scale[i / 27] : 1.f)));
@@ -55,7 +35,7 @@ __global__ void stem_pack_kernel(const float* __restrict__ w, const float* __res
     const int kx = (m > 0.f && m < 3e38f) ? min(40, max(-40, 14 - e)) : 0;
     const float pre = ldexpf(1.f, kx), post = ldexpf(1.f, -kx);
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx == ST_CT * 2 * 64 + 16) packed[idx] = (u32x4){__builtin_bit_cast(uint32_t, post), 0u, 0u, 0u};
+    if (idx == ST_CT * 2 * 64 + 16) packed[idx] = (otp_u32x4){__builtin_bit_cast(uint32_t, post), 0u, 0u, 0u};
     if (idx < ST_CT * 2 * 64) {
         const int t = idx >> 7, part = (idx >> 6) & 1, lane = idx & 63, co = 16 * t + (lane & 15), kq = lane >> 4;
         float v[8];
@@ -64,30 +44,27 @@ __global__ void stem_pack_kernel(const float* __restrict__ w, const float* __res
             const int k = 8 * kq + j, tap = k / 3, c = k - tap * 3;               // reference weight layout (Cout, 3, 3, 3): [co][c][dy][dx]
             v[j] = (k < 27 && co < Cout) ? w[(co * 3 + c) * 9 + tap] * (scale ? scale[co] : 1.f) * pre : 0.f;
         }
-        h16x8 hi, lo;
-        st_split8(v, hi, lo);
-        packed[idx] = __builtin_bit_cast(u32x4, part ? lo : hi);
+        otp_x3x8 hi, lo;
+        otp_x3_split8(v, hi, lo);
+        packed[idx] = __builtin_bit_cast(otp_u32x4, part ? lo : hi);
     } else if (idx < ST_CT * 2 * 64 + 16) {
         const int q = idx - ST_CT * 2 * 64;
         float v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = (4 * q + i < Cout && shift) ? shift[4 * q + i] * pre : 0.f;
-        packed[idx] = (u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]), __builtin_bit_cast(uint32_t, v[2]),
+        packed[idx] = (otp_u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]), __builtin_bit_cast(uint32_t, v[2]),
                               __builtin_bit_cast(uint32_t, v[3])};
     }
 }
 
 struct StArgs {
     const float* in;
-    const u32x4* packed;
+    const otp_u32x4* packed;
     float* out;
     int B, F, H, W, Ho, Wo, HoWo, Cout, total4;      // total4: groups of 4 output pixels over all frames
     unsigned mWo4;                                    // magic divisor of Wo / 4
     unsigned* rflag;                                  // range-guard word (common.h)
 };
-
-__device__ __forceinline__ uint32_t st_div(uint32_t i, uint32_t magic) { return magic ? __umulhi(i, magic) : i; }
-uint32_t st_magic(uint32_t d) { return d <= 1 ? 0u : (uint32_t)((1ull << 32) / d) + 1u; }
 
 // a wave: 4 tiles of 16 consecutive output pixels; lane (pixel i16, kq) gathers k slots 8 kq .. + 7 of its pixel
 template <int NPT>
@@ -97,11 +74,11 @@ __global__ __launch_bounds__(256) void stem_kernel(StArgs A) {
     __shared__ __attribute__((aligned(16))) float slabs[4 * 64 * ST_ROW];
     float* slab = slabs + wave * 64 * ST_ROW;
 #endif
-    h16x8 Wh[ST_CT], Wl[ST_CT];
+    otp_x3x8 Wh[ST_CT], Wl[ST_CT];
 #pragma unroll
     for (int t = 0; t < ST_CT; ++t) {
-        Wh[t] = __builtin_bit_cast(h16x8, A.packed[(t * 2) * 64 + lane]);
-        Wl[t] = __builtin_bit_cast(h16x8, A.packed[(t * 2 + 1) * 64 + lane]);
+        Wh[t] = __builtin_bit_cast(otp_x3x8, A.packed[(t * 2) * 64 + lane]);
+        Wl[t] = __builtin_bit_cast(otp_x3x8, A.packed[(t * 2 + 1) * 64 + lane]);
     }
     const float shv[ST_CT] = {reinterpret_cast<const float*>(A.packed + ST_CT * 2 * 64)[i16],
                               reinterpret_cast<const float*>(A.packed + ST_CT * 2 * 64)[16 + i16],
@@ -121,7 +98,7 @@ __global__ __launch_bounds__(256) void stem_kernel(StArgs A) {
         const bool pv = px < 4l * A.total4;
         uint32_t r4 = rem0 + (uint32_t)((16 * p + i16) >> 2), n = n0;            // its 4-pixel group inside frame n
         if (r4 >= H4) r4 -= H4, ++n;
-        const uint32_t yo = st_div(r4, A.mWo4), xo = 4 * (r4 - yo * (uint32_t)(A.Wo >> 2)) + (uint32_t)(px & 3);
+        const uint32_t yo = otp_magic_div(r4, A.mWo4), xo = 4 * (r4 - yo * (uint32_t)(A.Wo >> 2)) + (uint32_t)(px & 3);
         const int b = (int)(n % (uint32_t)A.B), f = (int)(n / (uint32_t)A.B);
         const int base = (b * 3 * A.F + 3 * f) * A.H * A.W;                     // channel 0 of frame f of clip b (fits 31 bits: checked on the host)
         float v[8];
@@ -132,8 +109,8 @@ __global__ __launch_bounds__(256) void stem_kernel(StArgs A) {
             const bool ok = pv && k < 27 && iy >= 0 && iy < A.H && ix >= 0 && ix < A.W;
             v[j] = bload(rin, ok ? (base + (c * A.H + iy) * A.W + ix) * 4 : -16, 0);
         }
-        h16x8 ah, al;
-        st_split8(v, ah, al);
+        otp_x3x8 ah, al;
+        otp_x3_split8(v, ah, al);
         // ---- 3 split products per channel tile; D row = pixel, column = channel: register r of lane (channel i16, kq) is pixel 4 kq + r
         const long q0 = P0 + 16 * p + 4 * kq;                                    // this lane's 4 consecutive output pixels
         const bool qv = q0 < 4l * A.total4;
@@ -142,7 +119,7 @@ __global__ __launch_bounds__(256) void stem_kernel(StArgs A) {
         const uint32_t pi = 4 * r2;
 #pragma unroll
         for (int t = 0; t < ST_CT; ++t) {
-            f32x4 acc = {shv[t], shv[t], shv[t], shv[t]};
+            otp_f32x4 acc = {shv[t], shv[t], shv[t], shv[t]};
             acc = OTP_X3_MFMA(al, Wh[t], acc, 0, 0, 0);
             acc = OTP_X3_MFMA(ah, Wl[t], acc, 0, 0, 0);
             acc = OTP_X3_MFMA(ah, Wh[t], acc, 0, 0, 0);
@@ -152,13 +129,13 @@ __global__ __launch_bounds__(256) void stem_kernel(StArgs A) {
             const int co = 16 * t + i16;
 #if ST_LDS
             // through the wave's LDS slab [64 channels][64 + 4 pixels]: the stores below then cover 256 contiguous bytes per channel
-            *reinterpret_cast<f32x4*>(slab + co * ST_ROW + 16 * (p & 3) + 4 * kq) =
-                f32x4{fmaxf(acc[0], 0.f), fmaxf(acc[1], 0.f), fmaxf(acc[2], 0.f), fmaxf(acc[3], 0.f)};
+            *reinterpret_cast<otp_f32x4*>(slab + co * ST_ROW + 16 * (p & 3) + 4 * kq) =
+                otp_f32x4{fmaxf(acc[0], 0.f), fmaxf(acc[1], 0.f), fmaxf(acc[2], 0.f), fmaxf(acc[3], 0.f)};
             (void)qv; (void)n2; (void)pi;
 #else
             if (qv && co < A.Cout) {
-                f32x4 o = {fmaxf(acc[0], 0.f), fmaxf(acc[1], 0.f), fmaxf(acc[2], 0.f), fmaxf(acc[3], 0.f)};
-                *reinterpret_cast<f32x4*>(A.out + ((size_t)n2 * A.Cout + co) * A.HoWo + pi) = o;
+                otp_f32x4 o = {fmaxf(acc[0], 0.f), fmaxf(acc[1], 0.f), fmaxf(acc[2], 0.f), fmaxf(acc[3], 0.f)};
+                *reinterpret_cast<otp_f32x4*>(A.out + ((size_t)n2 * A.Cout + co) * A.HoWo + pi) = o;
             }
 #endif
         }
@@ -172,8 +149,8 @@ __global__ __launch_bounds__(256) void stem_kernel(StArgs A) {
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 const int co = 4 * j + kq;
-                const f32x4 o = *reinterpret_cast<const f32x4*>(slab + co * ST_ROW + 4 * i16);
-                if (rv && co < A.Cout) *reinterpret_cast<f32x4*>(A.out + ((size_t)n3 * A.Cout + co) * A.HoWo + pj) = o;
+                const otp_f32x4 o = *reinterpret_cast<const otp_f32x4*>(slab + co * ST_ROW + 4 * i16);
+                if (rv && co < A.Cout) *reinterpret_cast<otp_f32x4*>(A.out + ((size_t)n3 * A.Cout + co) * A.HoWo + pj) = o;
             }
         }
 #endif
@@ -201,7 +178,7 @@ extern "C" int otp_stem_conv_x3_pack(const void* w, const void* scale, const voi
     if (!otp_stem_conv_x3_weight_bytes(Cout)) return OTP_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(stem_pack_kernel, dim3(otp_ceil_div(ST_CT * 2 * 64 + 17, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const float*>(w), static_cast<const float*>(scale), static_cast<const float*>(shift),
-                       static_cast<u32x4*>(packed), Cout);
+                       static_cast<otp_u32x4*>(packed), Cout);
     return otp_launch_status();
 }
 
@@ -213,12 +190,12 @@ extern "C" int otp_stem_conv_x3(const void* in, const void* packed, void* out, i
         return OTP_ERR_BAD_ARG;
     StArgs a;
     a.in = static_cast<const float*>(in);
-    a.packed = static_cast<const u32x4*>(packed);
+    a.packed = static_cast<const otp_u32x4*>(packed);
     a.out = static_cast<float*>(out);
     a.B = B, a.F = F, a.H = H, a.W = W, a.Ho = (H - 1) / 2 + 1, a.Wo = (W - 1) / 2 + 1, a.HoWo = a.Ho * a.Wo, a.Cout = Cout;
     const long total = (long)B * F * a.HoWo;
     a.total4 = (int)(total / 4);
-    a.mWo4 = st_magic((uint32_t)(a.Wo / 4));
+    a.mWo4 = otp_magic((uint32_t)(a.Wo / 4));
     a.rflag = otp_range_word();
 #ifndef ST_NPT
 #define ST_NPT 4

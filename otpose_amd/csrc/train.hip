@@ -14,8 +14,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // ------------------------------------------------------------------------------------------------
 // dgrad helpers
 // ------------------------------------------------------------------------------------------------
@@ -71,13 +69,15 @@ struct WgradPlan {
     unsigned magicRT, magicNRX, magicWT, magicLWP, magicGX, magicGD;   // ceil(2^32 / d): exact quotients of the small (< 2^16) staging indices
 };
 
+// (a variant of common.h's otp_magic_div / otp_magic: magic = ceil(2^32 / d), d == 1 tested on the divisor itself - kept, because
+// testing magic == 0 instead reads other kernel arguments and changes the kernels' code)
 __device__ __forceinline__ int magic_div(int n, unsigned magic, int d) {
     return d == 1 ? n : (int)__umulhi((unsigned)n, magic);
 }
 
 // the MFMA loop of one wave over one staged tile: NG (tap, ci-block) combinations x up to 3 co-blocks
 template <int NG>
-__device__ __forceinline__ void wgrad_steps(f32x4 (&acc)[WG_GROUPS][3], const float* __restrict__ dys,
+__device__ __forceinline__ void wgrad_steps(otp_f32x4 (&acc)[WG_GROUPS][3], const float* __restrict__ dys,
                                             const float* __restrict__ xs, const int* __restrict__ poff,
                                             const int (&bbase)[WG_GROUPS], int abase, int PS16, int s0, int ds, int steps,
                                             int ncob) {
@@ -122,12 +122,12 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const float* __restr
     const int ng = split_steps ? ncombo : (ncombo > wave ? (ncombo - wave + 3) >> 2 : 0);
     const int s0 = split_steps ? wave : 0, ds = split_steps ? 4 : 1;
 
-    f32x4 acc[WG_GROUPS][3];
+    otp_f32x4 acc[WG_GROUPS][3];
     int bbase[WG_GROUPS];                                 // LDS word of the input fragment of combination g, pixel offset 0
 #pragma unroll
     for (int g = 0; g < WG_GROUPS; ++g) {
 #pragma unroll
-        for (int b = 0; b < 3; ++b) acc[g][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 3; ++b) acc[g][b] = (otp_f32x4){0.f, 0.f, 0.f, 0.f};
         const int combo = split_steps ? g : wave + 4 * g;
         const int tap = combo / ncib, cib = combo - tap * ncib;
         const int ti = tap / P.KS, tj = tap - ti * P.KS;
@@ -659,13 +659,13 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_kernel(const float* __restric
     for (int j = 0; j < 3; ++j) brow[j] = ((ntile[j] * 16 + m) * P.HW + 4 * kq) * 4;
     const int tstep = 16 * P.HW * 4;                                   // next row tile
 
-    f32x4 acc[9][3];
+    otp_f32x4 acc[9][3];
 #pragma unroll
     for (int i = 0; i < 9; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    f32x4 A[9], B[3], An[9], Bn[3];
-    auto load = [&](f32x4 (&a)[9], f32x4 (&b)[3], int p0) __attribute__((always_inline)) {
+        for (int j = 0; j < 3; ++j) acc[i][j] = (otp_f32x4){0.f, 0.f, 0.f, 0.f};
+    otp_f32x4 A[9], B[3], An[9], Bn[3];
+    auto load = [&](otp_f32x4 (&a)[9], otp_f32x4 (&b)[3], int p0) __attribute__((always_inline)) {
         const bool ok = p0 + 4 * kq < p_end;                           // HW % 4 == 0: a pixel quad is inside or outside
         const int po = p0 * 4;                                         // offset -1 = past every descriptor -> zeros
 #pragma unroll
@@ -695,19 +695,19 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_kernel(const float* __restric
 #pragma unroll
         for (int j = 0; j < 3; ++j)
             if (i < nmt && j < nnt)
-                *reinterpret_cast<f32x4*>(part + ((((size_t)s * P.MT + mt0 + i) * P.NT + ntile[j]) * 64 + lane) * 4) = acc[i][j];
+                *reinterpret_cast<otp_f32x4*>(part + ((((size_t)s * P.MT + mt0 + i) * P.NT + ntile[j]) * 64 + lane) * 4) = acc[i][j];
 }
 
 // grid (tiles, 4 quarters of a tile); 256 threads = 16 float4 lanes x 16 chunk groups
 __global__ __launch_bounds__(256) void w1x1_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw, int S, int MT,
                                                            int NT, int Cout, int Cin) {
-    __shared__ f32x4 red[16][16];
+    __shared__ otp_f32x4 red[16][16];
     const int tile = blockIdx.x, mt = tile / NT, nt = tile - mt * NT;
     const int l4 = threadIdx.x & 15, sg = threadIdx.x >> 4, lane = blockIdx.y * 16 + l4;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    otp_f32x4 v = {0.f, 0.f, 0.f, 0.f};
     const size_t stride = (size_t)MT * NT * 256;
     const float* src = part + ((size_t)tile * 64 + lane) * 4;
-    for (int s = sg; s < S; s += 16) v += *reinterpret_cast<const f32x4*>(src + (size_t)s * stride);
+    for (int s = sg; s < S; s += 16) v += *reinterpret_cast<const otp_f32x4*>(src + (size_t)s * stride);
     red[sg][l4] = v;
     __syncthreads();
     if (sg == 0) {

@@ -18,8 +18,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // ---- channel LayerNorm ---------------------------------------------------------------------------
 // CREG > 0: the C <= CREG channel values of a time step are held in registers (one HBM read).
 template <int CREG>
@@ -256,25 +254,25 @@ __global__ __launch_bounds__(256) void attn_scores_kernel(const float* __restric
     const float* qb = q + (size_t)bh * hs * T;
     const float* kb = k + (size_t)bh * hs * T;
     const int t_begin = s * chunk, t_end = min(T, t_begin + chunk);
-    f32x4 acc[TPW];
+    otp_f32x4 acc[TPW];
 #pragma unroll
-    for (int i = 0; i < TPW; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < TPW; ++i) acc[i] = (otp_f32x4){0.f, 0.f, 0.f, 0.f};
     const int r16 = lane & 15, kk = lane >> 4;
     // rows are T floats apart; 16-byte vectors need T % 4 == 0 (and the chunk start is a multiple of 64)
     const bool vec = (T & 3) == 0 && ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) == 0;
-    f32x4 pq[NQ], pk[NQ];
+    otp_f32x4 pq[NQ], pk[NQ];
     auto load_tile = [&](int t0) __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
             const int idx = tid + j * 256;
             const int row = idx / (ATT_TC / 4), t = t0 + 4 * (idx - row * (ATT_TC / 4));
-            f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
+            otp_f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
             if (row < hs && idx < HSP * (ATT_TC / 4)) {
                 const float* qp = qb + (size_t)row * T + t;
                 const float* kp = kb + (size_t)row * T + t;
                 if (vec && t + 3 < t_end) {
-                    a = *reinterpret_cast<const f32x4*>(qp);
-                    b = *reinterpret_cast<const f32x4*>(kp);
+                    a = *reinterpret_cast<const otp_f32x4*>(qp);
+                    b = *reinterpret_cast<const otp_f32x4*>(kp);
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
@@ -335,9 +333,6 @@ __global__ __launch_bounds__(256) void attn_scores_kernel(const float* __restric
 // q / k tiles are split once into bf16 hi / lo images [row][64 tokens] (row pitch 144 B: an odd multiple of 16 B, so the 16
 // rows of a fragment read hit 16 distinct bank groups); a fragment is one ds_read_b128 (8 consecutive tokens of a row), a
 // 16 x 16 score tile takes 3 MFMAs per 32 tokens instead of 8 f32 ones at twice the cycles.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef otp_x3x8 sx_h16x8;
-typedef otp_x3x2 sx_h16x2;
 constexpr int SX_PITCH = ATT_TC * 2 + 16;          // bytes per LDS row
 
 template <int NB>
@@ -353,24 +348,24 @@ __global__ __launch_bounds__(256) void attn_scores_x3_kernel(const float* __rest
     const float* qb = q + (size_t)bh * hs * T;
     const float* kb = k + (size_t)bh * hs * T;
     const int t_begin = s * chunk, t_end = min(T, t_begin + chunk);
-    f32x4 acc[TPW];
+    otp_f32x4 acc[TPW];
 #pragma unroll
-    for (int i = 0; i < TPW; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < TPW; ++i) acc[i] = (otp_f32x4){0.f, 0.f, 0.f, 0.f};
     const int r16 = lane & 15, kk = lane >> 4;
     const bool vec = (T & 3) == 0 && ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) == 0;
-    f32x4 pq[NQ], pk[NQ];
+    otp_f32x4 pq[NQ], pk[NQ];
     auto load_tile = [&](int t0) __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
             const int idx = tid + j * 256;
             const int row = idx / (ATT_TC / 4), t = t0 + 4 * (idx - row * (ATT_TC / 4));
-            f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
+            otp_f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
             if (row < hs && idx < HSP * (ATT_TC / 4)) {
                 const float* qp = qb + (size_t)row * T + t;
                 const float* kp = kb + (size_t)row * T + t;
                 if (vec && t + 3 < t_end) {
-                    a = *reinterpret_cast<const f32x4*>(qp);
-                    b = *reinterpret_cast<const f32x4*>(kp);
+                    a = *reinterpret_cast<const otp_f32x4*>(qp);
+                    b = *reinterpret_cast<const otp_f32x4*>(kp);
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
@@ -381,15 +376,15 @@ __global__ __launch_bounds__(256) void attn_scores_x3_kernel(const float* __rest
             pk[j] = b;
         }
     };
-    auto split4 = [](f32x4 v, unsigned long long& hi, unsigned long long& lo) __attribute__((always_inline)) {
+    auto split4 = [](otp_f32x4 v, unsigned long long& hi, unsigned long long& lo) __attribute__((always_inline)) {
         uint32_t h[2], l[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const f32x2 a = {v[2 * i], v[2 * i + 1]};
-            const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, sx_h16x2));
-            const f32x2 af = otp_x3_widen(hb);
+            const otp_f32x2 a = {v[2 * i], v[2 * i + 1]};
+            const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, otp_x3x2));
+            const otp_f32x2 af = otp_x3_widen(hb);
             h[i] = hb;
-            l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a - af, sx_h16x2));
+            l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a - af, otp_x3x2));
         }
         hi = (unsigned long long)h[0] | ((unsigned long long)h[1] << 32);
         lo = (unsigned long long)l[0] | ((unsigned long long)l[1] << 32);
@@ -424,10 +419,10 @@ __global__ __launch_bounds__(256) void attn_scores_x3_kernel(const float* __rest
                 const int qo = (ib * 16 + r16) * SX_PITCH + kk * 16, ko = (jb * 16 + r16) * SX_PITCH + kk * 16;
 #pragma unroll
                 for (int ks = 0; ks < ATT_TC / 32; ++ks) {
-                    const sx_h16x8 a_h = *reinterpret_cast<const sx_h16x8*>(qh + qo + ks * 64);
-                    const sx_h16x8 a_l = *reinterpret_cast<const sx_h16x8*>(ql + qo + ks * 64);
-                    const sx_h16x8 b_h = *reinterpret_cast<const sx_h16x8*>(kh + ko + ks * 64);
-                    const sx_h16x8 b_l = *reinterpret_cast<const sx_h16x8*>(kl_ + ko + ks * 64);
+                    const otp_x3x8 a_h = *reinterpret_cast<const otp_x3x8*>(qh + qo + ks * 64);
+                    const otp_x3x8 a_l = *reinterpret_cast<const otp_x3x8*>(ql + qo + ks * 64);
+                    const otp_x3x8 b_h = *reinterpret_cast<const otp_x3x8*>(kh + ko + ks * 64);
+                    const otp_x3x8 b_l = *reinterpret_cast<const otp_x3x8*>(kl_ + ko + ks * 64);
                     acc[i] = OTP_X3_MFMA(a_l, b_h, acc[i], 0, 0, 0);
                     acc[i] = OTP_X3_MFMA(a_h, b_l, acc[i], 0, 0, 0);
                     acc[i] = OTP_X3_MFMA(a_h, b_h, acc[i], 0, 0, 0);
@@ -507,21 +502,21 @@ __global__ __launch_bounds__(256) void attn_pv_kernel(const float* __restrict__ 
     {
         constexpr int NP4 = (HSP * HSP / 4 + 255) / 256, NV4 = (HSP * (TT / 4) + 255) / 256;
         const bool vecv = (T & 3) == 0 && (reinterpret_cast<uintptr_t>(v) & 15) == 0;
-        f32x4 rp[NP4], rv[NV4];
+        otp_f32x4 rp[NP4], rv[NV4];
 #pragma unroll
         for (int j = 0; j < NP4; ++j) {
             const int idx = tid + j * 256;
-            rp[j] = idx < HSP * HSP / 4 ? reinterpret_cast<const f32x4*>(pb)[idx] : (f32x4){0.f, 0.f, 0.f, 0.f};
+            rp[j] = idx < HSP * HSP / 4 ? reinterpret_cast<const otp_f32x4*>(pb)[idx] : (otp_f32x4){0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
         for (int j = 0; j < NV4; ++j) {
             const int idx = tid + j * 256;
             const int row = idx / (TT / 4), t = t0 + 4 * (idx - row * (TT / 4));
-            f32x4 a = {0.f, 0.f, 0.f, 0.f};
+            otp_f32x4 a = {0.f, 0.f, 0.f, 0.f};
             if (row < hs && idx < HSP * (TT / 4)) {
                 const float* vp = vb + (size_t)row * T + t;
                 if (vecv && t + 3 < T) {
-                    a = *reinterpret_cast<const f32x4*>(vp);
+                    a = *reinterpret_cast<const otp_f32x4*>(vp);
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
@@ -544,17 +539,17 @@ __global__ __launch_bounds__(256) void attn_pv_kernel(const float* __restrict__ 
             const int idx = tid + j * 256;
             if (idx < HSP * (TT / 4)) {
                 const int row = idx / (TT / 4), tt = 4 * (idx - row * (TT / 4));
-                *reinterpret_cast<f32x4*>(vl + row * VS + tt) = rv[j];
+                *reinterpret_cast<otp_f32x4*>(vl + row * VS + tt) = rv[j];
             }
         }
     }
     __syncthreads();
     const int r16 = lane & 15, kk = lane >> 4;
-    f32x4 acc[TB][NB];
+    otp_f32x4 acc[TB][NB];
 #pragma unroll
     for (int tb = 0; tb < TB; ++tb)
 #pragma unroll
-        for (int ib = 0; ib < NB; ++ib) acc[tb][ib] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int ib = 0; ib < NB; ++ib) acc[tb][ib] = (otp_f32x4){0.f, 0.f, 0.f, 0.f};
     const float* va = vl + kk * VS + wave * (TT / 4) + r16;          // A[t][j]: lane (t = r16, k = kk)
     const float* pa = pl + r16 * PS + kk;                      // B[j][i]: lane (k = kk, i = r16)
     for (int j0 = 0; j0 < HSP; j0 += 4) {
@@ -616,15 +611,15 @@ __global__ __launch_bounds__(64 * pvx_waves(NB), 2) void attn_pv_x3_kernel(const
     const int bh = blockIdx.x, t0 = blockIdx.y * PVX_TT;
     const float* vb = v + (size_t)bh * hs * T;
     const float* pb = P + (size_t)bh * HSP * HSP;
-    auto split4 = [](f32x4 x, unsigned long long& hi, unsigned long long& lo) __attribute__((always_inline)) {
+    auto split4 = [](otp_f32x4 x, unsigned long long& hi, unsigned long long& lo) __attribute__((always_inline)) {
         uint32_t h[2], l[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const f32x2 a = {x[2 * i], x[2 * i + 1]};
-            const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, sx_h16x2));
-            const f32x2 af = otp_x3_widen(hb);
+            const otp_f32x2 a = {x[2 * i], x[2 * i + 1]};
+            const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, otp_x3x2));
+            const otp_f32x2 af = otp_x3_widen(hb);
             h[i] = hb;
-            l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a - af, sx_h16x2));
+            l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a - af, otp_x3x2));
         }
         hi = (unsigned long long)h[0] | ((unsigned long long)h[1] << 32);
         lo = (unsigned long long)l[0] | ((unsigned long long)l[1] << 32);
@@ -632,11 +627,11 @@ __global__ __launch_bounds__(64 * pvx_waves(NB), 2) void attn_pv_x3_kernel(const
     if (tid < 4) reinterpret_cast<uint32_t*>(zrec)[tid] = 0u;
     // P (HSP x HSP fp32, zero padded) -> rows of bf16 hi / lo
     {
-        f32x4 rp[NP4];
+        otp_f32x4 rp[NP4];
 #pragma unroll
         for (int j = 0; j < NP4; ++j) {
             const int idx = tid + j * PVX_TH;
-            rp[j] = idx < HSP * HSP / 4 ? reinterpret_cast<const f32x4*>(pb)[idx] : (f32x4){0.f, 0.f, 0.f, 0.f};
+            rp[j] = idx < HSP * HSP / 4 ? reinterpret_cast<const otp_f32x4*>(pb)[idx] : (otp_f32x4){0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
         for (int j = 0; j < NP4; ++j) {
@@ -657,15 +652,15 @@ __global__ __launch_bounds__(64 * pvx_waves(NB), 2) void attn_pv_x3_kernel(const
         const int idx = tid + it * PVX_TH;
         const int g = idx / (PVX_TT / 4), f4 = idx - g * (PVX_TT / 4);
         const int t = t0 + 4 * f4;
-        f32x4 x[8];
+        otp_f32x4 x[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int row = 8 * g + e;
-            f32x4 a = {0.f, 0.f, 0.f, 0.f};
+            otp_f32x4 a = {0.f, 0.f, 0.f, 0.f};
             if (idx < G * (PVX_TT / 4) && row < hs) {
                 const float* vp = vb + (size_t)row * T + t;
                 if (vecv && t + 3 < T) {
-                    a = *reinterpret_cast<const f32x4*>(vp);
+                    a = *reinterpret_cast<const otp_f32x4*>(vp);
                 } else {
 #pragma unroll
                     for (int c = 0; c < 4; ++c)
@@ -678,8 +673,8 @@ __global__ __launch_bounds__(64 * pvx_waves(NB), 2) void attn_pv_x3_kernel(const
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 unsigned long long h0, l0, h1, l1;
-                split4((f32x4){x[0][c], x[1][c], x[2][c], x[3][c]}, h0, l0);
-                split4((f32x4){x[4][c], x[5][c], x[6][c], x[7][c]}, h1, l1);
+                split4((otp_f32x4){x[0][c], x[1][c], x[2][c], x[3][c]}, h0, l0);
+                split4((otp_f32x4){x[4][c], x[5][c], x[6][c], x[7][c]}, h1, l1);
                 unsigned char* r = vrec + (4 * f4 + c) * REC + g * 16;
                 *reinterpret_cast<unsigned long long*>(r) = h0;
                 *reinterpret_cast<unsigned long long*>(r + 8) = h1;
@@ -690,27 +685,27 @@ __global__ __launch_bounds__(64 * pvx_waves(NB), 2) void attn_pv_x3_kernel(const
     }
     __syncthreads();
     const int r16 = lane & 15, kk = lane >> 4;
-    f32x4 acc[2][NB];
+    otp_f32x4 acc[2][NB];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < NB; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int nt = 0; nt < NB; ++nt) acc[mt][nt] = (otp_f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         const int kg = 4 * ks + kk;                                // 8-wide j group of this lane
         const bool kv = kg < G;
-        sx_h16x8 ah[2], al[2];
+        otp_x3x8 ah[2], al[2];
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             const unsigned char* a = kv ? vrec + ((wave * 2 + mt) * 16 + r16) * REC + kg * 16 : zrec;
-            ah[mt] = *reinterpret_cast<const sx_h16x8*>(a);
-            al[mt] = *reinterpret_cast<const sx_h16x8*>(kv ? a + HSP * 2 : zrec);
+            ah[mt] = *reinterpret_cast<const otp_x3x8*>(a);
+            al[mt] = *reinterpret_cast<const otp_x3x8*>(kv ? a + HSP * 2 : zrec);
         }
 #pragma unroll
         for (int nt = 0; nt < NB; ++nt) {
             const unsigned char* b = kv ? prec + (nt * 16 + r16) * REC + kg * 16 : zrec;
-            const sx_h16x8 b_h = *reinterpret_cast<const sx_h16x8*>(b);
-            const sx_h16x8 b_l = *reinterpret_cast<const sx_h16x8*>(kv ? b + HSP * 2 : zrec);
+            const otp_x3x8 b_h = *reinterpret_cast<const otp_x3x8*>(b);
+            const otp_x3x8 b_l = *reinterpret_cast<const otp_x3x8*>(kv ? b + HSP * 2 : zrec);
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
                 acc[mt][nt] = OTP_X3_MFMA(al[mt], b_h, acc[mt][nt], 0, 0, 0);
@@ -776,9 +771,9 @@ __global__ void upsample_linear4_kernel(const float* __restrict__ x, float* __re
     if (t4 >= To) return;
     const int c = blockIdx.y % C, b = blockIdx.y / C;
     const float* xr = x + ((size_t)b * C + c) * T;
-    f32x4 r;
+    otp_f32x4 r;
     if (f == 1) {
-        r = *reinterpret_cast<const f32x4*>(xr + t4);
+        r = *reinterpret_cast<const otp_f32x4*>(xr + t4);
     } else {
         const float inv = 1.f / (float)f;
 #pragma unroll
@@ -791,7 +786,7 @@ __global__ void upsample_linear4_kernel(const float* __restrict__ x, float* __re
             r[k] = l0 * xr[i0] + l1 * xr[i1];
         }
     }
-    *reinterpret_cast<f32x4*>(out + ((size_t)b * out_ctot + out_coff + c) * To + t4) = r;
+    *reinterpret_cast<otp_f32x4*>(out + ((size_t)b * out_ctot + out_coff + c) * To + t4) = r;
 }
 
 }  // namespace

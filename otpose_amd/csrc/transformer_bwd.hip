@@ -282,21 +282,20 @@ __global__ void dwconv3_bwd_x_kernel(const float* __restrict__ dy, const float* 
 // one-element kernel above pays two integer divisions per tap and ran at 2.2 TB/s (54 us at 16 x 136 x 6912).
 __global__ __launch_bounds__(256) void dwconv3_bwd_x_s1_kernel(const float* __restrict__ dy, const float* __restrict__ w,
                                                                 float* __restrict__ dx, int C, int T, size_t groups) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int q4 = T >> 2;
     for (size_t gidx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; gidx < groups; gidx += (size_t)gridDim.x * blockDim.x) {
         const size_t row = gidx / q4;
         const int q = (int)(gidx - row * q4), c = (int)(row % C);
         const float* dr = dy + row * T + 4 * q;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(dr);
+        const otp_f32x4 v = *reinterpret_cast<const otp_f32x4*>(dr);
         const float lft = q > 0 ? dr[-1] : 0.f, rgt = q + 1 < q4 ? dr[4] : 0.f;
         const float w0 = w[c * 3], w1 = w[c * 3 + 1], w2 = w[c * 3 + 2];
-        f32x4 o;
+        otp_f32x4 o;
         o[0] = w0 * v[1] + w1 * v[0] + w2 * lft;
         o[1] = w0 * v[2] + w1 * v[1] + w2 * v[0];
         o[2] = w0 * v[3] + w1 * v[2] + w2 * v[1];
         o[3] = w0 * rgt + w1 * v[3] + w2 * v[2];
-        *reinterpret_cast<f32x4*>(dx + row * T + 4 * q) = o;
+        *reinterpret_cast<otp_f32x4*>(dx + row * T + 4 * q) = o;
     }
 }
 
@@ -314,13 +313,12 @@ __global__ __launch_bounds__(DWW_THREADS) void dwconv3_bwd_w_kernel(const float*
     if (stride == 1 && (T & 3) == 0) {
         // rows of T = To floats, 16-byte aligned: a thread takes four consecutive time steps per pass (one float4 of dy, one of x
         // and the two neighbours), two passes in flight - the one-element loop below ran at 1.3 TB/s (91 us at 16 x 136 x 6912)
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
         const int q4 = T >> 2, groups = B * q4;
         auto one = [&](int i) __attribute__((always_inline)) {
             const int b = i / q4, t = (i - b * q4) << 2;
             const float* xr = x + ((size_t)b * C + c) * T + t;
-            const f32x4 g = *reinterpret_cast<const f32x4*>(dy + ((size_t)b * C + c) * T + t);
-            const f32x4 v = *reinterpret_cast<const f32x4*>(xr);
+            const otp_f32x4 g = *reinterpret_cast<const otp_f32x4*>(dy + ((size_t)b * C + c) * T + t);
+            const otp_f32x4 v = *reinterpret_cast<const otp_f32x4*>(xr);
             const float left = t > 0 ? xr[-1] : 0.f, right = t + 4 < T ? xr[4] : 0.f;
             s0 += g[0] * left + g[1] * v[0] + g[2] * v[1] + g[3] * v[2];
             s1 += g[0] * v[0] + g[1] * v[1] + g[2] * v[2] + g[3] * v[3];

@@ -23,13 +23,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float wino_gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
-__device__ __forceinline__ uint32_t wdiv(uint32_t i, uint32_t magic) { return magic ? __umulhi(i, magic) : i; }
-uint32_t wmagic(uint32_t d) { return d <= 1 ? 0u : (uint32_t)((1ull << 32) / d) + 1u; }
-
 constexpr int WMB = 3;            // 16-row output-channel blocks per workgroup
 constexpr int WMS = 16 * WMB;     // 48: LDS row of the weight slab (== 16 mod 32: the 4 k-rows of a fragment hit distinct banks)
 constexpr int WG_ = 4;            // guard floats in front of every channel window (column -1 of the first row)
@@ -107,13 +100,13 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const float* __restri
     const int grp = (int)blockIdx.x / per, rem = (int)blockIdx.x - grp * per;
     const int bp = grp * 8 + (rem & 7), m0 = (rem >> 3) * WMS;
     if (bp >= P.N * P.bpi) return;                                // uniform per workgroup (padding of the last group of 8)
-    const int n = (int)wdiv((uint32_t)bp, P.magicBpi);
+    const int n = (int)otp_magic_div((uint32_t)bp, P.magicBpi);
     const int bi = bp - n * P.bpi;
     // row-major run: tiles t0 .. t0 + nt - 1;  rectangle: tile rows ty0 .. ty0 + BR - 1, tile columns tx0 .. tx0 + BC - 1
     const int t0 = TWOD ? 0 : bi * NT;
     const int nt = TWOD ? NT : min(NT, P.tpi - t0);
-    const int by = TWOD ? (int)wdiv((uint32_t)bi, P.magicTXB) : 0;
-    const int ty0 = TWOD ? by * BR : (int)wdiv((uint32_t)t0, P.magicTX);
+    const int by = TWOD ? (int)otp_magic_div((uint32_t)bi, P.magicTXB) : 0;
+    const int ty0 = TWOD ? by * BR : (int)otp_magic_div((uint32_t)t0, P.magicTX);
     const int tx0 = TWOD ? (bi - by * P.TXB) * BCc : 0;
     const int f0 = (2 * ty0 - 1) * P.W;                           // first flattened input position the block touches (< 0 at the top)
     const int f0a = f0 & ~3;
@@ -126,14 +119,14 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const float* __restri
             return ty * 2 < P.H && tx * 2 < P.W;
         }
         const int t = t0 + (j < nt ? j : 0);
-        ty = (int)wdiv((uint32_t)t, P.magicTX); tx = t - ty * P.TX;
+        ty = (int)otp_magic_div((uint32_t)t, P.magicTX); tx = t - ty * P.TX;
         return j < nt;
     };
     const float* img = in + ((size_t)n * P.in_ctot + P.in_coff) * P.HW;
 
     // ---- staging ---------------------------------------------------------------------------------------------------------
     constexpr int NJI = TWOD ? NI2 : (WCK == 8 ? 6 : 8);
-    f32x4 pfi[NJI];
+    otp_f32x4 pfi[NJI];
     int goff[TWOD ? NI2 : 1], ldst[TWOD ? NI2 : 1];               // 2-D: byte offset inside the chunk's channels / LDS word
     if (TWOD) {
 #pragma unroll
@@ -191,14 +184,14 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const float* __restri
         if (TWOD) {
 #pragma unroll
             for (int j = 0; j < NI2; ++j)
-                if (ldst[j] >= 0) *reinterpret_cast<f32x4*>(raw + ldst[j]) = pfi[j];
+                if (ldst[j] >= 0) *reinterpret_cast<otp_f32x4*>(raw + ldst[j]) = pfi[j];
         } else {
             int jc = 0, jr = 0;
 #pragma unroll
             for (int j = 0; j < NJI; ++j) {
                 if (j < (WCK / 4) * P.JR) {
                     const int c = wave * (WCK / 4) + jc, r4 = lane + 64 * jr;
-                    if (r4 < P.L4) *reinterpret_cast<f32x4*>(raw + c * P.WS + WG_ + 4 * r4) = pfi[j];
+                    if (r4 < P.L4) *reinterpret_cast<otp_f32x4*>(raw + c * P.WS + WG_ + 4 * r4) = pfi[j];
                     if (++jr == P.JR) { jr = 0; ++jc; }
                 }
             }
@@ -210,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const float* __restri
     // else in the window is image data or range-check zeros, so 0 * x is exact).
     static_assert(SLOTS == 2, "the packed transform pairs two patches per thread");
     int toff[SLOTS], vdst[SLOTS];
-    f32x2 cm[4];                                                  // cm[jj] = (slot 0, slot 1) keep factors of patch column jj
+    otp_f32x2 cm[4];                                                  // cm[jj] = (slot 0, slot 1) keep factors of patch column jj
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) {
         const int i = tid + 256 * s;
@@ -234,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const float* __restri
     if (!TWOD)
         for (int c = tid; c < WCK * WG_; c += 256) raw[(c / WG_) * P.WS + (c % WG_)] = 0.f;   // guard floats
 
-    f32x4 acc[4][WMB][TB];
+    otp_f32x4 acc[4][WMB][TB];
 
     const float* Vw = V + (wave * 4) * WCK * VS + kl * VS + i16;
 
@@ -249,18 +242,18 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const float* __restri
             const int RS_ = TWOD ? WC : P.W;                       // row pitch of the staged window
             const float* s0 = raw + toff[0];
             const float* s1 = raw + toff[1];
-            f32x2 t[4][4];
+            otp_f32x2 t[4][4];
             if (WEVEN) {
                 // even W: patch columns 1, 2 of every row are an 8-byte aligned pair -> 3 LDS reads per row instead of 4, and
                 // the paired read is conflict-free (the single reads step 2 floats per lane: 2-way)
                 {                                                  // columns 1 and 2 together
-                    f32x2 e[4][2];
+                    otp_f32x2 e[4][2];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const f32x2 m0 = *reinterpret_cast<const f32x2*>(s0 + i * RS_ + 1);
-                        const f32x2 m1 = *reinterpret_cast<const f32x2*>(s1 + i * RS_ + 1);
-                        e[i][0] = (f32x2){m0[0], m1[0]} * (TWOD ? (f32x2){1.f, 1.f} : cm[1]);
-                        e[i][1] = (f32x2){m0[1], m1[1]} * (TWOD ? (f32x2){1.f, 1.f} : cm[2]);
+                        const otp_f32x2 m0 = *reinterpret_cast<const otp_f32x2*>(s0 + i * RS_ + 1);
+                        const otp_f32x2 m1 = *reinterpret_cast<const otp_f32x2*>(s1 + i * RS_ + 1);
+                        e[i][0] = (otp_f32x2){m0[0], m1[0]} * (TWOD ? (otp_f32x2){1.f, 1.f} : cm[1]);
+                        e[i][1] = (otp_f32x2){m0[1], m1[1]} * (TWOD ? (otp_f32x2){1.f, 1.f} : cm[2]);
                     }
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
@@ -272,10 +265,10 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const float* __restri
                 }
 #pragma unroll
                 for (int jj = 0; jj < 4; jj += 3) {               // columns 0 and 3
-                    const f32x2 d0 = (f32x2){s0[jj], s1[jj]} * (TWOD ? (f32x2){1.f, 1.f} : cm[jj]);
-                    const f32x2 d1 = (f32x2){s0[RS_ + jj], s1[RS_ + jj]} * (TWOD ? (f32x2){1.f, 1.f} : cm[jj]);
-                    const f32x2 d2 = (f32x2){s0[2 * RS_ + jj], s1[2 * RS_ + jj]} * (TWOD ? (f32x2){1.f, 1.f} : cm[jj]);
-                    const f32x2 d3 = (f32x2){s0[3 * RS_ + jj], s1[3 * RS_ + jj]} * (TWOD ? (f32x2){1.f, 1.f} : cm[jj]);
+                    const otp_f32x2 d0 = (otp_f32x2){s0[jj], s1[jj]} * (TWOD ? (otp_f32x2){1.f, 1.f} : cm[jj]);
+                    const otp_f32x2 d1 = (otp_f32x2){s0[RS_ + jj], s1[RS_ + jj]} * (TWOD ? (otp_f32x2){1.f, 1.f} : cm[jj]);
+                    const otp_f32x2 d2 = (otp_f32x2){s0[2 * RS_ + jj], s1[2 * RS_ + jj]} * (TWOD ? (otp_f32x2){1.f, 1.f} : cm[jj]);
+                    const otp_f32x2 d3 = (otp_f32x2){s0[3 * RS_ + jj], s1[3 * RS_ + jj]} * (TWOD ? (otp_f32x2){1.f, 1.f} : cm[jj]);
                     t[0][jj] = d0 - d2;
                     t[1][jj] = d1 + d2;
                     t[2][jj] = d2 - d1;
@@ -284,10 +277,10 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const float* __restri
             } else {
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {                   // one patch column at a time: 4 loads -> 4 results
-                    const f32x2 d0 = (f32x2){s0[jj], s1[jj]} * (TWOD ? (f32x2){1.f, 1.f} : cm[jj]);
-                    const f32x2 d1 = (f32x2){s0[RS_ + jj], s1[RS_ + jj]} * (TWOD ? (f32x2){1.f, 1.f} : cm[jj]);
-                    const f32x2 d2 = (f32x2){s0[2 * RS_ + jj], s1[2 * RS_ + jj]} * (TWOD ? (f32x2){1.f, 1.f} : cm[jj]);
-                    const f32x2 d3 = (f32x2){s0[3 * RS_ + jj], s1[3 * RS_ + jj]} * (TWOD ? (f32x2){1.f, 1.f} : cm[jj]);
+                    const otp_f32x2 d0 = (otp_f32x2){s0[jj], s1[jj]} * (TWOD ? (otp_f32x2){1.f, 1.f} : cm[jj]);
+                    const otp_f32x2 d1 = (otp_f32x2){s0[RS_ + jj], s1[RS_ + jj]} * (TWOD ? (otp_f32x2){1.f, 1.f} : cm[jj]);
+                    const otp_f32x2 d2 = (otp_f32x2){s0[2 * RS_ + jj], s1[2 * RS_ + jj]} * (TWOD ? (otp_f32x2){1.f, 1.f} : cm[jj]);
+                    const otp_f32x2 d3 = (otp_f32x2){s0[3 * RS_ + jj], s1[3 * RS_ + jj]} * (TWOD ? (otp_f32x2){1.f, 1.f} : cm[jj]);
                     t[0][jj] = d0 - d2;
                     t[1][jj] = d1 + d2;
                     t[2][jj] = d2 - d1;
@@ -299,7 +292,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const float* __restri
             const bool w1 = vdst[1] >= 0;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const f32x2 v0 = t[i][0] - t[i][2], v1 = t[i][1] + t[i][2], v2 = t[i][2] - t[i][1], v3 = t[i][1] - t[i][3];
+                const otp_f32x2 v0 = t[i][0] - t[i][2], v1 = t[i][1] + t[i][2], v2 = t[i][2] - t[i][1], v3 = t[i][1] - t[i][3];
                 q0[(i * 4 + 0) * WCK * VS] = v0[0]; q0[(i * 4 + 1) * WCK * VS] = v1[0];
                 q0[(i * 4 + 2) * WCK * VS] = v2[0]; q0[(i * 4 + 3) * WCK * VS] = v3[0];
                 if (w1) {
@@ -327,7 +320,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const float* __restri
                     for (int mb = 0; mb < WMB; ++mb)
 #pragma unroll
                         for (int tb = 0; tb < TB; ++tb) {
-                            const f32x4 cin = (FIRST && k == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[nu][mb][tb];
+                            const otp_f32x4 cin = (FIRST && k == 0) ? (otp_f32x4){0.f, 0.f, 0.f, 0.f} : acc[nu][mb][tb];
                             acc[nu][mb][tb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mb], b[tb], cin, 0, 0, 0);
                         }
                 }
@@ -390,7 +383,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const float* __restri
                     const bool two = etwo[tb];
                     if (rrow) {
                         if (two && WEVEN) {
-                            const f32x2 rv = *reinterpret_cast<const f32x2*>(rrow + o);
+                            const otp_f32x2 rv = *reinterpret_cast<const otp_f32x2*>(rrow + o);
                             y0 += rv.x; y1 += rv.y;
                         } else {
                             y0 += rrow[o];
@@ -398,9 +391,9 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const float* __restri
                         }
                     }
                     if (P.act == OTP_ACT_RELU) { y0 = fmaxf(y0, 0.f); y1 = fmaxf(y1, 0.f); }
-                    else if (P.act == OTP_ACT_GELU) { y0 = wino_gelu(y0); y1 = wino_gelu(y1); }
+                    else if (P.act == OTP_ACT_GELU) { y0 = otp_gelu_erf(y0); y1 = otp_gelu_erf(y1); }
                     if (two && WEVEN) {
-                        *reinterpret_cast<f32x2*>(orow + o) = (f32x2){y0, y1};
+                        *reinterpret_cast<otp_f32x2*>(orow + o) = (otp_f32x2){y0, y1};
                     } else {
                         orow[o] = y0;
                         if (two) orow[o + 1] = y1;
@@ -431,8 +424,8 @@ bool wino_plan(const otp_conv_desc& d, WinoPlan& P, size_t& lds, int NT, int WCK
     P.WS = WG_ + 4 * P.L4 + 4;
     if ((P.WS & 31) == 0) P.WS += 4;
     P.w_even = (d.W & 1) == 0 ? 1 : 0;
-    P.magicTX = wmagic(P.TX);
-    P.magicBpi = wmagic(P.bpi);
+    P.magicTX = otp_magic(P.TX);
+    P.magicBpi = otp_magic(P.bpi);
     const int VS = (NT % 32 == 16) ? NT : NT + 16;
     lds = ((size_t)WCK * P.WS + (size_t)16 * WCK * VS) * sizeof(float);
     const size_t ep = (size_t)4 * 2 * 16 * (NT + 2) * sizeof(float);      // epilogue tiles alias the window + V
@@ -453,8 +446,8 @@ bool wino_plan2d(const otp_conv_desc& d, WinoPlan& P, size_t& lds, int NT, int W
     P.bpi = P.TXB * ((TY + BR - 1) / BR);
     const int NR = 2 * BR + 2, GW = (2 * BC + 2 + 3 + 3) / 4;
     P.WS = NR * 4 * GW;
-    P.magicTXB = wmagic(P.TXB);
-    P.magicBpi = wmagic(P.bpi);
+    P.magicTXB = otp_magic(P.TXB);
+    P.magicBpi = otp_magic(P.bpi);
     const int VS = (NT % 32 == 16) ? NT : NT + 16;
     lds = ((size_t)WCK * P.WS + (size_t)16 * WCK * VS) * sizeof(float);
     const size_t ep = (size_t)4 * 2 * 16 * (NT + 2) * sizeof(float);

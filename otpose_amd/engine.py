@@ -11,35 +11,130 @@ residual-scale live in conv epilogues, and the 5-dilation weighted sum is folded
 Data layout: everything NCHW float32, frames of a clip stacked on the batch axis in the reference's
 order [cur | prev | next | pprev | nnext] x B (OTPose.py:317) without materialising the re-layout
 (``frame_split`` addressing in the stem conv).
+
+Which kernel runs a layer is decided by the layer's shape and by :class:`Routes`, the ``OTPOSE_*`` switches read once per engine;
+what a launch is handed is stated once, by the ``*_args`` functions of :mod:`ops` that the eager wrappers use too.
 """
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import os
 import sys
 import warnings
-from typing import Callable, List
+from typing import Callable, List, Optional, Tuple
 
 import torch
 
 from . import hip, ops
 from .ops import ACT_GELU, ACT_NONE, ACT_RELU, View
 
-BN_EPS = 1e-5
-
-
 def _pair(v):
     return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
 
 
+def plain_conv(cv, k, stride=1, pad="same", dil=1, groups=1, bias=False, cin=None, cout=None) -> bool:
+    """``cv`` is a k x k Conv2d with this stride, padding ("same": dil * (k // 2)), dilation, group count, presence of a bias and
+    (when given) channel counts.  ``None`` leaves a field untested."""
+    if pad == "same":
+        pad = (dil or 1) * (k // 2)
+    return (cv.kernel_size == (k, k) and (stride is None or cv.stride == (stride, stride))
+            and (pad is None or tuple(cv.padding) == (pad, pad)) and (dil is None or tuple(cv.dilation) == (dil, dil))
+            and (groups is None or cv.groups == groups) and (bias is None or (cv.bias is not None) == bias)
+            and (cin is None or cv.in_channels == cin) and (cout is None or cv.out_channels == cout))
+
+
+@dataclasses.dataclass(frozen=True)
+class Routes:
+    """The ``OTPOSE_*`` switches of the two inference engines, read once (:meth:`from_env`) when an engine is built.  The field
+    defaults are the defaults of the switches; every route stays reachable through its switch (tests/test_gpu_e2e.py)."""
+    use_graph: bool = True            # OTPOSE_HIP_GRAPH: replay the launch list as one captured hipGraph
+    use_winograd: bool = True         # OTPOSE_WINOGRAD: 3x3 stride-1 convs via csrc/wino.hip
+    # OTPOSE_CONV_MATH: "x3" = fp32 operands split into two bf16 pieces, three bf16 MFMAs per product, fp32 accumulate
+    # (csrc/convx.hip); "f32" = the f32 MFMA kernels only (Winograd / direct)
+    use_x3: bool = True
+    # OTPOSE_DCN_FUSED (needs x3): offset / mask convs + DCN gathers of all dilations in one launch
+    use_dcn_fused: bool = True
+    # OTPOSE_S8 (needs x3): HRNet branches (chains of BasicBlocks) on split-record activations fed by the LDS-DMA (csrc/convs.hip)
+    use_s8: bool = True
+    use_flow_fused: bool = True       # OTPOSE_FLOW_FUSED: flow-encoder blocks via csrc/flowenc.hip
+    use_small_conv: bool = True       # OTPOSE_SMALL_CONV: RSB staircase convs via csrc/conv_small.hip
+    use_fused_mlp: bool = True        # OTPOSE_FUSED_MLP: transformer MLP via csrc/mlp.hip
+    fuse_shortcut: bool = True        # OTPOSE_FUSE_SHORTCUT: layer1 shortcut folded into conv3
+    fuse_upsample: bool = True        # OTPOSE_FUSE_UPSAMPLE: a fuse row's upsampled terms in one pass
+    use_dense_cc: bool = True         # OTPOSE_DENSE_CC: q / k / v / proj via csrc/dense.hip
+    use_qkv_front: bool = True        # OTPOSE_QKV_FRONT: + dwconv / LayerNorm fused in front of them
+    use_pointx: bool = True           # OTPOSE_POINTX (needs x3): layer1's 1x1 convs via csrc/pointx.hip
+    pointx_fuse: bool = True          # OTPOSE_POINTX_FUSE: ... and the fuse layers' (any multiple of 16 input channels)
+    pointx_any: bool = False          # OTPOSE_POINTX_ANY=1 (opt-in: the RSB heads' and the final 1x1 convs too - 26.69 against
+    #                                   26.72 ms, and they leave exact fp32)
+    # OTPOSE_STREAMS: independent sub-graphs (the HRNet branches of a stage, the rows of its fuse layer, the two temporal
+    # encoders) are emitted on side HIP streams: inside the captured graph they become parallel branches, so the small-map
+    # launches (640-960 workgroups on 512 resident slots) fill each other's tails
+    multi_stream: bool = True
+    # OTPOSE_F32_TAIL (0 without x3): the last n HighResolutionModules of stage 4 and the backbone's final 1x1 conv on the exact-fp32
+    # MFMA kernels (Winograd / direct) instead of split products: the layers whose rounding reaches `rough` un-attenuated
+    # (DESIGN.md section 4)
+    f32_tail: int = 0
+    # OTPOSE_H16_TAIL: fp16 engine (engine_h16.py) - the encoders' matrix kernels also take their operands as halves rounded once
+    # (csrc/mlpx.hip, csrc/densex.hip: the *_h1 entry points); 0 keeps their split products
+    h16_tail: bool = True
+    # OTPOSE_RANGE_CHECK: range guard of the half-piece arithmetic (csrc/range.hip, csrc/common.h:75): "defer" (default) raises at
+    # the NEXT forward / at check_range() and NaN-fills this forward's heat-maps on the device; "sync" synchronises and raises in
+    # the forward that overflowed; "off" only keeps the device-side NaN fill
+    range_check: str = "defer"
+    s8_residual: bool = True          # OTPOSE_S8_RESIDUAL: a BasicBlock's residual from its input's S8 records, not a C4 fp32 image
+    s8_lazy_nchw: bool = True         # OTPOSE_S8_LAZY_NCHW: see :attr:`lazy_nchw`
+    s8_stride2: bool = True           # OTPOSE_S8_STRIDE2: stride-2 conv chains on S8 records (csrc/convs2.hip)
+    t1_s8: bool = True                # OTPOSE_T1_S8: transition1's convs read layer1's result as S8 records
+    l1_s8: bool = True                # OTPOSE_L1_S8: a Bottleneck's conv1 -> conv2 intermediate as S8 records
+    l1_pair: bool = True              # OTPOSE_L1_PAIR: a Bottleneck's conv3 and the next one's conv1 in one launch
+    stem_x3: bool = True              # OTPOSE_STEM_X3: the stem's first conv via csrc/stem.hip
+    chain_modules: bool = True        # OTPOSE_CHAIN_MODULES: consecutive modules of a stage chained stream by stream
+    up_any_width: bool = True         # OTPOSE_UP_ANY_WIDTH: otp_upsample_add for widths that are no multiple of 4
+    # development aids
+    conv_log: bool = False            # OTPOSE_CONV_LOG: one line per emitted convolution
+    poison: Optional[Tuple[int, int]] = None   # OTPOSE_POISON="lo:hi": NaN-fill the activation buffers with these indices
+    te_serial: bool = False           # OTPOSE_TE_SERIAL=1: both temporal encoders on the main stream
+
+    @classmethod
+    def from_env(cls) -> "Routes":
+        env = os.environ.get
+        on = lambda name: env("OTPOSE_" + name, "1") != "0"                         # noqa: E731
+        x3 = env("OTPOSE_CONV_MATH", "x3") != "f32"
+        poison = env("OTPOSE_POISON")
+        return cls(use_graph=on("HIP_GRAPH"), use_winograd=on("WINOGRAD"), use_x3=x3, use_dcn_fused=x3 and on("DCN_FUSED"),
+                   use_s8=x3 and on("S8"), use_flow_fused=on("FLOW_FUSED"), use_small_conv=on("SMALL_CONV"),
+                   use_fused_mlp=on("FUSED_MLP"), fuse_shortcut=on("FUSE_SHORTCUT"), fuse_upsample=on("FUSE_UPSAMPLE"),
+                   use_dense_cc=on("DENSE_CC"), use_qkv_front=on("QKV_FRONT"), use_pointx=x3 and on("POINTX"),
+                   pointx_fuse=on("POINTX_FUSE"), pointx_any=env("OTPOSE_POINTX_ANY", "0") == "1", multi_stream=on("STREAMS"),
+                   f32_tail=int(env("OTPOSE_F32_TAIL", "0")) if x3 else 0, h16_tail=on("H16_TAIL"),
+                   range_check=env("OTPOSE_RANGE_CHECK", "defer"), s8_residual=on("S8_RESIDUAL"), s8_lazy_nchw=on("S8_LAZY_NCHW"),
+                   s8_stride2=on("S8_STRIDE2"), t1_s8=on("T1_S8"), l1_s8=on("L1_S8"), l1_pair=on("L1_PAIR"), stem_x3=on("STEM_X3"),
+                   chain_modules=on("CHAIN_MODULES"), up_any_width=on("UP_ANY_WIDTH"), conv_log=bool(env("OTPOSE_CONV_LOG")),
+                   poison=tuple(int(v) for v in poison.split(":")) if poison else None, te_serial=env("OTPOSE_TE_SERIAL") == "1")
+
+    @property
+    def lazy_nchw(self) -> bool:
+        """A tensor that also exists as S8 records gets its NCHW form written only if some consumer asks for it before the first
+        launch (``InferenceEngine._needs_nchw``); needs the S8 residual - the C4 residual chain reads the NCHW-born images."""
+        return self.s8_residual and self.s8_lazy_nchw
+
+
+class Aux:
+    """The S8 / C4 images of an NCHW activation written by its producer, and whether any consumer reads the NCHW tensor itself."""
+    __slots__ = ("s8", "c4", "nchw_needed")
+
+    def __init__(self, s8=None, c4=None, nchw_needed=False):
+        self.s8, self.c4, self.nchw_needed = s8, c4, nchw_needed
+
+
 class InferenceEngine:
+    h16 = False
+
     def __init__(self, model, batch: int, device, use_graph: bool | None = None, stream_set: int = 0, inp=None, margin=None):
-        device = torch.device(device)
-        if device.type != "cuda" or not torch.cuda.is_available():
-            raise RuntimeError("otpose_amd.OTPose runs on an MI355X through libotpose_hip.so; "
-                               f"got device '{device}' (there is no CPU or PyTorch-op fallback)")
-        self.lib = hip.lib()
-        self.dev = device
+        routes = Routes.from_env()
+        self._init(device, routes, routes.use_graph if use_graph is None else use_graph, stream_set)
         self.B = batch
         self.model = model
         cfg = model.cfg
@@ -47,55 +142,31 @@ class InferenceEngine:
         self.F = getattr(model, "window_frames", 5)             # frames per clip window
         self.W_img, self.H_img = cfg.MODEL.IMAGE_SIZE
         self.h, self.w = model.pe_h, model.pe_w
-        self.ops: List[Callable] = []
-        self._pair_s8 = {}                    # id(NCHW tensor) -> S8 image of the next Bottleneck's conv1, written with it (pointx_pair)
-        self.l1_pairs = 0                     # conv3 + next conv1 pair launches emitted (tests)
-        self._aux = {}                        # id(NCHW tensor) -> {"s8", "c4", "nchw_needed"}: S8 / C4 images written by its producer
-        self._keep = []                       # parameter-derived tensors that must outlive the ops
-        self._bufs = []                       # every activation buffer (see new())
-        self._stream = None
-        if use_graph is None:
-            use_graph = os.environ.get("OTPOSE_HIP_GRAPH", "1") != "0"
-        self.use_graph = use_graph
-        self.use_winograd = os.environ.get("OTPOSE_WINOGRAD", "1") != "0"     # 3x3 stride-1 convs via csrc/wino.hip
-        # conv products: "x3" = fp32 operands split into two bf16 pieces, three bf16 MFMAs per product, fp32 accumulate
-        # (csrc/convx.hip); "f32" = the f32 MFMA kernels only (Winograd / direct)
-        self.use_x3 = os.environ.get("OTPOSE_CONV_MATH", "x3") != "f32"
-        # offset / mask convs + DCN gathers of all dilations in one launch (split-half products for the convs)
-        self.use_dcn_fused = self.use_x3 and os.environ.get("OTPOSE_DCN_FUSED", "1") != "0"
-        # HRNet branches (chains of BasicBlocks) on split-record activations fed by the LDS-DMA (csrc/convs.hip)
-        self.use_s8 = self.use_x3 and os.environ.get("OTPOSE_S8", "1") != "0"
-        self.use_flow_fused = os.environ.get("OTPOSE_FLOW_FUSED", "1") != "0"       # flow-encoder blocks via csrc/flowenc.hip
-        self.use_small_conv = os.environ.get("OTPOSE_SMALL_CONV", "1") != "0"       # RSB staircase convs via csrc/conv_small.hip
-        self.use_fused_mlp = os.environ.get("OTPOSE_FUSED_MLP", "1") != "0"   # transformer MLP via csrc/mlp.hip
-        self.fuse_shortcut = os.environ.get("OTPOSE_FUSE_SHORTCUT", "1") != "0"  # layer1 shortcut folded into conv3
-        self.fuse_upsample = os.environ.get("OTPOSE_FUSE_UPSAMPLE", "1") != "0"  # a fuse row's upsampled terms in one pass
-        self.use_dense_cc = os.environ.get("OTPOSE_DENSE_CC", "1") != "0"     # q / k / v / proj via csrc/dense.hip
-        self.use_qkv_front = os.environ.get("OTPOSE_QKV_FRONT", "1") != "0"   # + dwconv / LayerNorm fused in front of them
-        self.use_pointx = self.use_x3 and os.environ.get("OTPOSE_POINTX", "1") != "0"   # layer1's 1x1 convs via csrc/pointx.hip
-        # independent sub-graphs (the HRNet branches of a stage, the rows of its fuse layer, the two temporal encoders) are
-        # emitted on side HIP streams: inside the captured graph they become parallel branches, so the small-map launches
-        # (640-960 workgroups on 512 resident slots) fill each other's tails
-        self.multi_stream = os.environ.get("OTPOSE_STREAMS", "1") != "0"
-        # the last OTPOSE_F32_TAIL HighResolutionModules of stage 4 and the backbone's final 1x1 conv on the exact-fp32 MFMA kernels
-        # (Winograd / direct) instead of split products: the layers whose rounding reaches `rough` un-attenuated
-        self.f32_tail = int(os.environ.get("OTPOSE_F32_TAIL", "0")) if self.use_x3 else 0
-        self._exact = False
-        self._sid = 0
-        # fp16 engine (engine_h16.py): the encoders' matrix kernels also take their operands as halves rounded once (csrc/mlpx.hip,
-        # csrc/densex.hip: the *_h1 entry points); OTPOSE_H16_TAIL=0 keeps their split products
-        self.half_products = bool(getattr(self, "h16", False)) and self.use_x3 and os.environ.get("OTPOSE_H16_TAIL", "1") != "0"
-        # range guard of the half-piece arithmetic (csrc/range.hip, csrc/common.h:75): "defer" (default) raises at the NEXT
-        # forward / at check_range() and NaN-fills this forward's heat-maps on the device; "sync" synchronises and raises in the
-        # forward that overflowed; "off" only keeps the device-side NaN fill
-        self.range_check = os.environ.get("OTPOSE_RANGE_CHECK", "defer")
-        # process-wide pool (see hip.side_streams); stream_set > 0: the streams of another sub-batch of a PipelinedEngine
-        self._side = hip.side_streams(device, 3, 4 * stream_set) if self.multi_stream else []
         self._given = (inp, margin)
-        self.graph = None
         self.param_version = self._param_version()
         with torch.no_grad():
             self._build()
+
+    def _init(self, device, routes: Routes, use_graph: bool, stream_set: int = 0):
+        """State shared by a full engine and a :meth:`bare` one."""
+        device = torch.device(device)
+        if device.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("otpose_amd.OTPose runs on an MI355X through libotpose_hip.so; "
+                               f"got device '{device}' (there is no CPU or PyTorch-op fallback)")
+        self.lib, self.dev, self.routes = hip.lib(), device, routes
+        self.model, self.B, self.inp, self.margin = None, 0, None, None
+        self.ops: List[Callable] = []
+        self._pair_s8 = {}                    # id(NCHW tensor) -> S8 image of the next Bottleneck's conv1, written with it (pointx_pair)
+        self.l1_pairs = 0                     # conv3 + next conv1 pair launches emitted (tests)
+        self._aux = {}                        # id(NCHW tensor) -> Aux: S8 / C4 images written by its producer
+        self._keep = []                       # parameter-derived tensors that must outlive the ops
+        self._bufs = []                       # every activation buffer (see new())
+        self._stream = None
+        self.use_graph, self.graph = use_graph, None
+        self._exact = False                   # this part of the backbone runs on the exact-fp32 kernels (Routes.f32_tail)
+        self._sid = 0
+        # process-wide pool (see hip.side_streams); stream_set > 0: the streams of another sub-batch of a PipelinedEngine
+        self._side = hip.side_streams(device, 3, 4 * stream_set) if routes.multi_stream else []
 
     @classmethod
     def bare(cls, device, multi_stream=False):
@@ -104,33 +175,26 @@ class InferenceEngine:
         stream is the launch stream) and runs the list with :meth:`_launch_all` - exactly the launches a full engine would
         issue for that module, without building an OTPose around it.  Never captures a graph."""
         self = cls.__new__(cls)
-        device = torch.device(device)
-        if device.type != "cuda" or not torch.cuda.is_available():
-            raise RuntimeError("InferenceEngine.bare needs the GPU (there is no CPU or PyTorch-op fallback)")
-        env = os.environ.get
-        self.lib, self.dev, self.model, self.B = hip.lib(), device, None, 0
-        self.ops, self._aux, self._keep, self._bufs, self._stream = [], {}, [], [], None
-        self.use_graph, self.graph = False, None
-        self.use_winograd = env("OTPOSE_WINOGRAD", "1") != "0"
-        self.use_x3 = env("OTPOSE_CONV_MATH", "x3") != "f32"
-        self.use_dcn_fused = self.use_x3 and env("OTPOSE_DCN_FUSED", "1") != "0"
-        self.use_s8 = self.use_x3 and env("OTPOSE_S8", "1") != "0"
-        self.use_flow_fused = env("OTPOSE_FLOW_FUSED", "1") != "0"
-        self.use_small_conv = env("OTPOSE_SMALL_CONV", "1") != "0"
-        self.use_fused_mlp = env("OTPOSE_FUSED_MLP", "1") != "0"
-        self.fuse_shortcut = env("OTPOSE_FUSE_SHORTCUT", "1") != "0"
-        self.fuse_upsample = env("OTPOSE_FUSE_UPSAMPLE", "1") != "0"
-        self.use_dense_cc = env("OTPOSE_DENSE_CC", "1") != "0"
-        self.use_qkv_front = env("OTPOSE_QKV_FRONT", "1") != "0"
-        self.use_pointx = self.use_x3 and env("OTPOSE_POINTX", "1") != "0"
-        self.multi_stream = bool(multi_stream)
-        self.f32_tail, self._exact = 0, False
-        self._sid = 0
-        self.half_products = False
-        self.range_check = env("OTPOSE_RANGE_CHECK", "defer")
-        self._side = hip.side_streams(device, 3, 0) if self.multi_stream else []
-        self.inp = None
+        self._init(device, dataclasses.replace(Routes.from_env(), multi_stream=bool(multi_stream)), use_graph=False)
         return self
+
+    # ---- routes: what callers and tests read, and the conditions that combine a route with the per-module ``_exact`` state ------
+    use_x3 = property(lambda self: self.routes.use_x3)
+    use_dcn_fused = property(lambda self: self.routes.use_dcn_fused)
+    multi_stream = property(lambda self: self.routes.multi_stream)
+    f32_tail = property(lambda self: self.routes.f32_tail)
+    range_check = property(lambda self: self.routes.range_check)
+    half_products = property(lambda self: self.h16 and self.routes.use_x3 and self.routes.h16_tail)
+
+    @property
+    def s8_here(self) -> bool:
+        """Split-record (S8) kernels for the layer being emitted."""
+        return self.routes.use_s8 and not self._exact
+
+    @property
+    def s2_here(self) -> bool:
+        """Stride-2 conv chains on S8 records for the layer being emitted."""
+        return self.routes.use_s8 and not self._exact and self.routes.s8_stride2
 
     # ---------------------------------------------------------------------------------------------
     def matches(self, x) -> bool:
@@ -159,11 +223,9 @@ class InferenceEngine:
         """A static activation / scratch buffer.  The engine owns it for its whole life: the launch list holds
         raw device pointers, and torch.cuda.graph() empties the allocator cache before capturing."""
         t = torch.empty(shape, dtype=torch.float32, device=self.dev)
-        rng = os.environ.get("OTPOSE_POISON")                  # development aid ("lo:hi"): NaN-fill the buffers with these indices to
-        if rng:                                                # find a kernel that reads memory nothing wrote (tools/poison_engine.py)
-            lo, hi = (int(v) for v in rng.split(":"))
-            if lo <= len(self._bufs) < hi:
-                t.fill_(float("nan"))
+        rng = self.routes.poison                               # development aid: find a kernel that reads memory nothing wrote
+        if rng and rng[0] <= len(self._bufs) < rng[1]:         # (tools/poison_engine.py)
+            t.fill_(float("nan"))
         self._bufs.append(t)
         return t
 
@@ -213,102 +275,101 @@ class InferenceEngine:
         """Ops emitted from now on go to side stream ``sid`` (0 = main; ids past the pool fall back to main)."""
         self._sid = sid if (self.multi_stream and 0 <= sid <= len(self._side)) else 0
 
+    def call(self, fn, name, *args):
+        """Record one launch: ``args`` (an ``ops.*_args`` tuple) are fixed now, the stream is the one the op is replayed on."""
+        def run():
+            hip.check(fn(*args, self._stream), name)
+        self._emit(run)
+
+    def call_lazy_nchw(self, aux: Aux, fn, name, args_of, unpack=None):
+        """Record one launch whose NCHW output pointer is decided at the first launch: ``args_of(nchw)`` states its arguments
+        with (True) and without (False) that pointer, and the tensor is written only if a consumer has asked for it by then
+        (:meth:`_needs_nchw`).  ``unpack``: the arguments of an ``otp_s8_unpack`` pass behind a launch that cannot write the
+        NCHW tensor itself."""
+        full, lean = args_of(True), args_of(False)
+        if unpack is None:
+            def run():
+                hip.check(fn(*(full if aux.nchw_needed else lean), self._stream), name)
+        else:
+            s8_unpack = self.lib.otp_s8_unpack
+
+            def run():
+                hip.check(fn(*lean, self._stream), name)
+                if aux.nchw_needed:                         # (a consumer without an S8 path: hi + lo back to fp32 NCHW)
+                    hip.check(s8_unpack(*unpack, self._stream), "otp_s8_unpack")
+        self._emit(run)
+
+    def _bn_fold(self, bn, bias=None):
+        """BatchNorm (eval) as a per-channel scale and shift, a conv bias in front of it folded into the shift."""
+        g, b = self.dev_param(bn.weight), self.dev_param(bn.bias)
+        mu, var = self.dev_param(bn.running_mean), self.dev_param(bn.running_var)
+        sc = (g / torch.sqrt(var + bn.eps)).contiguous()
+        sh = b - mu * sc
+        if bias is not None:
+            sh = sh + self.dev_param(bias) * sc
+        sh = sh.contiguous()
+        self._keep += [sc, sh]
+        return sc, sh
+
     def conv(self, inp: View, weight, out: View, stride=1, pad=0, dil=1, bn=None, bias=None, act=ACT_NONE,
              res: View = None, in2: View = None, res_up=1, frame_split=0, cin=None, scale=None, shift=None):
         """Emit act(scale*conv(inp (+in2)) + shift (+res)) with BN / bias folded into scale / shift."""
         for v_ in (inp, in2, res):
             self._needs_nchw(v_)
+        r = self.routes
         w = self.dev_param(weight)
         if w.dim() == 3:
             w = w.unsqueeze(-1)
         cout, cin_w, kh, kw = w.shape
         if bn is not None:
-            g, b = self.dev_param(bn.weight), self.dev_param(bn.bias)
-            mu, var = self.dev_param(bn.running_mean), self.dev_param(bn.running_var)
-            sc = g / torch.sqrt(var + bn.eps)
-            sh = b - mu * sc
-            if bias is not None:
-                sh = sh + self.dev_param(bias) * sc
+            sc, sh = self._bn_fold(bn, bias)
         else:
             sc = self.dev_param(scale) if scale is not None else None
-            sh = self.dev_param(bias) if bias is not None else None
-            if shift is not None:
-                sh = self.dev_param(shift)
-        if sc is not None:
-            sc = sc.contiguous()
-            self._keep.append(sc)
-        if sh is not None:
-            sh = sh.contiguous()
-            self._keep.append(sh)
+            sh = shift if shift is not None else bias
+            sh = self.dev_param(sh) if sh is not None else None
         d = ops.conv_desc(inp, out, cout, kh, kw, stride, pad, dil, act, in2, res, res_up, frame_split, cin)
         self._keep.append(d)
         L = self.lib
-        if os.environ.get("OTPOSE_CONV_LOG"):                       # development aid: one line per emitted convolution
-            route = ("x3" if self.use_x3 and in2 is None and (kh, kw) in ((3, 3), (1, 1)) and ops.x3_supported(d) else
-                     "wino" if self.use_winograd and in2 is None and self.winograd_pays(cin_w, cout) and ops.wino_supported(d)
+        if r.conv_log:                                              # development aid: one line per emitted convolution
+            route = ("x3" if r.use_x3 and in2 is None and (kh, kw) in ((3, 3), (1, 1)) and ops.x3_supported(d) else
+                     "wino" if r.use_winograd and in2 is None and self.winograd_pays(cin_w, cout) and ops.wino_supported(d)
                      else "direct")
             print(f"conv {d.N}x{d.Cin}->{cout} k{kh} s{stride} p{pad} d{dil} {d.H}x{d.W} in2={in2 is not None} "
                   f"res={res is not None} up={res_up} fs={frame_split} {route}", file=sys.stderr)
-        if self.use_small_conv and in2 is not None and res is None and (kh, kw) == (3, 3) and ops.small_conv_supported(d):
+        if r.use_small_conv and in2 is not None and res is None and (kh, kw) == (3, 3) and ops.small_conv_supported(d):
             # RSB staircase convs (a few channels, pre-added second input): one thread per pixel, exact fp32 (csrc/conv_small.hip)
             wc = ops.pack_small_conv_weight(w)
             self._keep.append(wc)
-            sargs = (hip.ptr(inp.t), hip.ptr(in2.t), hip.ptr(wc), hip.ptr(sc), hip.ptr(sh), hip.ptr(out.t), d)
-
-            def run_small():
-                hip.check(L.otp_conv3x3_small(*sargs, self._stream), "otp_conv3x3_small")
-            self._emit(run_small)
+            self.call(L.otp_conv3x3_small, "otp_conv3x3_small", *ops.conv3x3_small_args(inp, in2, wc, sc, sh, out, d))
             return out
-        if (self.use_pointx and not self._exact and in2 is None and (kh, kw) == (1, 1) and stride == 1 and pad == 0 and res_up <= 1 and not frame_split
-                and act in (ACT_NONE, ACT_RELU) and inp.C == cin_w
-                and (cin_w in (64, 128, 256) or (os.environ.get("OTPOSE_POINTX_FUSE", "1") != "0" and cin_w % 16 == 0)
-                     or os.environ.get("OTPOSE_POINTX_ANY", "0") == "1")       # (opt-in: the RSB heads' and the final 1x1 convs too -
-                                                                              #  26.69 against 26.72 ms, and they leave exact fp32)
+        if (r.use_pointx and not self._exact and in2 is None and (kh, kw) == (1, 1) and stride == 1 and pad == 0 and res_up <= 1
+                and not frame_split and act in (ACT_NONE, ACT_RELU) and inp.C == cin_w
+                and (cin_w in (64, 128, 256) or (r.pointx_fuse and cin_w % 16 == 0) or r.pointx_any)
                 and ops.pointwise_x3_supported(cin_w, cout, inp.t.shape[2] * inp.t.shape[3])):
             # HRNet layer1's and the fuse layers' 1x1 convs (<= 256 channels in and out): register-resident pixels, streamed weights
             # (csrc/pointx.hip) - bound by their HBM streams, which the implicit-GEMM kernel ran at a third of the rate
             pk = ops.pack_pointwise_x3(w, sc, sh)
             self._keep.append(pk)
-            pargs = (hip.ptr(inp.t), hip.ptr(pk), hip.ptr(res.t if res is not None else None), hip.ptr(out.t), inp.t.shape[0],
-                     cin_w, cout, inp.t.shape[2] * inp.t.shape[3], inp.ctot, inp.coff, res.ctot if res is not None else 0,
-                     res.coff if res is not None else 0, out.ctot, out.coff, int(act == ACT_RELU))
-
-            def run_px():
-                hip.check(L.otp_pointwise_x3(*pargs, self._stream), "otp_pointwise_x3")
-            self._emit(run_px)
+            self.call(L.otp_pointwise_x3, "otp_pointwise_x3", *ops.pointwise_x3_args(inp, pk, out, res, act == ACT_RELU))
             return out
-        if self.use_x3 and not self._exact and in2 is None and (kh, kw) in ((3, 3), (1, 1)) and ops.x3_supported(d):
+        if r.use_x3 and not self._exact and in2 is None and (kh, kw) in ((3, 3), (1, 1)) and ops.x3_supported(d):
             # 3x3 / stride 1 with Cin % 16 == 0: split-half (f16x3) products on the 16-bit matrix cores, fp32 storage and
             # accumulation (csrc/convx.hip); the per-channel scale is folded into the packed weights
             e = ops.x3_weight_exponent(w, sc)         # weights stored times 2^e, the sum multiplied by 2^-e (otp_conv_desc.out_scale)
             d.out_scale = 2.0 ** -e
             xp = ops.pack_x3_weight(w, sc, stride, e)
             self._keep.append(xp)
-            xargs = (hip.ptr(inp.t), hip.ptr(xp), hip.ptr(sh), hip.ptr(res.t if res is not None else None), hip.ptr(out.t), d)
-
-            def run_x3():
-                hip.check(L.otp_conv2d_x3(*xargs, self._stream), "otp_conv2d_x3")
-            self._emit(run_x3)
+            self.call(L.otp_conv2d_x3, "otp_conv2d_x3", *ops.conv2d_x3_args(inp, xp, sh, out, d, res))
             return out
-        if self.use_winograd and in2 is None and self.winograd_pays(cin_w, cout) and ops.wino_supported(d):
+        if r.use_winograd and in2 is None and self.winograd_pays(cin_w, cout) and ops.wino_supported(d):
             # 3x3 / stride 1 / pad 1 with enough channels: Winograd F(2x2,3x3) kernel (csrc/wino.hip), same epilogue
             up = ops.pack_wino_weight(w)
             self._keep.append(up)
-            wargs = (hip.ptr(inp.t), hip.ptr(up), hip.ptr(sc), hip.ptr(sh), hip.ptr(res.t if res is not None else None),
-                     hip.ptr(out.t), d)
-
-            def run_wino():
-                hip.check(L.otp_conv2d_wino(*wargs, self._stream), "otp_conv2d_wino")
-            self._emit(run_wino)
+            self.call(L.otp_conv2d_wino, "otp_conv2d_wino", *ops.conv2d_wino_args(inp, up, sc, sh, out, d, res))
             return out
         wp = ops.pack_conv_weight(w)
         self._keep.append(wp)
-        args = (hip.ptr(inp.t), hip.ptr(in2.t if in2 is not None else None), hip.ptr(wp), hip.ptr(sc), hip.ptr(sh),
-                hip.ptr(res.t if res is not None else None), hip.ptr(out.t), d)
-
-        def run():
-            hip.check(L.otp_conv2d(*args, self._stream), "otp_conv2d")
-        self._emit(run)
+        self.call(L.otp_conv2d, "otp_conv2d", *ops.conv2d_args(inp, wp, sc, sh, out, d, in2, res))
         return out
 
     def conv_bn(self, inp: View, conv_mod, bn_mod, act=ACT_NONE, res=None, out=None, res_up=1, **kw):
@@ -332,11 +393,6 @@ class InferenceEngine:
         fn = (self.lib.otp_dense_h1 if self.half_products else self.lib.otp_dense_x3) if x3 else self.lib.otp_dense_cc
         self.call(fn, "otp_dense_cc", ax, ap, ar, ao, len(xs), B, C, T)
 
-    def call(self, fn, name, *args):
-        def run():
-            hip.check(fn(*args, self._stream), name)
-        self._emit(run)
-
     # ---- HRNet (reference model/HRNet.py:116-152) -------------------------------------------------
     def basic_block(self, blk, x: View) -> View:
         y = self.conv_bn(x, blk.conv1, blk.bn1, ACT_RELU)
@@ -349,41 +405,34 @@ class InferenceEngine:
         """A consumer reads the NCHW tensor of ``v``: its producer must write it (see fuse_s8)."""
         a = self._aux.get(id(v.t)) if v is not None else None
         if a is not None:
-            a["nchw_needed"] = True
+            a.nchw_needed = True
 
     def fuse_s8(self, lows, factors, res: View, tgt: View):
         """Last op of a fuse row whose tail is upsampled terms (HRNet.py:487-494): relu(res + up(low0) + ...) written as the
         S8 and C4 images the next module's branch reads (csrc/convs.hip, otp_s8_upsample_add); the NCHW tensor ``tgt`` is
         written only if some other consumer asks for it before the first launch.  Returns False when the row is not eligible."""
         n_, c_, hh, wh = tgt.t.shape
-        if not self.use_s8 or self._exact or tgt.coff != 0 or tgt.C != c_ or c_ % 16 or wh % 4 or (hh * wh) % 4:
+        if not self.s8_here or tgt.coff != 0 or tgt.C != c_ or c_ % 16 or wh % 4 or (hh * wh) % 4:
             return False
         if not ops.s8_conv_supported(ops.s8_conv_desc(n_, c_, c_, hh, wh, ACT_RELU)):
             return False
-        s8_res = os.environ.get("OTPOSE_S8_RESIDUAL", "1") != "0"
-        lazy = s8_res and os.environ.get("OTPOSE_S8_LAZY_NCHW", "1") != "0"
+        r = self.routes
         # the identity term: the S8 image of `res` when its producer wrote one (a branch output: hi + lo of the records, 2^-22) -
         # `res` then needs no NCHW tensor on this account - else the fp32 NCHW tensor
-        raux = self._aux.get(id(res.t)) if (lazy and res.coff == 0 and res.C == c_ and res.ctot == c_) else None
-        res_img = raux.get("s8") if raux is not None else None
+        raux = self._aux.get(id(res.t)) if (r.lazy_nchw and res.coff == 0 and res.C == c_ and res.ctot == c_) else None
+        res_img = raux.s8 if raux is not None else None
         if res_img is None:
             self._needs_nchw(res)
         # (the C4 fp32 image only when the next module's branch reads its residual from it: OTPOSE_S8_RESIDUAL=0)
         s8 = self.new(n_ * c_ * hh * wh)
-        c4 = None if s8_res else self.new(n_ * c_ * hh * wh)
-        aux = {"s8": s8, "c4": c4, "nchw_needed": False}
-        self._aux[id(tgt.t)] = aux
+        c4 = None if r.s8_residual else self.new(n_ * c_ * hh * wh)
+        aux = self._aux[id(tgt.t)] = Aux(s8, c4)
         lp = (ctypes.c_void_p * len(lows))(*[hip.ptr(v.t) for v in lows])
         fp = (ctypes.c_int * len(lows))(*factors)
         self._keep += [lp, fp]
-        L = self.lib
-        args = (lp, fp, len(lows), hip.ptr(res_img if res_img is not None else res.t), int(res_img is not None))
-        tail = (hip.ptr(s8), hip.ptr(c4), n_, c_, hh, wh, 1, res.ctot, res.coff, tgt.ctot, tgt.coff)
-
-        def run():
-            hip.check(L.otp_s8_upsample_add_ex(*args, hip.ptr(tgt.t) if aux["nchw_needed"] else None, *tail, self._stream),
-                      "otp_s8_upsample_add")
-        self._emit(run)
+        self.call_lazy_nchw(aux, self.lib.otp_s8_upsample_add_ex, "otp_s8_upsample_add", lambda nchw: (
+            lp, fp, len(lows), hip.ptr(res_img if res_img is not None else res.t), int(res_img is not None),
+            hip.ptr(tgt.t) if nchw else None, hip.ptr(s8), hip.ptr(c4), n_, c_, hh, wh, 1, res.ctot, res.coff, tgt.ctot, tgt.coff))
         return True
 
     def s8_image(self, v: View, want_c4=False):
@@ -391,20 +440,20 @@ class InferenceEngine:
         ``otp_s8_pack`` pass emitted here, on the current stream, and cached for later consumers.  None when the tensor is not
         eligible (channel slice, channels % 16, pixels % 4)."""
         n, c, h, w = v.t.shape
-        if not self.use_s8 or v.coff != 0 or v.C != c or c % 16 or (h * w) % 4:
+        if not self.routes.use_s8 or v.coff != 0 or v.C != c or c % 16 or (h * w) % 4:
             return None
         aux = self._aux.get(id(v.t))
-        if aux is not None and "s8" in aux and (not want_c4 or aux.get("c4") is not None):
+        if aux is not None and aux.s8 is not None and (not want_c4 or aux.c4 is not None):
             return aux
         self._needs_nchw(v)
-        s8 = aux["s8"] if aux is not None and "s8" in aux else self.new(n * c * h * w)
+        s8 = aux.s8 if aux is not None and aux.s8 is not None else self.new(n * c * h * w)
         c4 = self.new(n * c * h * w) if want_c4 else None
         self.call(self.lib.otp_s8_pack, "otp_s8_pack", hip.ptr(v.t), hip.ptr(s8), hip.ptr(c4), n, c, h, w, v.ctot, v.coff)
         if aux is None:
-            aux = self._aux[id(v.t)] = {"nchw_needed": True}
-        aux["s8"] = s8
+            aux = self._aux[id(v.t)] = Aux(nchw_needed=True)
+        aux.s8 = s8
         if c4 is not None:
-            aux["c4"] = c4
+            aux.c4 = c4
         return aux
 
     def s2_chain_s8(self, layers, x: View, act_last, res: View = None, out: View = None):
@@ -412,7 +461,7 @@ class InferenceEngine:
         transition layer's new branch, :213-229) on S8 records (csrc/convs2.hip): every intermediate exists only as its S8 image,
         the last layer writes act(conv + shift (+ res)) into the fp32 NCHW tensor ``out``.  ``layers`` = [(conv, bn, relu)].
         Returns the output view, or None (nothing emitted) when a layer is not of that shape."""
-        if not (self.use_s8 and not self._exact and os.environ.get("OTPOSE_S8_STRIDE2", "1") != "0"):
+        if not self.s2_here:
             return None
         n, c, h, w = x.t.shape
         if x.coff != 0 or x.C != c:
@@ -421,8 +470,7 @@ class InferenceEngine:
         descs = []
         for li, (cv, bn, relu) in enumerate(layers):
             last = li == len(layers) - 1
-            if (cv.kernel_size != (3, 3) or cv.stride != (2, 2) or cv.padding != (1, 1) or cv.dilation != (1, 1) or cv.bias is not None
-                    or cv.groups != 1 or cv.in_channels != cin or hh % 2 or ww % 2):
+            if not plain_conv(cv, 3, stride=2, cin=cin) or hh % 2 or ww % 2:
                 return None
             co = cv.out_channels
             if last:
@@ -439,39 +487,46 @@ class InferenceEngine:
         if aux is None:
             return None
         self._needs_nchw(res)
-        L = self.lib
-        cur = aux["s8"]
-        hh, ww, cin = h, w, c
-        for li, ((cv, bn, relu), d) in enumerate(zip(layers, descs)):
-            last = li == len(layers) - 1
-            sc, sh = self._bn_fold(bn)
-            wp = self._pack_s8(cv, sc, d)
-            self._keep += [wp, d]
-            if last:
-                self.call(L.otp_conv3x3_s2_s8, "otp_conv3x3_s2_s8", hip.ptr(cur), hip.ptr(wp), hip.ptr(sh),
-                          hip.ptr(res.t) if res is not None else None, hip.ptr(out.t), None, d)
+        cur = aux.s8
+        hh, ww = h, w
+        for (cv, bn, relu), d in zip(layers, descs):
+            wp, sh = self._pack_s8(cv, bn, d)
+            if d is descs[-1]:
+                args = ops.conv3x3_s2_s8_args(cur, wp, sh, d, res, out)
             else:
                 nxt = self.new(n * cv.out_channels * (hh // 2) * (ww // 2))
-                self.call(L.otp_conv3x3_s2_s8, "otp_conv3x3_s2_s8", hip.ptr(cur), hip.ptr(wp), hip.ptr(sh), None, None, hip.ptr(nxt), d)
+                args = ops.conv3x3_s2_s8_args(cur, wp, sh, d, out_s8=nxt)
                 cur = nxt
-            hh, ww, cin = hh // 2, ww // 2, cv.out_channels
+            self.call(self.lib.otp_conv3x3_s2_s8, "otp_conv3x3_s2_s8", *args)
+            hh, ww = hh // 2, ww // 2
         return out
 
-    def _pack_s8(self, conv, sc, desc):
-        """Packed split-product weights of a 3x3 conv for csrc/convs.hip / convs2.hip, stored times the layer's power of two
-        (ops.x3_weight_exponent) with the inverse in ``desc.out_scale``."""
+    def _pack_s8(self, conv, bn, desc):
+        """Packed split-product weights of a 3x3 conv + BN for csrc/convs.hip / convs2.hip, stored times the layer's power of two
+        (ops.x3_weight_exponent) with the inverse in ``desc.out_scale``, and the BN shift."""
+        sc, sh = self._bn_fold(bn)
         w = self.dev_param(conv.weight)
         e = ops.x3_weight_exponent(w, sc)
         desc.out_scale = 2.0 ** -e
-        return ops.pack_s8_weight(w, sc, e)
+        wp = ops.pack_s8_weight(w, sc, e)
+        self._keep += [wp, desc]
+        return wp, sh
 
-    def _bn_fold(self, bn):
-        g, b = self.dev_param(bn.weight), self.dev_param(bn.bias)
-        mu, var = self.dev_param(bn.running_mean), self.dev_param(bn.running_var)
-        sc = (g / torch.sqrt(var + bn.eps)).contiguous()
-        sh = (b - mu * sc).contiguous()
-        self._keep += [sc, sh]
-        return sc, sh
+    def conv_s8(self, x8, conv, bn, d, **outputs):
+        """Emit one otp_conv3x3_s8 launch: bn(conv(S8 image ``x8``)) by descriptor ``d``; ``outputs``: the residual and output
+        arguments of ``ops.conv3x3_s8_args``."""
+        wp, sh = self._pack_s8(conv, bn, d)
+        self.call(self.lib.otp_conv3x3_s8, "otp_conv3x3_s8", *ops.conv3x3_s8_args(x8, wp, sh, d, **outputs))
+
+    def conv_s8_lazy(self, x8, conv, bn, d, out: View, o8, res=None):
+        """:meth:`conv_s8` writing the S8 image ``o8`` (if any) and, registered as lazily written when there is one and
+        ``Routes.lazy_nchw``, the NCHW tensor ``out``."""
+        wp, sh = self._pack_s8(conv, bn, d)
+        aux = Aux(o8, nchw_needed=o8 is None or not self.routes.lazy_nchw)
+        if o8 is not None:
+            self._aux[id(out.t)] = aux
+        self.call_lazy_nchw(aux, self.lib.otp_conv3x3_s8, "otp_conv3x3_s8", lambda nchw: ops.conv3x3_s8_args(
+            x8, wp, sh, d, res, out.t if nchw else None, ops.S8_F32_NCHW, o8))
 
     def branch_s8(self, blocks, x: View, want_s8=False):
         """A branch of a HighResolutionModule (HRNet.py:478-496: 4 BasicBlocks, :500-530) on split-record activations
@@ -480,76 +535,48 @@ class InferenceEngine:
         S8; the last conv2 writes the NCHW tensor the fuse layer reads.  Returns None when the branch is not of that
         shape (the caller then emits the blocks one convolution at a time)."""
         n, c, h, w = x.t.shape
-        if x.coff != 0 or x.C != c or self._exact:
+        if not self.s8_here or x.coff != 0 or x.C != c:
             return None
         for blk in blocks:
             convs = (getattr(blk, "conv1", None), getattr(blk, "conv2", None))
-            if (getattr(blk, "downsample", None) is not None or hasattr(blk, "conv3") or any(
-                    cv is None or cv.kernel_size != (3, 3) or cv.stride != (1, 1) or cv.padding != (1, 1) or cv.dilation != (1, 1)
-                    or cv.bias is not None or cv.in_channels != c or cv.out_channels != c or cv.groups != 1 for cv in convs)):
+            if (getattr(blk, "downsample", None) is not None or hasattr(blk, "conv3")
+                    or any(cv is None or not plain_conv(cv, 3, cin=c, cout=c) for cv in convs)):
                 return None
         if not ops.s8_conv_supported(ops.s8_conv_desc(n, c, c, h, w, ACT_RELU)):
             return None
-        L = self.lib
         new_img = lambda: self.new(n * c * h * w)                          # noqa: E731  (S8 and C4 images are 4 bytes per element)
         # residual of a block: its input's S8 records (hi + lo holds the value to 2^-22: otp_conv_desc.res_layout = 1) - no fp32 (C4)
         # image exists between the blocks of a branch; OTPOSE_S8_RESIDUAL=0: the exact fp32 residual chain of round 3
-        res_s8 = os.environ.get("OTPOSE_S8_RESIDUAL", "1") != "0"
+        res_s8 = self.routes.s8_residual
         aux = self.s8_image(x, want_c4=not res_s8)                         # written by the producer (a fuse row), or packed here
         if aux is None:
             return None
-        xs8, xc4 = aux["s8"], (None if res_s8 else aux["c4"])
-        out = None
+        x8, xres = aux.s8, (aux.s8 if res_s8 else aux.c4)
         for b, blk in enumerate(blocks):
-            last = b == len(blocks) - 1
-            sc1, sh1 = self._bn_fold(blk.bn1)
-            sc2, sh2 = self._bn_fold(blk.bn2)
             y8 = new_img()
-            d1 = ops.s8_conv_desc(n, c, c, h, w, ACT_RELU)
-            w1 = self._pack_s8(blk.conv1, sc1, d1)
-            self._keep += [w1, d1]
-            self.call(L.otp_conv3x3_s8, "otp_conv3x3_s8", hip.ptr(xs8), hip.ptr(w1), hip.ptr(sh1), None, None, ops.S8_F32_C4,
-                      hip.ptr(y8), d1)
-            if last:
+            self.conv_s8(x8, blk.conv1, blk.bn1, ops.s8_conv_desc(n, c, c, h, w, ACT_RELU), out_s8=y8)
+            if b == len(blocks) - 1:
                 out = View(self.new(n, c, h, w))
                 d2 = ops.s8_conv_desc(n, c, c, h, w, ACT_RELU, out)
                 d2.res_layout = int(res_s8)
-                w2 = self._pack_s8(blk.conv2, sc2, d2)
-                self._keep += [w2, d2]
-                # a stride-2 consumer in the fuse layer (csrc/convs2.hip) reads the S8 image: written here, next to the NCHW tensor
-                o8 = new_img() if want_s8 else None
-                lazy = res_s8 and os.environ.get("OTPOSE_S8_LAZY_NCHW", "1") != "0"
-                oaux = {"s8": o8, "nchw_needed": not lazy} if o8 is not None else {"nchw_needed": True}
-                if o8 is not None:
-                    # consumers that can read the S8 image (stride-2 chains, the fuse row's identity term) do; the NCHW tensor is
-                    # written only if some consumer asks for it before the first launch (_needs_nchw)
-                    self._aux[id(out.t)] = oaux
-                largs = (hip.ptr(y8), hip.ptr(w2), hip.ptr(sh2), hip.ptr(xs8 if res_s8 else xc4))
-                optr, o8ptr = hip.ptr(out.t), (hip.ptr(o8) if o8 is not None else None)
-
-                def run_last(largs=largs, optr=optr, o8ptr=o8ptr, d2=d2, oaux=oaux):
-                    hip.check(L.otp_conv3x3_s8(*largs, optr if oaux["nchw_needed"] else None, ops.S8_F32_NCHW, o8ptr, d2, self._stream),
-                              "otp_conv3x3_s8")
-                self._emit(run_last)
-            else:
-                oc4, o8 = (None if res_s8 else new_img()), new_img()
-                d2 = ops.s8_conv_desc(n, c, c, h, w, ACT_RELU)
-                d2.res_layout = int(res_s8)
-                w2 = self._pack_s8(blk.conv2, sc2, d2)
-                self._keep += [w2, d2]
-                self.call(L.otp_conv3x3_s8, "otp_conv3x3_s8", hip.ptr(y8), hip.ptr(w2), hip.ptr(sh2),
-                          hip.ptr(xs8 if res_s8 else xc4), hip.ptr(oc4) if oc4 is not None else None, ops.S8_F32_C4, hip.ptr(o8), d2)
-                xs8, xc4 = o8, oc4
-        return out
+                # a stride-2 consumer in the fuse layer (csrc/convs2.hip) reads the S8 image: written here, next to the NCHW tensor.
+                # Consumers that can read the S8 image (stride-2 chains, the fuse row's identity term) do; the NCHW tensor is
+                # written only if some consumer asks for it before the first launch (_needs_nchw)
+                self.conv_s8_lazy(y8, blk.conv2, blk.bn2, d2, out, new_img() if want_s8 else None, res=xres)
+                return out
+            oc4, o8 = (None if res_s8 else new_img()), new_img()
+            d2 = ops.s8_conv_desc(n, c, c, h, w, ACT_RELU)
+            d2.res_layout = int(res_s8)
+            self.conv_s8(y8, blk.conv2, blk.bn2, d2, res=xres, out_f32=oc4, out_s8=o8)
+            x8, xres = o8, (o8 if res_s8 else oc4)
+        return None
 
     def conv_bn_s8(self, x: View, conv, bn, act=ACT_RELU):
         """act(bn(conv3x3 stride 1 pad 1 (x))) on csrc/convs.hip from the S8 image of ``x`` (packed here unless its producer wrote
         one), result as S8 records for the branch that follows and as the NCHW tensor only if another consumer asks for it.
         Returns None (nothing emitted) when the layer is not of that shape."""
         n, c, h, w = x.t.shape
-        if (not self.use_s8 or self._exact or conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1)
-                or conv.dilation != (1, 1) or conv.bias is not None or conv.groups != 1 or conv.in_channels != c
-                or x.coff != 0 or x.C != c or conv.out_channels % 16):
+        if not self.s8_here or not plain_conv(conv, 3, cin=c) or x.coff != 0 or x.C != c or conv.out_channels % 16:
             return None
         co = conv.out_channels
         out = View(self.new(n, co, h, w))
@@ -559,41 +586,25 @@ class InferenceEngine:
         aux = self.s8_image(x)
         if aux is None:
             return None
-        sc, sh = self._bn_fold(bn)
-        wp = self._pack_s8(conv, sc, d)
-        o8 = self.new(n * co * h * w)
-        lazy = os.environ.get("OTPOSE_S8_RESIDUAL", "1") != "0" and os.environ.get("OTPOSE_S8_LAZY_NCHW", "1") != "0"
-        oaux = {"s8": o8, "nchw_needed": not lazy}
-        self._aux[id(out.t)] = oaux
-        self._keep += [wp, d]
-        L = self.lib
-        largs = (hip.ptr(aux["s8"]), hip.ptr(wp), hip.ptr(sh), None)
-        optr, o8ptr = hip.ptr(out.t), hip.ptr(o8)
-
-        def run():
-            hip.check(L.otp_conv3x3_s8(*largs, optr if oaux["nchw_needed"] else None, ops.S8_F32_NCHW, o8ptr, d, self._stream),
-                      "otp_conv3x3_s8")
-        self._emit(run)
+        self.conv_s8_lazy(aux.s8, conv, bn, d, out, self.new(n * co * h * w))
         return out
 
     def _conv1_conv2_s8_ok(self, xc, n, h, w, conv1, conv2) -> bool:
         """Shape test of :meth:`conv1_conv2_s8` for an input of ``xc`` channels (the conv's own buffer as output)."""
-        if not (self.use_s8 and self.use_pointx and os.environ.get("OTPOSE_L1_S8", "1") != "0"):
+        r = self.routes
+        if not (r.use_s8 and r.use_pointx and r.l1_s8):
             return False
-        c1i, c1o, c2o = conv1.in_channels, conv1.out_channels, conv2.out_channels
-        if (conv1.kernel_size != (1, 1) or conv1.stride != (1, 1) or conv1.padding != (0, 0) or conv1.bias is not None
-                or conv1.groups != 1 or conv2.kernel_size != (3, 3) or conv2.stride != (1, 1) or conv2.padding != (1, 1)
-                or conv2.dilation != (1, 1) or conv2.bias is not None or conv2.groups != 1 or conv2.in_channels != c1o
-                or xc != c1i or not ops.pointwise_x3_s8_supported(c1i, c1o, h * w)):
+        c1o = conv1.out_channels
+        if not (plain_conv(conv1, 1, cin=xc) and plain_conv(conv2, 3, cin=c1o) and ops.pointwise_x3_s8_supported(xc, c1o, h * w)):
             return False
-        return bool(ops.s8_conv_supported(ops.s8_conv_desc(n, c1o, c2o, h, w, ACT_RELU)))
+        return bool(ops.s8_conv_supported(ops.s8_conv_desc(n, c1o, conv2.out_channels, h, w, ACT_RELU)))
 
     def pointx_pair(self, inp: View, weight, sc, sh, res: View, nxt):
         """relu(sc * conv1x1(inp) + sh (+ res)) in front of Bottleneck ``nxt`` (a layer1 block boundary, HRNet.py:551-571) with
         nxt's conv1 + bn1 + relu in the same launch (csrc/pointx.hip, pointx_pair_kernel): the 256-channel tensor is written for
         nxt's residual and not read back, nxt's conv1_conv2_s8 finds the S8 image of its conv1 ready.  The same bits as the two
         launches; OTPOSE_L1_PAIR=0 keeps those.  Returns None when either convolution is not of that shape."""
-        if not (self.use_pointx and not self._exact and os.environ.get("OTPOSE_L1_PAIR", "1") != "0"):
+        if not (self.routes.use_pointx and not self._exact and self.routes.l1_pair):
             return None
         w = self.dev_param(weight)
         n, _, h, wd = inp.t.shape
@@ -612,9 +623,8 @@ class InferenceEngine:
         self._keep.append(pk)
         self._pair_s8[id(out.t)] = y8
         self.l1_pairs += 1
-        self.call(self.lib.otp_pointwise_x3_pair, "otp_pointwise_x3_pair", hip.ptr(inp.t), hip.ptr(pk),
-                  hip.ptr(res.t if res is not None else None), hip.ptr(out.t), hip.ptr(y8), n, cin, cmid, c1.out_channels, h * wd,
-                  inp.ctot, inp.coff, res.ctot if res is not None else 0, res.coff if res is not None else 0, out.ctot, out.coff, 1, 1)
+        self.call(self.lib.otp_pointwise_x3_pair, "otp_pointwise_x3_pair",
+                  *ops.pointwise_x3_pair_args(inp, pk, out, c1.out_channels, y8, res))
         return out
 
     def conv1_conv2_s8(self, x: View, conv1, bn1, conv2, bn2, out: View = None):
@@ -631,9 +641,6 @@ class InferenceEngine:
         d2 = ops.s8_conv_desc(n, c1o, c2o, h, w, ACT_RELU, out)
         if not ops.s8_conv_supported(d2):
             return None
-        L = self.lib
-        sc2, sh2 = self._bn_fold(bn2)
-        w2 = self._pack_s8(conv2, sc2, d2)
         y8 = self._pair_s8.pop(id(x.t), None)          # conv1's S8 image, already written by the launch that wrote x (pointx_pair)
         if y8 is None:
             self._needs_nchw(x)
@@ -641,11 +648,9 @@ class InferenceEngine:
             pk = ops.pack_pointwise_x3_s8(self.dev_param(conv1.weight), sc1, sh1)
             y8 = self.new(n * c1o * h * w)
             self._keep.append(pk)
-            self.call(L.otp_pointwise_x3_s8, "otp_pointwise_x3_s8", hip.ptr(x.t), hip.ptr(pk), hip.ptr(y8), n, c1i, c1o, h * w,
+            self.call(self.lib.otp_pointwise_x3_s8, "otp_pointwise_x3_s8", hip.ptr(x.t), hip.ptr(pk), hip.ptr(y8), n, c1i, c1o, h * w,
                       x.ctot, x.coff, 1)
-        self._keep += [w2, d2]
-        self.call(L.otp_conv3x3_s8, "otp_conv3x3_s8", hip.ptr(y8), hip.ptr(w2), hip.ptr(sh2), None, hip.ptr(out.t), ops.S8_F32_NCHW,
-                  None, d2)
+        self.conv_s8(y8, conv2, bn2, d2, out_f32=out.t, f32_layout=ops.S8_F32_NCHW)
         return out
 
     def bottleneck(self, blk, x: View, s8_only=False, nxt=None) -> View:
@@ -668,30 +673,22 @@ class InferenceEngine:
             self.join((1,))
         n, _, h, w = y.t.shape
         c3 = blk.conv3
-        if (s8_only and self.use_s8 and self.use_pointx and not self._exact and c3.kernel_size == (1, 1) and c3.bias is None
-                and c3.stride == (1, 1) and y.C == c3.in_channels and res.C == c3.out_channels
-                and ops.pointwise_x3_s8_supported(c3.in_channels, c3.out_channels, h * w)):
+        co = c3.out_channels
+        if (s8_only and self.s8_here and self.routes.use_pointx and plain_conv(c3, 1, cin=y.C, cout=res.C)
+                and ops.pointwise_x3_s8_supported(c3.in_channels, co, h * w)):
             for v_ in (y, res):
                 self._needs_nchw(v_)
-            co = c3.out_channels
             sc, sh = self._bn_fold(blk.bn3)
             pk = ops.pack_pointwise_x3_s8(self.dev_param(c3.weight), sc, sh)
             out = View(self.new(n, co, h, w))
             o8 = self.new(n * co * h * w)
-            oaux = {"s8": o8, "nchw_needed": False}
-            self._aux[id(out.t)] = oaux
+            aux = self._aux[id(out.t)] = Aux(o8)
             self._keep.append(pk)
-            L = self.lib
-            args = (hip.ptr(y.t), hip.ptr(pk), hip.ptr(res.t), hip.ptr(o8), n, y.C, co, h * w, y.ctot, y.coff, res.ctot, res.coff, 1)
-
-            def run():
-                hip.check(L.otp_pointwise_x3_s8_res(*args, self._stream), "otp_pointwise_x3_s8_res")
-                if oaux["nchw_needed"]:                         # (a consumer without an S8 path: hi + lo back to fp32 NCHW)
-                    hip.check(L.otp_s8_unpack(hip.ptr(o8), hip.ptr(out.t), n, co, h, w, self._stream), "otp_s8_unpack")
-            self._emit(run)
+            self.call_lazy_nchw(aux, self.lib.otp_pointwise_x3_s8_res, "otp_pointwise_x3_s8_res",
+                                lambda nchw: ops.pointwise_x3_s8_res_args(y, pk, co, o8, res, True),
+                                unpack=(hip.ptr(o8), hip.ptr(out.t), n, co, h, w))
             return out
-        if (nxt is not None and c3.kernel_size == (1, 1) and c3.stride == (1, 1) and c3.padding == (0, 0) and c3.bias is None
-                and c3.groups == 1):
+        if nxt is not None and plain_conv(c3, 1):
             sc, sh = self._bn_fold(blk.bn3)
             out = self.pointx_pair(y, c3.weight, sc, sh, res, nxt)
             if out is not None:
@@ -705,13 +702,13 @@ class InferenceEngine:
         as ITS row is done instead of when the slowest row is."""
         n = mod.num_branches
         xs = list(xs)
+        r = self.routes
         if fork_in:
             self.fork(range(1, n))
         for i in range(n):
             self.on_stream(i)                                     # branch i is independent of the others until the fuse
             # branch i feeds the stride-2 chains of the fuse rows below it
-            down = i < len(mod.fuse_layers) - 1 and not self._exact and os.environ.get("OTPOSE_S8_STRIDE2", "1") != "0"
-            y = self.branch_s8(list(mod.branches[i]), xs[i], want_s8=down) if self.use_s8 else None
+            y = self.branch_s8(list(mod.branches[i]), xs[i], want_s8=i < len(mod.fuse_layers) - 1 and self.s2_here)
             if y is not None:
                 xs[i] = y
                 continue
@@ -722,7 +719,7 @@ class InferenceEngine:
         if n == 1:
             return xs
         outs = []
-        if self.use_s8 and not self._exact and os.environ.get("OTPOSE_S8_STRIDE2", "1") != "0":
+        if self.s2_here:
             for j in range(min(n, len(mod.fuse_layers) - 1)):     # S8 images the rows below read, made before the rows fork
                 self.s8_image(xs[j])
         self.fork(range(1, len(mod.fuse_layers)))
@@ -736,7 +733,7 @@ class InferenceEngine:
             # adds them all to the high-resolution tensor (same summation order as chaining them)
             ups = [j for j in terms if j > i]
             hi_w = xs[i].t.shape[3]
-            if self.fuse_upsample and len(ups) >= 2 and hi_w % 4 == 0:
+            if r.fuse_upsample and len(ups) >= 2 and hi_w % 4 == 0:
                 terms = [j for j in terms if j < i]
             else:
                 ups = []
@@ -745,28 +742,24 @@ class InferenceEngine:
                 act = ACT_RELU if last else ACT_NONE
                 res = xs[i] if y is None else y
                 fl = mod.fuse_layers[i][j]
+                tgt = y if y is not None else View(self.new(*xs[i].t.shape))
                 if j > i:
                     f = 2 ** (j - i)
-                    tgt = y if y is not None else View(self.new(*xs[i].t.shape))
-                    if f >= 2 and ((xs[j].t.shape[3] * f) % 4 == 0 or os.environ.get("OTPOSE_UP_ANY_WIDTH", "1") != "0"):
+                    if f >= 2 and ((xs[j].t.shape[3] * f) % 4 == 0 or r.up_any_width):
                         # (any width: otp_upsample_add has a one-element form - rows of 18 at 384x288 used to send the 384 -> 192
                         #  term of stage 4's row 2 to the generic conv kernel's upsample epilogue, 195 us on the row's critical path)
                         # the upsampled tensor is f*f x the conv result: conv at low resolution, then one streaming
                         # accumulate kernel (measured faster than the conv kernel's element-wise upsample epilogue)
                         low = self.conv_bn(xs[j], fl[0], fl[1], ACT_NONE)
-                        n_, c_, hl, wl = low.t.shape
-                        if act == ACT_RELU and low.coff == 0 and low.C == c_ and self.fuse_s8([low], [f], res, tgt):
+                        if act == ACT_RELU and low.coff == 0 and low.C == low.ctot and self.fuse_s8([low], [f], res, tgt):
                             y = tgt
                             continue
                         self._needs_nchw(res)
-                        self.call(self.lib.otp_upsample_add, "otp_upsample_add", hip.ptr(low.t), hip.ptr(res.t),
-                                  hip.ptr(tgt.t), n_, c_, hl, wl, f, int(act == ACT_RELU), low.ctot, low.coff,
-                                  res.ctot, res.coff, tgt.ctot, tgt.coff)
+                        self.call(self.lib.otp_upsample_add, "otp_upsample_add", *ops.upsample_add_args(low, res, tgt, f, act == ACT_RELU))
                         y = tgt
                     else:
                         y = self.conv_bn(xs[j], fl[0], fl[1], act, res=res, out=tgt, res_up=f)
                 else:
-                    tgt = y if y is not None else View(self.new(*xs[i].t.shape))
                     chain = [(fl[k][0], fl[k][1], k < len(fl) - 1) for k in range(len(fl))]
                     if self.s2_chain_s8(chain, xs[j], act, res=res, out=tgt) is not None:
                         y = tgt
@@ -779,16 +772,14 @@ class InferenceEngine:
                 res = xs[i] if y is None else y
                 tgt = y if y is not None else View(self.new(*xs[i].t.shape))
                 lows = [self.conv_bn(xs[j], mod.fuse_layers[i][j][0], mod.fuse_layers[i][j][1], ACT_NONE) for j in ups]
-                n_, c_, hh, wh = tgt.t.shape[0], xs[i].C, xs[i].t.shape[2], xs[i].t.shape[3]
-                if self.fuse_s8(lows, [2 ** (j - i) for j in ups], res, tgt):
+                factors = [2 ** (j - i) for j in ups]
+                if self.fuse_s8(lows, factors, res, tgt):
                     outs.append(tgt)
                     continue
                 self._needs_nchw(res)
-                lp = (ctypes.c_void_p * len(ups))(*[hip.ptr(v.t) for v in lows])
-                fp = (ctypes.c_int * len(ups))(*[2 ** (j - i) for j in ups])
-                self._keep += [lp, fp]
-                self.call(self.lib.otp_upsample_add_multi, "otp_upsample_add_multi", lp, fp, len(ups), hip.ptr(res.t),
-                          hip.ptr(tgt.t), n_, c_, hh, wh, 1, res.ctot, res.coff, tgt.ctot, tgt.coff)
+                args, arrays = ops.upsample_add_multi_args(lows, factors, res, tgt, relu=True)
+                self._keep += arrays
+                self.call(self.lib.otp_upsample_add_multi, "otp_upsample_add_multi", *args)
                 y = tgt
             outs.append(y)
         self.on_stream(0)
@@ -796,12 +787,47 @@ class InferenceEngine:
             self.join(range(1, len(mod.fuse_layers)))
         return outs
 
+    def hr_stages(self, net, x, width_change, new_branch, module, before_fork=None):
+        """Transitions and stages 2 - 4 of an HRNet (model/HRNet.py:131-152), the walk both engines share: the convs of a
+        transition only share their inputs and run on a stream each; consecutive modules of a stage are chained stream by
+        stream (see :meth:`hr_module`).  The engine's emitters: ``width_change(s, x, tr)`` and ``new_branch(s, x, tr)`` for the
+        two kinds of transition layer (:213-229), ``module(s, mi, n_mods, mod, xs, fork_in, join_out)`` for module ``mi`` of
+        the ``n_mods`` of stage ``s``, ``before_fork(s, xs)`` ahead of a transition's fork."""
+        ys = [x]
+        for s in (2, 3, 4):
+            trans = getattr(net, f"transition{s - 1}")
+            live = [i for i, tr in enumerate(trans) if tr is not None]
+            if before_fork is not None:
+                before_fork(s, ys)
+            self.fork(range(1, len(live)))                         # the transition convs only share their inputs
+            xs = []
+            for i, tr in enumerate(trans):
+                if tr is None:
+                    xs.append(ys[i])
+                    continue
+                self.on_stream(live.index(i))
+                if isinstance(tr[0], torch.nn.Conv2d):            # same-resolution width change (:213-220)
+                    xs.append(width_change(s, ys[i], tr))
+                else:                                              # new branch from the last tensor (:221-229)
+                    xs.append(new_branch(s, ys[-1], tr))
+            self.on_stream(0)
+            self.join(range(1, len(live)))
+            ys = xs
+            mods = list(getattr(net, f"stage{s}"))
+            cont = False
+            for mi, mod in enumerate(mods):
+                # the next module's branch i continues on the stream of this module's row i (same count of rows and branches)
+                fork_in, nxt = not cont, (mods[mi + 1] if mi + 1 < len(mods) else None)
+                cont = (self.routes.chain_modules and nxt is not None and len(mod.fuse_layers) == nxt.num_branches
+                        and mod.num_branches > 1)
+                ys = module(s, mi, len(mods), mod, ys, fork_in, not cont)
+        return ys
+
     def hrnet(self, net, x_in: View) -> View:
         c1 = net.conv1
+        r = self.routes
         n_in, c_in, h_in, w_in = x_in.t.shape
-        if (self.use_x3 and os.environ.get("OTPOSE_STEM_X3", "1") != "0" and x_in.coff == 0 and x_in.C == c_in and c_in == 3 * self.F
-                and c1.kernel_size == (3, 3) and c1.stride == (2, 2) and c1.padding == (1, 1) and c1.dilation == (1, 1)
-                and c1.in_channels == 3 and c1.bias is None and c1.groups == 1
+        if (r.use_x3 and r.stem_x3 and x_in.coff == 0 and x_in.C == c_in and c_in == 3 * self.F and plain_conv(c1, 3, stride=2, cin=3)
                 and ops.stem_conv_x3_supported(n_in, self.F, h_in, w_in, c1.out_channels)):
             # conv1 + bn1 + relu on the frames of the clip (HRNet.py:118-120 after OTPose.py:317): one k-step of split products per
             # 16 pixels x 16 channels, gathered straight from the image (csrc/stem.hip), stored through an LDS slab as 256-byte runs
@@ -810,14 +836,12 @@ class InferenceEngine:
             pk = ops.pack_stem_conv_x3(self.dev_param(c1.weight), sc, sh)
             self._keep.append(pk)
             x = View(self.new(self.F * n_in, c1.out_channels, (h_in - 1) // 2 + 1, (w_in - 1) // 2 + 1))
-            self.call(self.lib.otp_stem_conv_x3, "otp_stem_conv_x3", hip.ptr(x_in.t), hip.ptr(pk), hip.ptr(x.t), n_in, self.F, h_in,
-                      w_in, c1.out_channels)
+            self.call(self.lib.otp_stem_conv_x3, "otp_stem_conv_x3", *ops.stem_conv_x3_args(x_in.t, pk, x.t, self.F, c1.out_channels))
         else:
             x = self.conv_bn(x_in, net.conv1, net.bn1, ACT_RELU, frame_split=self.B, cin=3)
         blocks = list(net.layer1)
         b0 = blocks[0]
-        if (self.fuse_shortcut and b0.downsample is not None and b0.conv3.kernel_size == (1, 1)
-                and b0.downsample[0].kernel_size == (1, 1) and b0.downsample[0].stride == (1, 1)):
+        if (r.fuse_shortcut and b0.downsample is not None and plain_conv(b0.conv3, 1) and plain_conv(b0.downsample[0], 1)):
             # first Bottleneck (HRNet.py:551-571 with the 1x1 shortcut of :240-247): relu(bn3(conv3(y)) + bn_d(conv_d(x))) is
             # one 1x1 conv over the channel concatenation [x, y] with both BatchNorm scales folded into the weights - the
             # 256-channel shortcut tensor (566 MB at cfg2) is neither written nor read back.  x (stem conv2) and y
@@ -834,10 +858,8 @@ class InferenceEngine:
                 self.conv_bn(y, b0.conv2, b0.bn2, ACT_RELU, out=View(cat, cx, cy))
 
             def fold(conv, bn):
-                g, b = self.dev_param(bn.weight), self.dev_param(bn.bias)
-                mu, var = self.dev_param(bn.running_mean), self.dev_param(bn.running_var)
-                sc = g / torch.sqrt(var + bn.eps)
-                return self.dev_param(conv.weight) * sc[:, None, None, None], b - mu * sc
+                sc, sh = self._bn_fold(bn)
+                return self.dev_param(conv.weight) * sc[:, None, None, None], sh
             wd, shd = fold(b0.downsample[0], b0.downsample[1])
             w3, sh3 = fold(b0.conv3, b0.bn3)
             cout = b0.conv3.out_channels
@@ -848,54 +870,40 @@ class InferenceEngine:
             blocks = blocks[1:]
         else:
             x = self.conv_bn(x, net.conv2, net.bn2, ACT_RELU)
-        t1_s8 = self.use_s8 and not self._exact and os.environ.get("OTPOSE_T1_S8", "1") != "0" \
-            and os.environ.get("OTPOSE_S8_STRIDE2", "1") != "0"
         for bi, blk in enumerate(blocks):
-            x = self.bottleneck(blk, x, s8_only=t1_s8 and bi == len(blocks) - 1, nxt=blocks[bi + 1] if bi + 1 < len(blocks) else None)
-        ys = [x]
-        for s in (2, 3, 4):
-            trans = getattr(net, f"transition{s - 1}")
-            xs = []
-            live = [i for i, tr in enumerate(trans) if tr is not None]
-            t1_s8 = s == 2 and self.use_s8 and not self._exact and os.environ.get("OTPOSE_T1_S8", "1") != "0"
-            if (s >= 3 or t1_s8) and self.use_s8 and os.environ.get("OTPOSE_S8_STRIDE2", "1") != "0":
+            # (the last Bottleneck's result as S8 records only: transition1's convs read them)
+            x = self.bottleneck(blk, x, s8_only=self.s2_here and r.t1_s8 and bi == len(blocks) - 1,
+                                nxt=blocks[bi + 1] if bi + 1 < len(blocks) else None)
+
+        def t1_s8(s):
+            return s == 2 and self.s8_here and r.t1_s8
+
+        def before_fork(s, ys):
+            if (s >= 3 or t1_s8(s)) and self.s2_here:
                 # the lowest-resolution tensor feeds the new branch's stride-2 conv AND its own branch of the next module (s >= 3) /
                 # the width-change conv of transition1 (s = 2: 256 -> 48 and 256 -> 96 stride 2 ran at 100-160 TFLOP/s on the
                 # fp32-input kernel): one pack pass before the streams fork serves both
-                self.s8_image(ys[-1], want_c4=s >= 3 and os.environ.get("OTPOSE_S8_RESIDUAL", "1") == "0")
-            self.fork(range(1, len(live)))                         # the transition convs only share their inputs
-            for i, tr in enumerate(trans):
-                if tr is None:
-                    xs.append(ys[i])
-                    continue
-                self.on_stream(live.index(i))
-                if isinstance(tr[0], torch.nn.Conv2d):            # same-resolution width change
-                    y_ = self.conv_bn_s8(ys[i], tr[0], tr[1], ACT_RELU) if t1_s8 else None
-                    xs.append(y_ if y_ is not None else self.conv_bn(ys[i], tr[0], tr[1], ACT_RELU))
-                else:                                              # new branch from the last tensor
-                    z = ys[-1]
-                    zs = self.s2_chain_s8([(step[0], step[1], True) for step in tr], z, ACT_RELU) if (s >= 3 or t1_s8) else None
-                    if zs is None:
-                        for step in tr:
-                            z = self.conv_bn(z, step[0], step[1], ACT_RELU)
-                        zs = z
-                    xs.append(zs)
-            self.on_stream(0)
-            self.join(range(1, len(live)))
-            ys = xs
-            mods = list(getattr(net, f"stage{s}"))
-            chain = os.environ.get("OTPOSE_CHAIN_MODULES", "1") != "0"
-            for mi, mod in enumerate(mods):
-                nxt = mods[mi + 1] if mi + 1 < len(mods) else None
-                # the next module's branch i continues on the stream of this module's row i (same count of rows and branches)
-                cont = chain and nxt is not None and len(mod.fuse_layers) == nxt.num_branches and mod.num_branches > 1
-                self._exact = s == 4 and mi >= len(mods) - self.f32_tail
-                ys = self.hr_module(mod, ys, fork_in=not (mi > 0 and prev_cont), join_out=not cont) if mi > 0 else \
-                    self.hr_module(mod, ys, fork_in=True, join_out=not cont)
-                prev_cont = cont
+                self.s8_image(ys[-1], want_c4=s >= 3 and not r.s8_residual)
+
+        def width_change(s, x, tr):
+            y = self.conv_bn_s8(x, tr[0], tr[1], ACT_RELU) if t1_s8(s) else None
+            return y if y is not None else self.conv_bn(x, tr[0], tr[1], ACT_RELU)
+
+        def new_branch(s, z, tr):
+            zs = self.s2_chain_s8([(step[0], step[1], True) for step in tr], z, ACT_RELU) if (s >= 3 or t1_s8(s)) else None
+            if zs is not None:
+                return zs
+            for step in tr:
+                z = self.conv_bn(z, step[0], step[1], ACT_RELU)
+            return z
+
+        def module(s, mi, n_mods, mod, xs, fork_in, join_out):
+            self._exact = s == 4 and mi >= n_mods - r.f32_tail          # the exact-fp32 tail (Routes.f32_tail)
+            return self.hr_module(mod, xs, fork_in, join_out)
+        ys = self.hr_stages(net, x, width_change, new_branch, module, before_fork)
         fl = net.final_layer
         rough = View(self.new(self.F * self.B, self.J, self.h, self.w))
-        self._exact = self.f32_tail > 0
+        self._exact = r.f32_tail > 0
         out = self.conv(ys[0], fl.weight, rough, 1, fl.padding[0], 1, bias=fl.bias)
         self._exact = False
         return out
@@ -911,20 +919,16 @@ class InferenceEngine:
         To = T if stride == 1 else (T + 2 - 3) // 2 + 1
         L = self.lib
         a = blk.attn
-        if self.use_flow_fused and stride == 1 and ops.flow_block_supported(blk, C, T):
+        r = self.routes
+        if r.use_flow_fused and stride == 1 and ops.flow_block_supported(blk, C, T):
             # the C = 17 flow encoder: per-token chains in two launches around the attention (csrc/flowenc.hip); the generic
             # kernels below are latency bound at this width (12 launches per block on the serial path)
             fp, bp = ops.pack_flow_front(blk, self.dev), ops.pack_flow_back(blk, self.dev)
             self._keep += [fp, bp]
             q, k, v, att, out = (self.new(B, C, T) for _ in range(5))
-            self.call(L.otp_flow_front, "otp_flow_front", hip.ptr(x), hip.ptr(fp), hip.ptr(q), hip.ptr(k), hip.ptr(v),
-                      B, C, T, blk.ln1.eps)
-            nbytes = L.otp_chan_attn_workspace(B, C, T, a.n_head)
-            ws = self.new(max(nbytes // 4, 1))
-            self.call(L.otp_chan_attn, "otp_chan_attn", hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(att), hip.ptr(ws),
-                      nbytes, B, C, T, a.n_head, a.scale)
-            self.call(L.otp_flow_back, "otp_flow_back", hip.ptr(x), hip.ptr(att), hip.ptr(bp), hip.ptr(out), B, C,
-                      blk.mlp[0].out_channels, T, blk.ln2.eps)
+            self.call(L.otp_flow_front, "otp_flow_front", *ops.flow_front_args(x, fp, q, k, v, blk.ln1.eps))
+            self.chan_attn(q, k, v, att, a)
+            self.call(L.otp_flow_back, "otp_flow_back", *ops.flow_back_args(x, att, bp, out, blk.mlp[0].out_channels, blk.ln2.eps))
             return out
         ln1 = self.new(B, C, T)
         skip = self.new(B, C, To) if stride > 1 else None
@@ -935,21 +939,19 @@ class InferenceEngine:
         # (the split-product kernels of csrc/densex.hip also hold C = 204, the 7-frame window of BASELINE configs[4]; the exact-fp32
         #  ones of csrc/dense.hip only C = 136 - until round 4 this line asked the fp32 predicate first and cfg5 ran its
         #  projections and the q / k / v front end on the generic kernels: 23 ms of kernel time per forward)
-        dx3 = self.use_dense_cc and self.use_x3 and ops.dense_x3_supported(C, To)
-        dense = dx3 or (self.use_dense_cc and ops.dense_cc_supported(C, To))
+        dx3 = r.use_dense_cc and r.use_x3 and ops.dense_x3_supported(C, To)
+        dense = dx3 or (r.use_dense_cc and ops.dense_cc_supported(C, To))
         if dense:
             packs = [ops.pack_dense_cc(m.weight.to(self.dev), None, m.bias.to(self.dev), x3=dx3)
                      for m in (a.query, a.key, a.value)]
-        if dense and stride == 1 and self.use_qkv_front:
+        if dense and stride == 1 and r.use_qkv_front:
             # depthwise convs + LayerNorms + the three projections in one launch (csrc/dense.hip, qkv_front_kernel)
             table = ops.pack_qkv_table(*[p(t) for t in (a.query_conv.weight, a.key_conv.weight, a.value_conv.weight,
                                                          a.query_norm.weight, a.query_norm.bias, a.key_norm.weight,
                                                          a.key_norm.bias, a.value_norm.weight, a.value_norm.bias)])
             self._keep += [table, *packs]
             self.call((L.otp_qkv_front_h1 if self.half_products else L.otp_qkv_front_x3) if dx3 else L.otp_qkv_front, "otp_qkv_front",
-                      hip.ptr(ln1), hip.ptr(table),
-                      *[hip.ptr(t) for t in packs],
-                      hip.ptr(q), hip.ptr(k), hip.ptr(v), B, C, T, a.query_norm.eps)
+                      *ops.qkv_front_args(ln1, table, packs, (q, k, v), a.query_norm.eps))
         else:
             qn, kn, vn = self.new(B, C, To), self.new(B, C, To), self.new(B, C, To)
             self.call(L.otp_dwconv_ln3, "otp_dwconv_ln3", hip.ptr(ln1), hip.ptr(p(a.query_conv.weight)),
@@ -966,17 +968,14 @@ class InferenceEngine:
                 self.conv(self.v3(kn), a.key.weight, self.v3(k), bias=a.key.bias)
                 self.conv(self.v3(vn), a.value.weight, self.v3(v), bias=a.value.bias)
         att = self.new(B, C, To)
-        nbytes = L.otp_chan_attn_workspace(B, C, To, a.n_head)
-        ws = self.new(max(nbytes // 4, 1))
-        self.call(L.otp_chan_attn, "otp_chan_attn", hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(att), hip.ptr(ws),
-                  nbytes, B, C, To, a.n_head, a.scale)
+        self.chan_attn(q, k, v, att, a)
         # y = pool_skip(x) + scale_attn * (proj(att) + b)   (eval: dropout / drop-path are identities)
         sa = blk.drop_path_attn.scale.detach().reshape(-1)
         y = self.new(B, C, To)
         if dense:
             sad = sa.to(self.dev, torch.float32)
             pk = ops.pack_dense_cc(a.proj.weight.to(self.dev), sad, a.proj.bias.detach().to(self.dev) * sad,
-                                   x3=self.use_x3 and ops.dense_x3_supported(C, To))
+                                   x3=r.use_x3 and ops.dense_x3_supported(C, To))
             self.dense((att,), [pk], (skip if stride > 1 else x,), (y,), B, C, To)
         else:
             self.conv(self.v3(att), a.proj.weight, self.v3(y), scale=sa,
@@ -984,26 +983,19 @@ class InferenceEngine:
         sm = blk.drop_path_mlp.scale.detach().reshape(-1)
         out = self.new(B, C, To)
         hid = blk.mlp[0].out_channels
-        if self.use_fused_mlp and self.use_x3 and ops.mlp_x3_supported(C, hid, To):
-            # the same single launch with split-half products on the 16-bit matrix cores (csrc/mlpx.hip)
+        # ln2 -> Conv1d -> GELU -> Conv1d + residual as one launch, hidden activation kept on chip: with split-half products on
+        # the 16-bit matrix cores (csrc/mlpx.hip), else in exact fp32 (csrc/mlp.hip)
+        mlp_x3 = r.use_fused_mlp and r.use_x3 and ops.mlp_x3_supported(C, hid, To)
+        if mlp_x3 or (r.use_fused_mlp and ops.mlp_fused_supported(C, hid, To)):
             dev = lambda t: t.detach().to(self.dev, torch.float32)     # noqa: E731
-            packed = ops.pack_mlp_x3_weights(dev(blk.mlp[0].weight), dev(blk.mlp[0].bias), dev(blk.mlp[3].weight), half=self.half_products)
+            w1, b1, w2 = dev(blk.mlp[0].weight), dev(blk.mlp[0].bias), dev(blk.mlp[3].weight)
+            packed = ops.pack_mlp_x3_weights(w1, b1, w2, half=self.half_products) if mlp_x3 else ops.pack_mlp_weights(w1, b1, w2)
             scd = dev(sm).contiguous()
             shd = (dev(blk.mlp[3].bias) * scd).contiguous()
             self._keep += [packed, scd, shd]
-            self.call(L.otp_ln_mlp_h1 if self.half_products else L.otp_ln_mlp_x3, "otp_ln_mlp_x3", hip.ptr(y), hip.ptr(p(blk.ln2.weight)),
-                      hip.ptr(p(blk.ln2.bias)),
-                      blk.ln2.eps, hip.ptr(packed), hip.ptr(scd), hip.ptr(shd), hip.ptr(out), B, C, hid, To)
-            return out
-        if self.use_fused_mlp and ops.mlp_fused_supported(C, hid, To):
-            # ln2 -> Conv1d -> GELU -> Conv1d + residual as one launch, hidden activation kept on chip (csrc/mlp.hip)
-            dev = lambda t: t.detach().to(self.dev, torch.float32)     # noqa: E731
-            packed = ops.pack_mlp_weights(dev(blk.mlp[0].weight), dev(blk.mlp[0].bias), dev(blk.mlp[3].weight))
-            scd = dev(sm).contiguous()
-            shd = (dev(blk.mlp[3].bias) * scd).contiguous()
-            self._keep += [packed, scd, shd]
-            self.call(L.otp_ln_mlp_fused, "otp_ln_mlp_fused", hip.ptr(y), hip.ptr(p(blk.ln2.weight)), hip.ptr(p(blk.ln2.bias)),
-                      blk.ln2.eps, hip.ptr(packed), hip.ptr(scd), hip.ptr(shd), hip.ptr(out), B, C, hid, To)
+            fn, name = ((L.otp_ln_mlp_h1 if self.half_products else L.otp_ln_mlp_x3, "otp_ln_mlp_x3") if mlp_x3
+                        else (L.otp_ln_mlp_fused, "otp_ln_mlp_fused"))
+            self.call(fn, name, *ops.ln_mlp_args(y, p(blk.ln2.weight), p(blk.ln2.bias), blk.ln2.eps, packed, scd, shd, out, hid))
             return out
         ln2 = self.new(B, C, To)
         self.call(L.otp_ln_channel, "otp_ln_channel", hip.ptr(y), hip.ptr(p(blk.ln2.weight)), hip.ptr(p(blk.ln2.bias)),
@@ -1014,21 +1006,26 @@ class InferenceEngine:
                   shift=blk.mlp[3].bias.detach() * sm.to(blk.mlp[3].bias.device), res=self.v3(y))
         return out
 
+    def chan_attn(self, q, k, v, att, a):
+        """Channel attention of a MaskedMHCA ``a`` (csrc/attn.hip) with its workspace."""
+        B, C, T = q.shape
+        nbytes = self.lib.otp_chan_attn_workspace(B, C, T, a.n_head)
+        ws = self.new(max(nbytes // 4, 1))
+        self.call(self.lib.otp_chan_attn, "otp_chan_attn", *ops.chan_attn_args(q, k, v, att, ws, nbytes, a.n_head, a.scale))
+
     def conv_transformer(self, ct, x, stacked):
         """x (B, C, T) already holds input + positional table; writes levels into stacked (B, L*C, T)."""
-        B, C, T = x.shape
+        _, C, T = x.shape
         L = self.lib
         for blk in ct.stem:
             x = self.tblock(blk, x, 1)
-        self.call(L.otp_upsample_linear, "otp_upsample_linear", hip.ptr(x), hip.ptr(stacked), B, C, T, 1,
-                  stacked.shape[1], 0)
+        self.call(L.otp_upsample_linear, "otp_upsample_linear", *ops.upsample_linear_args(x, stacked, 1, 0))
         for i, blk in enumerate(ct.branch):
             x = self.tblock(blk, x, 2)
             f = 2 ** (i + 1)
             if x.shape[2] * f != T:
                 raise RuntimeError("heat-map size must make every pyramid level divide evenly (T % 4 == 0)")
-            self.call(L.otp_upsample_linear, "otp_upsample_linear", hip.ptr(x), hip.ptr(stacked), B, C, x.shape[2], f,
-                      stacked.shape[1], (i + 1) * C)
+            self.call(L.otp_upsample_linear, "otp_upsample_linear", *ops.upsample_linear_args(x, stacked, f, (i + 1) * C))
 
     # ---- RSB heads (reference model/RSB.py:77-103) --------------------------------------------------
     def rsb_block(self, blk, x: View) -> View:
@@ -1134,7 +1131,7 @@ class InferenceEngine:
         self.fork((1,))
         self.conv_transformer(m.temporal_encoder1, x1, s1)
         final(m.final_layer1, s1, 0)
-        self.on_stream(0 if os.environ.get("OTPOSE_TE_SERIAL") == "1" else 1)
+        self.on_stream(0 if self.routes.te_serial else 1)
         self.conv_transformer(m.temporal_encoder2, x2, s2)
         final(m.final_layer2, s2, 1)
         self.on_stream(0)
@@ -1145,10 +1142,7 @@ class InferenceEngine:
         dils = [int(d) for d in m.deformable_conv_dilations]
         cin_t = trans.C
         if (self.use_dcn_fused and trans.coff == 0 and trans.C == trans.ctot and ops.dcn_fused_supported(cin_t, J, h, w, nd)
-                and all(c[0].kernel_size == (3, 3) and c[0].bias is None and c[0].stride == (1, 1)
-                        for c in list(m.offsets_list) + list(m.masks_list))
-                and all(tuple(c[0].padding) == (d, d) == tuple(c[0].dilation)
-                        for cs in (m.offsets_list, m.masks_list) for c, d in zip(cs, dils))
+                and all(plain_conv(c[0], 3, dil=d, groups=None) for cs in (m.offsets_list, m.masks_list) for c, d in zip(cs, dils))
                 and all(tuple(mm.deform_conv.weight.shape) == (J, J, 3, 3) and mm.deform_conv.deformable_groups == J
                         and mm.deform_conv.groups == 1 and _pair(mm.deform_conv.stride) == (1, 1)
                         and _pair(mm.deform_conv.padding) == (d, d) == _pair(mm.deform_conv.dilation)
@@ -1184,7 +1178,7 @@ class InferenceEngine:
         process saw a value beyond a half's range, the heat-maps leave as NaN instead of as finite numbers computed from an
         overflowed operand (the host side raises: :meth:`run`, :meth:`check_range`)."""
         B, J, h, w = self.B, self.J, self.h, self.w
-        if self.use_x3 or getattr(self, "h16", False):
+        if self.use_x3 or self.h16:
             self.call(self.lib.otp_range_poison, "otp_range_poison", hip.ptr(out), out.numel())
         self.outputs = (out, rough, inter, prev_b, ctx.view(B, J, h, w), squeezed, total)
         torch.cuda.synchronize(self.dev)
@@ -1217,10 +1211,8 @@ class InferenceEngine:
 
     def copy_into(self, src: View, dst: View):
         """dst channels <- src (per-sample strided copy through the upsample kernel with f = 1)."""
-        n, _, h, w = src.t.shape
         assert src.coff == 0 and src.C == src.ctot
-        self.call(self.lib.otp_upsample_linear, "otp_upsample_linear", hip.ptr(src.t), hip.ptr(dst.t), n, src.C, h * w, 1,
-                  dst.ctot, dst.coff)
+        self.call(self.lib.otp_upsample_linear, "otp_upsample_linear", *ops.upsample_linear_args(src.t, dst.t, 1, dst.coff))
 
     # ---------------------------------------------------------------------------------------------
     def _launch_all(self, first=0, last=None):

@@ -366,6 +366,24 @@ class View:
         return self.t.shape[1]
 
 
+# ---- launch arguments ------------------------------------------------------------------------------------------------------
+# One ``*_args`` function per C entry point states its positional arguments (without the trailing stream) once: the eager
+# wrappers below launch ``fn(*args, stream)`` at once, the inference engine records the same tuple for its launch list.
+def _vp(v):
+    """Device pointer of the tensor behind a :class:`View` / :class:`H8` (``None`` -> NULL)."""
+    return None if v is None else hip.ptr(v.t)
+
+
+def _slice(v):
+    """(total channels, channel offset) of an optional :class:`View` / (groups, group offset) of an :class:`H8`."""
+    return (0, 0) if v is None else (v.gtot, v.goff) if isinstance(v, H8) else (v.ctot, v.coff)
+
+
+def _launch(fn, name, args, t, stream=None):
+    """Launch now, on ``stream`` or on the stream PyTorch is enqueuing on for tensor ``t``'s device."""
+    hip.check(fn(*args, stream if stream is not None else hip.stream_of(t)), name)
+
+
 def pack_conv_weight(weight):
     """(Cout, Cin, kh, kw) -> packed [kh*kw][Cin][Cout16] device tensor for :func:`conv2d`."""
     _require_gpu(weight)
@@ -409,11 +427,12 @@ def conv_desc(inp: View, out: View, cout, kh, kw, stride, pad, dil, act=ACT_NONE
     return d
 
 
+def conv2d_args(inp: View, wpacked, scale, shift, out: View, desc, in2: View = None, res: View = None):
+    return (_vp(inp), _vp(in2), hip.ptr(wpacked), hip.ptr(scale), hip.ptr(shift), _vp(res), _vp(out), desc)
+
+
 def conv2d_launch(inp: View, wpacked, scale, shift, out: View, desc, in2: View = None, res: View = None, stream=None):
-    st = hip.lib().otp_conv2d(hip.ptr(inp.t), hip.ptr(in2.t if in2 is not None else None), hip.ptr(wpacked),
-                              hip.ptr(scale), hip.ptr(shift), hip.ptr(res.t if res is not None else None),
-                              hip.ptr(out.t), desc, stream if stream is not None else hip.stream_of(out.t))
-    hip.check(st, "otp_conv2d")
+    _launch(hip.lib().otp_conv2d, "otp_conv2d", conv2d_args(inp, wpacked, scale, shift, out, desc, in2, res), out.t, stream)
 
 
 def pack_wino_weight(weight):
@@ -447,6 +466,10 @@ def pack_small_conv_weight(weight):
     return wt
 
 
+def conv3x3_small_args(inp: View, in2: View, wpacked, scale, shift, out: View, desc):
+    return (_vp(inp), _vp(in2), hip.ptr(wpacked), hip.ptr(scale), hip.ptr(shift), _vp(out), desc)
+
+
 def conv3x3_small(x, weight, scale=None, shift=None, act=ACT_NONE, in2=None):
     """act(scale * conv2d(x (+ in2), weight, 3x3, stride 1, pad 1) + shift) for <= 24 channels (csrc/conv_small.hip)."""
     _require_gpu(x, weight)
@@ -458,8 +481,7 @@ def conv3x3_small(x, weight, scale=None, shift=None, act=ACT_NONE, in2=None):
     i2 = View(in2.contiguous()) if in2 is not None else None
     d = conv_desc(iv, ov, cout, 3, 3, 1, 1, 1, act, i2)
     wt = pack_small_conv_weight(weight)
-    hip.check(hip.lib().otp_conv3x3_small(hip.ptr(iv.t), hip.ptr(i2.t if i2 is not None else None), hip.ptr(wt), hip.ptr(scale),
-                                          hip.ptr(shift), hip.ptr(out), d, hip.stream_of(x)), "otp_conv3x3_small")
+    _launch(hip.lib().otp_conv3x3_small, "otp_conv3x3_small", conv3x3_small_args(iv, i2, wt, scale, shift, ov, d), x)
     return out
 
 
@@ -519,10 +541,12 @@ def x3_supported(desc) -> bool:
     return bool(hip.lib().otp_conv2d_x3_supported(desc))
 
 
+def conv2d_x3_args(inp: View, wpacked, shift, out: View, desc, res: View = None):
+    return (_vp(inp), hip.ptr(wpacked), hip.ptr(shift), _vp(res), _vp(out), desc)
+
+
 def conv2d_x3_launch(inp: View, wpacked, shift, out: View, desc, res: View = None, stream=None):
-    st = hip.lib().otp_conv2d_x3(hip.ptr(inp.t), hip.ptr(wpacked), hip.ptr(shift), hip.ptr(res.t if res is not None else None),
-                                 hip.ptr(out.t), desc, stream if stream is not None else hip.stream_of(out.t))
-    hip.check(st, "otp_conv2d_x3")
+    _launch(hip.lib().otp_conv2d_x3, "otp_conv2d_x3", conv2d_x3_args(inp, wpacked, shift, out, desc, res), out.t, stream)
 
 
 def conv2d_x3(x, weight, scale=None, shift=None, act=ACT_NONE, res=None, pad=1, dil=1, stride=1):
@@ -592,34 +616,32 @@ def s8_conv_supported(desc) -> bool:
     return bool(hip.lib().otp_conv3x3_s8_supported(desc))
 
 
-def s8_conv_desc(n, cin, cout, h, w, act=ACT_NONE, out: View = None):
+def s8_conv_desc(n, cin, cout, h, w, act=ACT_NONE, out: View = None, res: View = None, stride=1):
+    """Descriptor of the S8 convolutions: 3x3, pad 1, (n, cin, h, w) -> (n, cout, h / stride, w / stride)."""
     d = hip.ConvDesc()
     d.N, d.Cin, d.H, d.W, d.Cout = n, cin, h, w, cout
     d.kh = d.kw = 3
-    d.stride, d.pad, d.dil = 1, 1, 1
+    d.stride, d.pad, d.dil = stride, 1, 1
     d.in_ctot, d.in_coff, d.in2_ctot, d.in2_coff = cin, 0, 0, 0
     d.out_ctot, d.out_coff = (out.ctot, out.coff) if out is not None else (cout, 0)
-    d.res_ctot, d.res_coff, d.res_up = 0, 0, 1
-    d.act, d.Ho, d.Wo, d.frame_split = act, h, w, 0
+    d.res_ctot, d.res_coff = (res.ctot, res.coff) if res is not None else (0, 0)
+    d.res_up = 1
+    d.act, d.Ho, d.Wo, d.frame_split = act, h // stride, w // stride, 0
     return d
 
 
 def s8_s2_conv_desc(n, cin, cout, h, w, act=ACT_NONE, out: View = None, res: View = None):
     """Descriptor of the stride-2 S8 convolution (csrc/convs2.hip): (n, cin, h, w) -> (n, cout, h / 2, w / 2)."""
-    d = hip.ConvDesc()
-    d.N, d.Cin, d.H, d.W, d.Cout = n, cin, h, w, cout
-    d.kh = d.kw = 3
-    d.stride, d.pad, d.dil = 2, 1, 1
-    d.in_ctot, d.in_coff, d.in2_ctot, d.in2_coff = cin, 0, 0, 0
-    d.out_ctot, d.out_coff = (out.ctot, out.coff) if out is not None else (cout, 0)
-    d.res_ctot, d.res_coff = (res.ctot, res.coff) if res is not None else (0, 0)
-    d.res_up = 1
-    d.act, d.Ho, d.Wo, d.frame_split = act, h // 2, w // 2, 0
-    return d
+    return s8_conv_desc(n, cin, cout, h, w, act, out, res, stride=2)
 
 
 def s8_s2_conv_supported(desc, nchw_out=True):
     return bool(hip.lib().otp_conv3x3_s2_s8_supported(desc, int(nchw_out)))
+
+
+def conv3x3_s2_s8_args(in_s8, wpacked, shift, desc, res: View = None, out: View = None, out_s8=None):
+    """``out``: the fp32 NCHW result (with the optional residual ``res``), or ``out_s8``: its S8 image (csrc/convs2.hip)."""
+    return (hip.ptr(in_s8), hip.ptr(wpacked), hip.ptr(shift), _vp(res), _vp(out), hip.ptr(out_s8), desc)
 
 
 def conv3x3_s2_s8(x_s8, shape, weight, scale=None, shift=None, act=ACT_NONE, res=None, out="nchw"):
@@ -638,15 +660,13 @@ def conv3x3_s2_s8(x_s8, shape, weight, scale=None, shift=None, act=ACT_NONE, res
         d = s8_s2_conv_desc(n, cin, cout, h, w, act)
         d.out_scale = 2.0 ** -e
         o8 = s8_empty(n, cout, h // 2, w // 2, x_s8.device)
-        hip.check(L.otp_conv3x3_s2_s8(hip.ptr(x_s8), hip.ptr(wp), hip.ptr(sh), None, None, hip.ptr(o8), d, hip.stream_of(x_s8)),
-                  "otp_conv3x3_s2_s8")
+        _launch(L.otp_conv3x3_s2_s8, "otp_conv3x3_s2_s8", conv3x3_s2_s8_args(x_s8, wp, sh, d, out_s8=o8), x_s8)
         return o8
     o = torch.empty(n, cout, h // 2, w // 2, dtype=torch.float32, device=x_s8.device)
     rv = View(res.contiguous()) if res is not None else None
     d = s8_s2_conv_desc(n, cin, cout, h, w, act, View(o), rv)
     d.out_scale = 2.0 ** -e
-    hip.check(L.otp_conv3x3_s2_s8(hip.ptr(x_s8), hip.ptr(wp), hip.ptr(sh), hip.ptr(rv.t) if rv is not None else None, hip.ptr(o),
-                                  None, d, hip.stream_of(x_s8)), "otp_conv3x3_s2_s8")
+    _launch(L.otp_conv3x3_s2_s8, "otp_conv3x3_s2_s8", conv3x3_s2_s8_args(x_s8, wp, sh, d, rv, View(o)), x_s8)
     return o
 
 
@@ -669,10 +689,14 @@ def pack_s8_weight(weight, scale=None, k=0):
     return u
 
 
+def conv3x3_s8_args(in_s8, wpacked, shift, desc, res=None, out_f32=None, f32_layout=S8_F32_C4, out_s8=None):
+    """``res``: the residual's C4 image, or its S8 image with ``desc.res_layout = 1``; ``out_f32``: a C4 image or an NCHW tensor."""
+    return (hip.ptr(in_s8), hip.ptr(wpacked), hip.ptr(shift), hip.ptr(res), hip.ptr(out_f32), f32_layout, hip.ptr(out_s8), desc)
+
+
 def conv3x3_s8_launch(in_s8, wpacked, shift, desc, res_c4=None, out_f32=None, f32_layout=S8_F32_C4, out_s8=None, stream=None):
-    st = hip.lib().otp_conv3x3_s8(hip.ptr(in_s8), hip.ptr(wpacked), hip.ptr(shift), hip.ptr(res_c4), hip.ptr(out_f32),
-                                  f32_layout, hip.ptr(out_s8), desc, stream if stream is not None else hip.stream_of(in_s8))
-    hip.check(st, "otp_conv3x3_s8")
+    _launch(hip.lib().otp_conv3x3_s8, "otp_conv3x3_s8",
+            conv3x3_s8_args(in_s8, wpacked, shift, desc, res_c4, out_f32, f32_layout, out_s8), in_s8, stream)
 
 
 def conv3x3_s8(x_s8, shape, weight, scale=None, shift=None, act=ACT_NONE, res_c4=None, f32="nchw", want_s8=True, res_s8=None):
@@ -701,17 +725,20 @@ def conv3x3_s8(x_s8, shape, weight, scale=None, shift=None, act=ACT_NONE, res_c4
     return out, out_s8
 
 
-def ln_mlp_fused(y, gamma, beta, eps, packed, scale, shift, out=None, hid=None, stream=None):
+def ln_mlp_args(y, gamma, beta, eps, packed, scale, shift, out, hid):
+    """Arguments of otp_ln_mlp_fused / otp_ln_mlp_x3 / otp_ln_mlp_h1 on a (B, C, T) tensor."""
+    b, c, t = y.shape
+    return (hip.ptr(y), hip.ptr(gamma), hip.ptr(beta), eps, hip.ptr(packed), hip.ptr(scale), hip.ptr(shift), hip.ptr(out), b, c, hid, t)
+
+
+def ln_mlp_fused(y, gamma, beta, eps, packed, scale, shift, out=None, hid=None, stream=None, entry="otp_ln_mlp_fused"):
     """out = y + scale * (W2 . gelu(W1 . LN(y) + b1)) + shift: ln2 + MLP + residual of TransformerBlock.forward
     (model/blocks.py:277-279) in one launch."""
     _require_gpu(y, packed)
     _check_f32(y)
-    b, c, t = y.shape
-    hid = 4 * c if hid is None else hid
+    hid = 4 * y.shape[1] if hid is None else hid
     out = torch.empty_like(y) if out is None else out
-    hip.check(hip.lib().otp_ln_mlp_fused(hip.ptr(y), hip.ptr(gamma), hip.ptr(beta), eps, hip.ptr(packed), hip.ptr(scale),
-                                         hip.ptr(shift), hip.ptr(out), b, c, hid, t,
-                                         stream if stream is not None else hip.stream_of(y)), "otp_ln_mlp_fused")
+    _launch(getattr(hip.lib(), entry), entry, ln_mlp_args(y, gamma, beta, eps, packed, scale, shift, out, hid), y, stream)
     return out
 
 
@@ -782,6 +809,12 @@ def pack_stem_conv_x3(weight, scale=None, shift=None):
     return packed
 
 
+def stem_conv_x3_args(clip, packed, out, frames, cout):
+    """Arguments of otp_stem_conv_x3 / otp_h16_stem: ``clip`` (B, 3 * frames, H, W) fp32, ``out`` a tensor or an :class:`H8`."""
+    b, _, h, w = clip.shape
+    return (hip.ptr(clip), hip.ptr(packed), hip.ptr(out.t if isinstance(out, H8) else out), b, frames, h, w, cout)
+
+
 def stem_conv_x3(clip, packed, cout, frames=5, out=None, stream=None):
     """relu(bn(conv3x3 stride 2 pad 1)) of the 3-channel frames of ``clip`` (B, 3 * frames, H, W) -> (frames * B, cout, Ho, Wo),
     frame-major like model/OTPose.py:317."""
@@ -790,8 +823,7 @@ def stem_conv_x3(clip, packed, cout, frames=5, out=None, stream=None):
     assert c == 3 * frames and clip.is_contiguous() and clip.dtype == torch.float32
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     out = torch.empty(frames * b, cout, ho, wo, dtype=torch.float32, device=clip.device) if out is None else out
-    hip.check(hip.lib().otp_stem_conv_x3(hip.ptr(clip), hip.ptr(packed), hip.ptr(out), b, frames, h, w, cout,
-                                         stream if stream is not None else hip.stream_of(clip)), "otp_stem_conv_x3")
+    _launch(hip.lib().otp_stem_conv_x3, "otp_stem_conv_x3", stem_conv_x3_args(clip, packed, out, frames, cout), clip, stream)
     return out
 
 
@@ -799,35 +831,41 @@ def pointwise_x3_supported(cin, cout, t) -> bool:
     return bool(hip.lib().otp_pointwise_x3_supported(int(cin), int(cout), int(t)))
 
 
-def pack_pointwise_x3(weight, scale=None, shift=None):
-    """(Cout, Cin[, 1, 1]) weight (+ per-output-channel scale / shift, e.g. a folded BatchNorm) -> the block image of
-    :func:`pointwise_x3` (HRNet layer1's 1x1 convs, model/HRNet.py:551-571)."""
+def _pack_pointwise(entry, weight, scale, shift):
+    """(Cout, Cin[, 1, 1]) weight (+ per-output-channel scale / shift) -> the image ``<entry>_pack`` writes."""
     _require_gpu(weight)
     cout, cin = weight.shape[:2]
     L = hip.lib()
-    nbytes = L.otp_pointwise_x3_weight_bytes(cin, cout)
+    nbytes = getattr(L, entry + "_weight_bytes")(cin, cout)
     if not nbytes:
-        raise RuntimeError(f"otp_pointwise_x3: unsupported weight shape {tuple(weight.shape)}")
+        raise RuntimeError(f"{entry}: unsupported weight shape {tuple(weight.shape)}")
     f = lambda t: None if t is None else t.detach().to(weight.device, torch.float32).contiguous()   # noqa: E731
     w, sc, sh = f(weight).reshape(cout, cin), f(scale), f(shift)
     e = x3_weight_exponent(w)                     # weights stored times 2^e, undone by the kernel's per-channel epilogue scale
     if e:
         w, sc = w * float(2.0 ** e), _scaled_vec(sc, -e, cout, w.device)
     packed = torch.empty(nbytes // 4, dtype=torch.float32, device=weight.device)
-    hip.check(L.otp_pointwise_x3_pack(hip.ptr(w), hip.ptr(sc), hip.ptr(sh), hip.ptr(packed), cin, cout, hip.stream_of(w)),
-              "otp_pointwise_x3_pack")
+    hip.check(getattr(L, entry + "_pack")(hip.ptr(w), hip.ptr(sc), hip.ptr(sh), hip.ptr(packed), cin, cout, hip.stream_of(w)),
+              entry + "_pack")
     return packed
+
+
+def pack_pointwise_x3(weight, scale=None, shift=None):
+    """(Cout, Cin[, 1, 1]) weight (+ per-output-channel scale / shift, e.g. a folded BatchNorm) -> the block image of
+    :func:`pointwise_x3` (HRNet layer1's 1x1 convs, model/HRNet.py:551-571)."""
+    return _pack_pointwise("otp_pointwise_x3", weight, scale, shift)
+
+
+def pointwise_x3_args(x: View, packed, out: View, res: View = None, relu=False):
+    b, _, h, w = x.t.shape
+    return (_vp(x), hip.ptr(packed), _vp(res), _vp(out), b, x.C, out.C, h * w, x.ctot, x.coff, *_slice(res), out.ctot, out.coff,
+            int(bool(relu)))
 
 
 def pointwise_x3(x: View, packed, out: View, res: View = None, relu=False, stream=None):
     """out = act(scale * (W . x) + shift (+ res)) over channel-slice views of (B, ctot, H, W) fp32 tensors."""
     _require_gpu(x.t, out.t)
-    b = x.t.shape[0]
-    t = x.t.shape[2] * x.t.shape[3]
-    hip.check(hip.lib().otp_pointwise_x3(hip.ptr(x.t), hip.ptr(packed), hip.ptr(res.t if res is not None else None), hip.ptr(out.t),
-                                         b, x.C, out.C, t, x.ctot, x.coff, res.ctot if res is not None else 0,
-                                         res.coff if res is not None else 0, out.ctot, out.coff, int(bool(relu)),
-                                         stream if stream is not None else hip.stream_of(x.t)), "otp_pointwise_x3")
+    _launch(hip.lib().otp_pointwise_x3, "otp_pointwise_x3", pointwise_x3_args(x, packed, out, res, relu), x.t, stream)
     return out
 
 
@@ -837,21 +875,12 @@ def pointwise_x3_s8_supported(cin, cout, t) -> bool:
 
 def pack_pointwise_x3_s8(weight, scale=None, shift=None):
     """Weight image of :func:`pointwise_x3_s8` (its own row order: pairs of 16-row tiles interleaved by groups of 4)."""
-    _require_gpu(weight)
-    cout, cin = weight.shape[:2]
-    L = hip.lib()
-    nbytes = L.otp_pointwise_x3_s8_weight_bytes(cin, cout)
-    if not nbytes:
-        raise RuntimeError(f"otp_pointwise_x3_s8: unsupported weight shape {tuple(weight.shape)}")
-    f = lambda t: None if t is None else t.detach().to(weight.device, torch.float32).contiguous()   # noqa: E731
-    w, sc, sh = f(weight).reshape(cout, cin), f(scale), f(shift)
-    e = x3_weight_exponent(w)                     # weights stored times 2^e, undone by the kernel's per-channel epilogue scale
-    if e:
-        w, sc = w * float(2.0 ** e), _scaled_vec(sc, -e, cout, w.device)
-    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=weight.device)
-    hip.check(L.otp_pointwise_x3_s8_pack(hip.ptr(w), hip.ptr(sc), hip.ptr(sh), hip.ptr(packed), cin, cout, hip.stream_of(w)),
-              "otp_pointwise_x3_s8_pack")
-    return packed
+    return _pack_pointwise("otp_pointwise_x3_s8", weight, scale, shift)
+
+
+def pointwise_x3_s8_res_args(x: View, packed, cout, out_s8, res: View = None, relu=False):
+    b, _, h, w = x.t.shape
+    return (_vp(x), hip.ptr(packed), _vp(res), hip.ptr(out_s8), b, x.C, cout, h * w, x.ctot, x.coff, *_slice(res), int(bool(relu)))
 
 
 def pointwise_x3_s8(x: View, packed, cout, out_s8=None, relu=False, stream=None, res: View = None):
@@ -860,11 +889,8 @@ def pointwise_x3_s8(x: View, packed, cout, out_s8=None, relu=False, stream=None,
     _require_gpu(x.t)
     b, _, h, w = x.t.shape
     out_s8 = s8_empty(b, cout, h, w, x.t.device) if out_s8 is None else out_s8
-    hip.check(hip.lib().otp_pointwise_x3_s8_res(hip.ptr(x.t), hip.ptr(packed), hip.ptr(res.t if res is not None else None),
-                                                hip.ptr(out_s8), b, x.C, cout, h * w, x.ctot, x.coff,
-                                                res.ctot if res is not None else 0, res.coff if res is not None else 0,
-                                                int(bool(relu)), stream if stream is not None else hip.stream_of(x.t)),
-              "otp_pointwise_x3_s8")
+    _launch(hip.lib().otp_pointwise_x3_s8_res, "otp_pointwise_x3_s8", pointwise_x3_s8_res_args(x, packed, cout, out_s8, res, relu),
+            x.t, stream)
     return out_s8
 
 
@@ -896,17 +922,20 @@ def pack_pointwise_x3_pair(weight1, scale1, shift1, weight2, scale2=None, shift2
     return packed
 
 
+def pointwise_x3_pair_args(x: View, packed, out: View, cout2, out_s8, res: View = None, relu1=True, relu2=True):
+    b, _, h, w = x.t.shape
+    return (_vp(x), hip.ptr(packed), _vp(res), _vp(out), hip.ptr(out_s8), b, x.C, out.C, cout2, h * w, x.ctot, x.coff, *_slice(res),
+            out.ctot, out.coff, int(bool(relu1)), int(bool(relu2)))
+
+
 def pointwise_x3_pair(x: View, packed, out: View, cout2, res: View = None, out_s8=None, relu1=True, relu2=True, stream=None):
     """out = act1(scale1 * (W1 . x) + shift1 (+ res)) as :func:`pointwise_x3` writes it AND the S8 image of
     act2(scale2 * (W2 . out) + shift2) as :func:`pointwise_x3_s8` of ``out`` writes it, in one launch; returns the S8 image."""
     _require_gpu(x.t, out.t)
     b, _, h, w = x.t.shape
     out_s8 = s8_empty(b, cout2, h, w, x.t.device) if out_s8 is None else out_s8
-    hip.check(hip.lib().otp_pointwise_x3_pair(hip.ptr(x.t), hip.ptr(packed), hip.ptr(res.t if res is not None else None),
-                                              hip.ptr(out.t), hip.ptr(out_s8), b, x.C, out.C, cout2, h * w, x.ctot, x.coff,
-                                              res.ctot if res is not None else 0, res.coff if res is not None else 0, out.ctot,
-                                              out.coff, int(bool(relu1)), int(bool(relu2)),
-                                              stream if stream is not None else hip.stream_of(x.t)), "otp_pointwise_x3_pair")
+    _launch(hip.lib().otp_pointwise_x3_pair, "otp_pointwise_x3_pair",
+            pointwise_x3_pair_args(x, packed, out, cout2, out_s8, res, relu1, relu2), x.t, stream)
     return out_s8
 
 
@@ -923,15 +952,19 @@ def pack_qkv_table(dwq, dwk, dwv, gq, bq, gk, bk, gv, bv):
     return table
 
 
+def qkv_front_args(x, table, packs, outs, eps):
+    """Arguments of otp_qkv_front / otp_qkv_front_x3 / otp_qkv_front_h1."""
+    b, c, t = x.shape
+    return (hip.ptr(x), hip.ptr(table), *[hip.ptr(p) for p in packs], *[hip.ptr(o) for o in outs], b, c, t, eps)
+
+
 def qkv_front(x, table, packs, eps=1e-5, outs=None, stream=None, x3=False, half=False):
     """q, k, v = W_p . LN_p(dwconv3_p(x)) + b_p (stride 1) in one launch; ``packs`` = three :func:`pack_dense_cc` images
     (``half`` with ``x3``: operands rounded to half once, otp_qkv_front_h1)."""
     _require_gpu(x, table)
-    b, c, t = x.shape
     outs = [torch.empty_like(x) for _ in range(3)] if outs is None else outs
     fn = (hip.lib().otp_qkv_front_h1 if half else hip.lib().otp_qkv_front_x3) if x3 else hip.lib().otp_qkv_front
-    hip.check(fn(hip.ptr(x), hip.ptr(table), *[hip.ptr(p) for p in packs], *[hip.ptr(o) for o in outs],
-                 b, c, t, eps, stream if stream is not None else hip.stream_of(x)), "otp_qkv_front")
+    _launch(fn, "otp_qkv_front", qkv_front_args(x, table, packs, outs, eps), x, stream)
     return outs
 
 
@@ -955,7 +988,7 @@ def pack_mlp_weights(w1, b1, w2):
     return packed
 
 
-def mlp_fused(x, packed, scale, shift, res, out=None, hid=None, stream=None):
+def mlp_fused(x, packed, scale, shift, res, out=None, hid=None, stream=None, entry="otp_mlp_fused"):
     """out = res + scale * (W2 . gelu(W1 . x + b1)) + shift on (B, C, T) tensors, one launch (eval-mode MLP half of
     TransformerBlock.forward, model/blocks.py:277-279)."""
     _require_gpu(x, packed, res)
@@ -963,9 +996,8 @@ def mlp_fused(x, packed, scale, shift, res, out=None, hid=None, stream=None):
     b, c, t = x.shape
     hid = 4 * c if hid is None else hid
     out = torch.empty_like(x) if out is None else out
-    hip.check(hip.lib().otp_mlp_fused(hip.ptr(x), hip.ptr(packed), hip.ptr(scale), hip.ptr(shift), hip.ptr(res),
-                                      hip.ptr(out), b, c, hid, t, stream if stream is not None else hip.stream_of(x)),
-              "otp_mlp_fused")
+    _launch(getattr(hip.lib(), entry), entry, (hip.ptr(x), hip.ptr(packed), hip.ptr(scale), hip.ptr(shift), hip.ptr(res), hip.ptr(out),
+                                                b, c, hid, t), x, stream)
     return out
 
 
@@ -1033,40 +1065,24 @@ def pack_mlp_x3_weights(w1, b1, w2, half=False):
 
 def mlp_x3(x, packed, scale, shift, res, out=None, hid=None, stream=None):
     """:func:`mlp_fused` with split-half products on the 16-bit matrix cores (fp32 storage / accumulation)."""
-    _require_gpu(x, packed, res)
-    _check_f32(x)
-    b, c, t = x.shape
-    hid = 4 * c if hid is None else hid
-    out = torch.empty_like(x) if out is None else out
-    hip.check(hip.lib().otp_mlp_x3(hip.ptr(x), hip.ptr(packed), hip.ptr(scale), hip.ptr(shift), hip.ptr(res),
-                                   hip.ptr(out), b, c, hid, t, stream if stream is not None else hip.stream_of(x)),
-              "otp_mlp_x3")
-    return out
+    return mlp_fused(x, packed, scale, shift, res, out, hid, stream, "otp_mlp_x3")
 
 
 def ln_mlp_x3(y, gamma, beta, eps, packed, scale, shift, out=None, hid=None, stream=None, half=False):
     """:func:`ln_mlp_fused` with split-half products (``half``: operands and the hidden layer rounded to half once, otp_ln_mlp_h1)."""
-    _require_gpu(y, packed)
-    _check_f32(y)
-    b, c, t = y.shape
-    hid = 4 * c if hid is None else hid
-    out = torch.empty_like(y) if out is None else out
-    fn = hip.lib().otp_ln_mlp_h1 if half else hip.lib().otp_ln_mlp_x3
-    hip.check(fn(hip.ptr(y), hip.ptr(gamma), hip.ptr(beta), eps, hip.ptr(packed), hip.ptr(scale),
-                                      hip.ptr(shift), hip.ptr(out), b, c, hid, t,
-                                      stream if stream is not None else hip.stream_of(y)), "otp_ln_mlp_x3")
-    return out
+    return ln_mlp_fused(y, gamma, beta, eps, packed, scale, shift, out, hid, stream, "otp_ln_mlp_h1" if half else "otp_ln_mlp_x3")
 
 
 def wino_supported(desc) -> bool:
     return bool(hip.lib().otp_conv2d_wino_supported(desc))
 
 
+def conv2d_wino_args(inp: View, upacked, scale, shift, out: View, desc, res: View = None):
+    return (_vp(inp), hip.ptr(upacked), hip.ptr(scale), hip.ptr(shift), _vp(res), _vp(out), desc)
+
+
 def conv2d_wino_launch(inp: View, upacked, scale, shift, out: View, desc, res: View = None, stream=None):
-    st = hip.lib().otp_conv2d_wino(hip.ptr(inp.t), hip.ptr(upacked), hip.ptr(scale), hip.ptr(shift),
-                                   hip.ptr(res.t if res is not None else None), hip.ptr(out.t), desc,
-                                   stream if stream is not None else hip.stream_of(out.t))
-    hip.check(st, "otp_conv2d_wino")
+    _launch(hip.lib().otp_conv2d_wino, "otp_conv2d_wino", conv2d_wino_args(inp, upacked, scale, shift, out, desc, res), out.t, stream)
 
 
 def conv2d_wino(x, weight, scale=None, shift=None, act=ACT_NONE, res=None):
@@ -1098,15 +1114,25 @@ def conv2d(x, weight, scale=None, shift=None, stride=1, pad=0, dil=1, act=ACT_NO
     return out
 
 
+def upsample_add_args(low: View, res: View, out: View, f, relu=False):
+    n, _, hl, wl = low.t.shape
+    return (_vp(low), _vp(res), _vp(out), n, low.C, hl, wl, f, int(relu), low.ctot, low.coff, res.ctot, res.coff, out.ctot, out.coff)
+
+
 def upsample_add(low, res, f, relu=False, out=None):
     """out = act(res + nearest_upsample_f(low)) (HRNet fuse accumulate for f >= 4); ``out`` may be ``res``."""
     _require_gpu(low, res)
-    n, c, hl, wl = low.shape
-    if out is None:
-        out = torch.empty_like(res)
-    hip.check(hip.lib().otp_upsample_add(hip.ptr(low), hip.ptr(res), hip.ptr(out), n, c, hl, wl, f, int(relu),
-                                         c, 0, c, 0, c, 0, hip.stream_of(low)), "otp_upsample_add")
+    out = torch.empty_like(res) if out is None else out
+    _launch(hip.lib().otp_upsample_add, "otp_upsample_add", upsample_add_args(View(low), View(res), View(out), f, relu), low)
     return out
+
+
+def upsample_add_multi_args(lows, factors, res: View, out: View, relu=False):
+    """(arguments, ctypes arrays the caller keeps alive while the launch may still be issued); ``lows``: whole-tensor Views."""
+    n, _, hh, wh = out.t.shape
+    lp = (ctypes.c_void_p * len(lows))(*[_vp(v) for v in lows])
+    fp = (ctypes.c_int * len(lows))(*[int(f) for f in factors])
+    return (lp, fp, len(lows), _vp(res), _vp(out), n, res.C, hh, wh, int(relu), res.ctot, res.coff, out.ctot, out.coff), (lp, fp)
 
 
 def upsample_add_multi(lows, res, relu=False, out=None):
@@ -1116,10 +1142,8 @@ def upsample_add_multi(lows, res, relu=False, out=None):
     n, c, hh, wh = res.shape
     out = torch.empty_like(res) if out is None else out
     lows = [t.contiguous() for t in lows]
-    lp = (ctypes.c_void_p * len(lows))(*[hip.ptr(t) for t in lows])
-    fp = (ctypes.c_int * len(lows))(*[hh // t.shape[2] for t in lows])
-    hip.check(hip.lib().otp_upsample_add_multi(lp, fp, len(lows), hip.ptr(res), hip.ptr(out), n, c, hh, wh, int(relu),
-                                               c, 0, c, 0, hip.stream_of(res)), "otp_upsample_add_multi")
+    args, _keep = upsample_add_multi_args([View(t) for t in lows], [hh // t.shape[2] for t in lows], View(res), View(out), relu)
+    _launch(hip.lib().otp_upsample_add_multi, "otp_upsample_add_multi", args, res)
     return out
 
 
@@ -1146,6 +1170,11 @@ def dwconv_ln3(x, dw, gammas, betas, stride, eps=1e-5):
     return outs
 
 
+def chan_attn_args(q, k, v, out, ws, nbytes, n_head, scale):
+    b, c, t = q.shape
+    return (hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(out), hip.ptr(ws), nbytes, b, c, t, n_head, scale)
+
+
 def chan_attn(q, k, v, n_head, scale):
     _require_gpu(q, k, v)
     b, c, t = q.shape
@@ -1153,9 +1182,14 @@ def chan_attn(q, k, v, n_head, scale):
     L = hip.lib()
     nbytes = L.otp_chan_attn_workspace(b, c, t, n_head)
     ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=q.device)
-    hip.check(L.otp_chan_attn(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(out), hip.ptr(ws), nbytes, b, c, t, n_head,
-                              scale, hip.stream_of(q)), "otp_chan_attn")
+    _launch(L.otp_chan_attn, "otp_chan_attn", chan_attn_args(q, k, v, out, ws, nbytes, n_head, scale), q)
     return out
+
+
+def upsample_linear_args(x, out, f, out_coff=0):
+    """``x`` (B, C, T) or (B, C, H, W) with T = H * W, written to channels [out_coff, out_coff + C) of ``out``."""
+    b, c = x.shape[:2]
+    return (hip.ptr(x), hip.ptr(out), b, c, x.numel() // (b * c), f, out.shape[1], out_coff)
 
 
 def upsample_linear(x, f, out=None, out_coff=0):
@@ -1163,8 +1197,7 @@ def upsample_linear(x, f, out=None, out_coff=0):
     b, c, t = x.shape
     if out is None:
         out = torch.empty((b, c, t * f), dtype=x.dtype, device=x.device)
-    hip.check(hip.lib().otp_upsample_linear(hip.ptr(x), hip.ptr(out), b, c, t, f, out.shape[1], out_coff,
-                                            hip.stream_of(x)), "otp_upsample_linear")
+    _launch(hip.lib().otp_upsample_linear, "otp_upsample_linear", upsample_linear_args(x, out, f, out_coff), x)
     return out
 
 
@@ -1715,15 +1748,23 @@ def pack_flow_back(blk, device):
     return prm
 
 
+def flow_front_args(x, prm, q, k, v, eps):
+    b, c, t = x.shape
+    return (hip.ptr(x), hip.ptr(prm), hip.ptr(q), hip.ptr(k), hip.ptr(v), b, c, t, float(eps))
+
+
+def flow_back_args(x, att, prm, out, hidden, eps):
+    b, c, t = x.shape
+    return (hip.ptr(x), hip.ptr(att), hip.ptr(prm), hip.ptr(out), b, c, int(hidden), t, float(eps))
+
+
 def flow_front(x, prm, eps=1e-5):
     """q, k, v of a flow-encoder block from its input (B, 17, T)."""
     _require_gpu(x, prm)
     _check_f32(x)
     x = x.contiguous()
-    b, c, t = x.shape
     q, k, v = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
-    hip.check(hip.lib().otp_flow_front(hip.ptr(x), hip.ptr(prm), hip.ptr(q), hip.ptr(k), hip.ptr(v), b, c, t, float(eps),
-                                       hip.stream_of(x)), "otp_flow_front")
+    _launch(hip.lib().otp_flow_front, "otp_flow_front", flow_front_args(x, prm, q, k, v, eps), x)
     return q, k, v
 
 
@@ -1732,10 +1773,8 @@ def flow_back(x, att, prm, hidden, eps=1e-5):
     _require_gpu(x, att, prm)
     _check_f32(x)
     x, att = x.contiguous(), att.contiguous()
-    b, c, t = x.shape
     out = torch.empty_like(x)
-    hip.check(hip.lib().otp_flow_back(hip.ptr(x), hip.ptr(att), hip.ptr(prm), hip.ptr(out), b, c, int(hidden), t, float(eps),
-                                      hip.stream_of(x)), "otp_flow_back")
+    _launch(hip.lib().otp_flow_back, "otp_flow_back", flow_back_args(x, att, prm, out, hidden, eps), x)
     return out
 
 
@@ -1827,13 +1866,16 @@ def pack_h16_conv_weight(weight, scale=None, k=0):
     return packed
 
 
+def h16_conv3x3_args(x: H8, wpacked, shift, out: H8, desc, res: H8 = None):
+    return (_vp(x), hip.ptr(wpacked), hip.ptr(shift), _vp(res), _vp(out), desc)
+
+
 def h16_conv3x3(x: H8, wpacked, shift, cout, stride=1, act=ACT_NONE, res: H8 = None, out: H8 = None, k=0, stream=None, desc=None):
     """out = act(conv3x3 pad 1 (x) + shift (+ res)) on H8 images (csrc/h16.hip)."""
     ho, wo = x.H // stride, x.W // stride
     out = h8_empty(x.N, cout, ho, wo, x.t.device) if out is None else out
     d = desc if desc is not None else h16_conv_desc(x, cout, stride, act, out, res, k)
-    hip.check(hip.lib().otp_h16_conv3x3(hip.ptr(x.t), hip.ptr(wpacked), hip.ptr(shift), hip.ptr(res.t if res is not None else None),
-                                        hip.ptr(out.t), d, stream if stream is not None else hip.stream_of(x.t)), "otp_h16_conv3x3")
+    _launch(hip.lib().otp_h16_conv3x3, "otp_h16_conv3x3", h16_conv3x3_args(x, wpacked, shift, out, d, res), x.t, stream)
     return out
 
 
@@ -1858,17 +1900,17 @@ def pack_h16_pointwise(weight, scale=None, shift=None, k=0):
     return packed
 
 
+def h16_pointwise_args(x: H8, packed, cout, out, relu=False, res: H8 = None, k=0):
+    """``out``: an :class:`H8`, or a :class:`View` of an fp32 NCHW tensor."""
+    return (_vp(x), hip.ptr(packed), _vp(res), _vp(out), int(isinstance(out, View)), x.N, x.C, cout, x.H * x.W, x.gtot, x.goff,
+            *_slice(res), *_slice(out), int(relu), float(2.0 ** -k))
+
+
 def h16_pointwise(x: H8, packed, cout, relu=False, res: H8 = None, out=None, k=0, stream=None):
     """out = act(W x + shift (+ res)): ``out`` an :class:`H8` (default: fresh) or a :class:`View` of an fp32 NCHW tensor."""
-    f32 = isinstance(out, View)
     if out is None:
         out = h8_empty(x.N, cout, x.H, x.W, x.t.device)
-    otot, ooff = (out.ctot, out.coff) if f32 else (out.gtot, out.goff)
-    hip.check(hip.lib().otp_h16_pointwise(hip.ptr(x.t), hip.ptr(packed), hip.ptr(res.t if res is not None else None), hip.ptr(out.t),
-                                          int(f32), x.N, x.C, cout, x.H * x.W, x.gtot, x.goff,
-                                          res.gtot if res is not None else 0, res.goff if res is not None else 0, otot, ooff,
-                                          int(relu), float(2.0 ** -k), stream if stream is not None else hip.stream_of(x.t)),
-              "otp_h16_pointwise")
+    _launch(hip.lib().otp_h16_pointwise, "otp_h16_pointwise", h16_pointwise_args(x, packed, cout, out, relu, res, k), x.t, stream)
     return out
 
 
@@ -1894,17 +1936,21 @@ def h16_stem(clip, packed, cout, frames, out: H8 = None, stream=None):
     assert c == 3 * frames and clip.is_contiguous()
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     out = h8_empty(frames * b, cout, ho, wo, clip.device) if out is None else out
-    hip.check(hip.lib().otp_h16_stem(hip.ptr(clip), hip.ptr(packed), hip.ptr(out.t), b, frames, h, w, cout,
-                                     stream if stream is not None else hip.stream_of(clip)), "otp_h16_stem")
+    _launch(hip.lib().otp_h16_stem, "otp_h16_stem", stem_conv_x3_args(clip, packed, out, frames, cout), clip, stream)
     return out
+
+
+def h16_upsample_add_args(lows, factors, res: H8, out: H8, relu=True):
+    """(arguments, ctypes arrays the caller keeps alive while the launch may still be issued) on dense H8 images."""
+    lp = (ctypes.c_void_p * len(lows))(*[_vp(v) for v in lows])
+    fp = (ctypes.c_int * len(lows))(*[int(f) for f in factors])
+    return (lp, fp, len(lows), _vp(res), _vp(out), res.N, res.C, res.H, res.W, int(relu)), (lp, fp)
 
 
 def h16_upsample_add(lows, factors, res: H8, relu=True, out: H8 = None, stream=None):
     """out = act(res + sum_k nearest_up(lows[k], factors[k])) on dense H8 images."""
     assert res.gtot * 8 == res.C and all(l.gtot * 8 == l.C for l in lows)
     out = h8_empty(res.N, res.C, res.H, res.W, res.t.device) if out is None else out
-    lp = (ctypes.c_void_p * len(lows))(*[hip.ptr(l.t) for l in lows])
-    fp = (ctypes.c_int * len(lows))(*[int(f) for f in factors])
-    hip.check(hip.lib().otp_h16_upsample_add(lp, fp, len(lows), hip.ptr(res.t), hip.ptr(out.t), res.N, res.C, res.H, res.W, int(relu),
-                                             stream if stream is not None else hip.stream_of(res.t)), "otp_h16_upsample_add")
+    args, _keep = h16_upsample_add_args(lows, factors, res, out, relu)
+    _launch(hip.lib().otp_h16_upsample_add, "otp_h16_upsample_add", args, res.t, stream)
     return out

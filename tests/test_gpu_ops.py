@@ -229,6 +229,20 @@ def test_rsb_chain_launches_match_golden(golden, tag, cin, cout, streams):
     _close(out.t, g[tag + "_y"], 5e-5)
 
 
+def test_bare_engine_reads_the_same_routes_as_a_full_one(monkeypatch):
+    """`InferenceEngine.bare` and `__init__` share one initialiser: a bare engine holds what `Routes.from_env()` reads (here with
+    one switch off its default), apart from the stream setting its caller chooses, and never captures a graph."""
+    import dataclasses
+    from otpose_amd.engine import InferenceEngine, Routes
+    monkeypatch.setenv("OTPOSE_SMALL_CONV", "0")
+    want = Routes.from_env()
+    assert not want.use_small_conv
+    for streams in (False, True):
+        eng = InferenceEngine.bare("cuda", multi_stream=streams)
+        assert eng.routes == dataclasses.replace(want, multi_stream=streams)
+        assert eng.multi_stream == streams and not eng.use_graph and eng.graph is None and eng.l1_pairs == 0
+
+
 def test_flow_encoder_block_matches_golden(golden):
     """The C = 17 TransformerBlock of the flow encoder as the engine runs it - otp_flow_front (ln1 + depthwise convs +
     LayerNorms + q / k / v projections), otp_chan_attn, otp_flow_back (proj + residual, ln2, MLP + residual) - against the

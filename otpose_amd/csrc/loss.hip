@@ -65,15 +65,16 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(const float* __restric
         sel[i] = 0;
     }
     __syncthreads();
-    // mse term: sum_j mean_{b,p}  (loss.py:52-64)
-    if (tid < J) {
-        float m = 0.f;
-        for (int b = 0; b < B; ++b) m += stats[(b * J + tid) * 3] + (fl[tid] ? 0.f : stats[(b * J + tid) * 3 + 1]);
-        mj[tid] = m / ((float)B * (float)HW);
+    // mse term: sum_j mean_{b,p}  (loss.py:52-64); a strided loop like joints_finish_kernel's: J may exceed the workgroup.
+    // The sums over B, J and topk terms of this kernel run in fp64 (a sequential fp32 sum of 300 terms loses several ulp).
+    for (int j = tid; j < J; j += blockDim.x) {
+        double m = 0.0;
+        for (int b = 0; b < B; ++b) m += (double)stats[(b * J + j) * 3] + (fl[j] ? 0.0 : (double)stats[(b * J + j) * 3 + 1]);
+        mj[j] = (float)(m / ((double)B * (double)HW));
     }
     // ohkm: per sample the k largest joint losses (loss.py:13-23); ties resolved by lower joint index
     for (int b = tid; b < B; b += blockDim.x) {
-        float sum = 0.f;
+        double sum = 0.0;
         for (int k = 0; k < topk; ++k) {
             int best = -1;
             float bv = -INFINITY;
@@ -81,20 +82,20 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(const float* __restric
                 if (!sel[b * J + j] && l[b * J + j] > bv) { bv = l[b * J + j]; best = j; }
             if (best < 0) break;
             sel[b * J + best] = 1;
-            sum += bv;
+            sum += (double)bv;
         }
-        ob[b] = sum / (float)topk;
+        ob[b] = (float)(sum / (double)topk);
     }
     __syncthreads();
     if (tid == 0) {                   // sums in index order: the same bits on every run (no atomics)
-        float a0 = 0.f, a1 = 0.f;
-        for (int b = 0; b < B; ++b) a0 += ob[b];
-        for (int j = 0; j < J; ++j) a1 += mj[j];
-        acc[0] = a0; acc[1] = a1;
-        const float ohkm = acc[0] / (float)B;
-        result[0] = ohkm;
-        result[1] = acc[1] / (float)J;
-        result[2] = ohkm + acc[1];
+        double a0 = 0.0, a1 = 0.0;
+        for (int b = 0; b < B; ++b) a0 += (double)ob[b];
+        for (int j = 0; j < J; ++j) a1 += (double)mj[j];
+        acc[0] = (float)a0; acc[1] = (float)a1;
+        const double ohkm = a0 / (double)B;
+        result[0] = (float)ohkm;
+        result[1] = (float)(a1 / (double)J);
+        result[2] = (float)(ohkm + a1);
     }
     if (coef) {
         for (int i = tid; i < B * J; i += blockDim.x) {
@@ -155,13 +156,13 @@ __global__ __launch_bounds__(256) void joints_finish_kernel(const float* __restr
     for (int i = tid; i < B * J; i += blockDim.x) { l[i] = 0.5f * ss[i] * inv_hw; sel[i] = 0; }
     __syncthreads();
     for (int j = tid; j < J; j += blockDim.x) {
-        float m = 0.f;
-        for (int b = 0; b < B; ++b) m += ss[b * J + j];
-        mj[j] = m / ((float)B * (float)HW);
+        double m = 0.0;
+        for (int b = 0; b < B; ++b) m += (double)ss[b * J + j];
+        mj[j] = (float)(m / ((double)B * (double)HW));
     }
     if (ohkm)
         for (int b = tid; b < B; b += blockDim.x) {
-            float sum = 0.f;
+            double sum = 0.0;
             for (int k = 0; k < topk; ++k) {
                 int best = -1;
                 float bv = -INFINITY;
@@ -169,22 +170,23 @@ __global__ __launch_bounds__(256) void joints_finish_kernel(const float* __restr
                     if (!sel[b * J + j] && l[b * J + j] > bv) { bv = l[b * J + j]; best = j; }
                 if (best < 0) break;
                 sel[b * J + best] = 1;
-                sum += bv;
+                sum += (double)bv;
             }
-            ob[b] = sum / (float)topk;
+            ob[b] = (float)(sum / (double)topk);
         }
     __syncthreads();
     if (tid == 0) {                                   // sums in index order (no atomics)
-        float a0 = 0.f, a1 = 0.f;
+        double a0 = 0.0, a1 = 0.0;
         if (ohkm)
-            for (int b = 0; b < B; ++b) a0 += ob[b];
-        for (int j = 0; j < J; ++j) a1 += mj[j];
-        acc[0] = a0; acc[1] = a1;
+            for (int b = 0; b < B; ++b) a0 += (double)ob[b];
+        for (int j = 0; j < J; ++j) a1 += (double)mj[j];
+        acc[0] = (float)a0; acc[1] = (float)a1;
+        const float mse = (float)(a1 / (double)eff);
         if (ohkm) {
-            const float v = acc[0] / (float)B;
-            result[0] = v; result[1] = acc[1] / eff; result[2] = v + acc[1];
+            const double v = a0 / (double)B;
+            result[0] = (float)v; result[1] = mse; result[2] = (float)(v + a1);
         } else {
-            result[0] = 0.f; result[1] = acc[1] / eff; result[2] = acc[1] / eff;
+            result[0] = 0.f; result[1] = mse; result[2] = mse;
         }
     }
     if (coef)

@@ -5,6 +5,13 @@
  * `stream` is a hipStream_t passed as void*.  Functions never allocate, never synchronise, launch
  * on `stream`, and return OTP_OK (0) or a negative OTP_ERR_* code (no exceptions cross the ABI).
  *
+ * Pointer convention: device memory is always `void*` (at any constness and depth: an array of device pointers is
+ * `const void* const*`, and its function says where the array itself lives), a typed pointer (`int*`, `double*`,
+ * `const otp_*_desc*`) is always HOST memory that the function reads or writes before it returns.
+ * otpose_amd/hip.py derives its ctypes signatures, descriptor structures and OTP_* constants from this file, so a
+ * prototype is `int|size_t otp_name(named parameters);` over int / float / double / size_t / unsigned long long
+ * and those pointers, and a new entry point needs no other declaration.
+ *
  * Reference interfaces replaced (paths relative to the reference repository):
  *   otp_mdcn_forward   <- modulated_deform_conv_cuda_forward   thirdparty/deform_conv/src/deform_conv_cuda.cpp:474-549
  *                         (+ modulated_deformable_im2col_cuda   src/deform_conv_cuda_kernel.cu:506-571, 707-737)

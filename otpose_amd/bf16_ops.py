@@ -15,12 +15,8 @@ import torch
 from torch.autograd import Function
 
 from . import hip
-from .ops import _require_gpu
-
-
-def grad_slot(param):
-    from .train_ops import grad_slot as _gs
-    return _gs(param)
+from .ops import _out_hw, _require_gpu
+from .train_ops import grad_slot
 
 BF16 = torch.bfloat16
 
@@ -170,8 +166,7 @@ def conv_forward(x, weight, bias=None, stride=1, pad=0, dil=1, out_mode=0, want_
     assert cins == cs(cin) and x.dtype == BF16 and x.is_contiguous()
     d = _desc(n, h, w, cin, cout, kh, kw, stride, pad, dil, out_mode)
     wp = _pack(weight.contiguous(), d, 0, packs)
-    ho = (h + 2 * pad - dil * (kh - 1) - 1) // stride + 1
-    wo = (w + 2 * pad - dil * (kw - 1) - 1) // stride + 1
+    ho, wo = _out_hw(h, w, kh, kw, stride, pad, dil)
     L = hip.lib()
     stats, rows = None, 0
     if out_mode == 0:
@@ -331,7 +326,7 @@ def conv_bn_forward(x, weight, gamma, beta, res, running_mean, running_var, stri
     assert cins == cs(cin) and x.dtype == BF16 and x.is_contiguous()
     d = _desc(n, h, w, cin, cout, kh, kw, stride, pad, 1, 0)
     wp = _pack(weight.contiguous(), d, 0, packs)
-    ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+    ho, wo = _out_hw(h, w, kh, kw, stride, pad, 1)
     L = hip.lib()
     csz = cs(cout)
     c = _new((n, ho, wo, csz), BF16, x)

@@ -19,7 +19,8 @@ from torch.autograd import Function
 from . import hip
 from .augment import FLIP_PAIRS
 
-_DTYPE_F32 = 0
+_K = hip.CONSTANTS              # the OTP_* integers of include/otpose_hip.h
+_DTYPE_F32 = _K["OTP_DTYPE_F32"]
 
 
 def _require_gpu(*tensors):
@@ -35,11 +36,26 @@ def _check_f32(*tensors):
 
 
 def _out_hw(h, w, kh, kw, stride, pad, dil):
+    """Output size of a convolution (the one statement of it: train_ops and bf16_ops call this too)."""
     return ((h + 2 * pad - (dil * (kh - 1) + 1)) // stride + 1,
             (w + 2 * pad - (dil * (kw - 1) + 1)) // stride + 1)
 
 
-_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}
+def _f32(t, device=None):
+    """Detached contiguous fp32 form of an optional tensor, on ``device`` (default: where it is); ``None`` stays ``None``."""
+    return None if t is None else t.detach().to(t.device if device is None else device, torch.float32).contiguous()
+
+
+def _image(nbytes, dtype, device, exc, what, zero=False):
+    """Storage of a packed image: ``nbytes`` is what the entry point's ``*_weight_bytes`` answered, 0 meaning that it has
+    no kernel for the shape (``exc(what)``); 4-byte elements of ``dtype``, zero-filled on request."""
+    if not nbytes:
+        raise exc(what)
+    return (torch.zeros if zero else torch.empty)(nbytes // 4, dtype=dtype, device=device)
+
+
+_DTYPES = {torch.float32: _K["OTP_DTYPE_F32"], torch.float16: _K["OTP_DTYPE_F16"], torch.bfloat16: _K["OTP_DTYPE_BF16"],
+           torch.float64: _K["OTP_DTYPE_F64"]}
 
 
 def _dcn_dtype(*tensors):
@@ -240,7 +256,7 @@ deform_conv = DeformConvFunction.apply
 
 
 # ---- deformable PS-RoI pooling: the pybind entry points of the reference's second native module (deform_pool_cuda) ----------
-_POOL_DTYPES = {torch.float32: 0, torch.float64: 3}
+_POOL_DTYPES = {torch.float32: _K["OTP_DTYPE_F32"], torch.float64: _K["OTP_DTYPE_F64"]}
 
 
 def _pool_dtype(*tensors):
@@ -348,7 +364,7 @@ def deform_psroi_pooling_cuda_backward(out_grad, input, bbox, trans, top_count, 
 # ------------------------------------------------------------------------------------------------
 # thin functional wrappers over the remaining C entry points (used by the engine and the tests)
 # ------------------------------------------------------------------------------------------------
-ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
+ACT_NONE, ACT_RELU, ACT_GELU = _K["OTP_ACT_NONE"], _K["OTP_ACT_RELU"], _K["OTP_ACT_GELU"]
 
 
 class View:
@@ -388,7 +404,7 @@ def pack_conv_weight(weight):
     """(Cout, Cin, kh, kw) -> packed [kh*kw][Cin][Cout16] device tensor for :func:`conv2d`."""
     _require_gpu(weight)
     _check_f32(weight)
-    w = weight.detach().contiguous()
+    w = _f32(weight)
     if w.dim() == 3:                      # Conv1d weight (Cout, Cin, k) with k == 1
         w = w.unsqueeze(-1)
     cout, cin, kh, kw = w.shape
@@ -411,8 +427,7 @@ def conv_desc(inp: View, out: View, cout, kh, kw, stride, pad, dil, act=ACT_NONE
     d.out_ctot, d.out_coff = out.ctot, out.coff
     d.res_ctot, d.res_coff = (res.ctot, res.coff) if res is not None else (0, 0)
     d.res_up, d.act, d.frame_split = res_up, act, frame_split
-    d.Ho = (h + 2 * pad - (dil * (kh - 1) + 1)) // stride + 1
-    d.Wo = (w + 2 * pad - (dil * (kw - 1) + 1)) // stride + 1
+    d.Ho, d.Wo = _out_hw(h, w, kh, kw, stride, pad, dil)
     f = max(res_up, 1)
     assert out.t.shape[2] == d.Ho * f and out.t.shape[3] == d.Wo * f, (tuple(out.t.shape), d.Ho, d.Wo, f)
     assert out.C == cout
@@ -439,7 +454,7 @@ def pack_wino_weight(weight):
     """(Cout, Cin, 3, 3) -> U[16][Cin][Cout16] = G g G^T device tensor for :func:`conv2d_wino_launch`."""
     _require_gpu(weight)
     _check_f32(weight)
-    w = weight.detach().contiguous()
+    w = _f32(weight)
     cout, cin, kh, kw = w.shape
     assert (kh, kw) == (3, 3)
     L = hip.lib()
@@ -455,13 +470,11 @@ def small_conv_supported(desc) -> bool:
 def pack_small_conv_weight(weight):
     """(Cout, Cin, 3, 3) -> the [ci][tap][co] image :func:`conv3x3_small` reads through the scalar cache."""
     _require_gpu(weight)
-    w = weight.detach().contiguous().float()
+    w = _f32(weight)
     cout, cin = w.shape[:2]
     L = hip.lib()
-    nbytes = L.otp_conv3x3_small_weight_bytes(cout, cin)
-    if not nbytes:
-        raise ValueError(f"otp_conv3x3_small: unsupported channel counts ({cout}, {cin})")
-    wt = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
+    wt = _image(L.otp_conv3x3_small_weight_bytes(cout, cin), torch.float32, w.device,
+                ValueError, f"otp_conv3x3_small: unsupported channel counts ({cout}, {cin})")
     hip.check(L.otp_conv3x3_small_pack(hip.ptr(w), hip.ptr(wt), cout, cin, hip.stream_of(w)), "otp_conv3x3_small_pack")
     return wt
 
@@ -496,19 +509,12 @@ def x3_weight_exponent(weight, scale=None) -> int:
     pointwise kernels through their per-channel epilogue scale).  ``OTPOSE_X3_WSCALE=0`` stores the weights unscaled."""
     if os.environ.get("OTPOSE_X3_WSCALE", "1") == "0":
         return 0
-    w = weight.detach()
-    m = w.abs().reshape(w.shape[0], -1).amax(dim=1)
-    if scale is not None:
-        m = m * scale.detach().abs().to(m.device, m.dtype)
-    m = float(m.max())
-    if not (m > 0.0 and math.isfinite(m)):
-        return 0
-    return max(-40, min(40, 14 - math.frexp(m)[1]))
+    return h16_weight_exponent(weight, scale)
 
 
 def _scaled_vec(scale, k, cout, device):
     """scale[cout] * 2^k as a contiguous fp32 vector (None when there is nothing to multiply by)"""
-    sc = scale.detach().to(device, torch.float32).contiguous() if scale is not None else None
+    sc = _f32(scale, device)
     if k == 0:
         return sc
     f = float(2.0 ** k)
@@ -521,16 +527,14 @@ def pack_x3_weight(weight, scale=None, stride=1, k=0):
     (:func:`x3_weight_exponent`)."""
     _require_gpu(weight)
     _check_f32(weight)
-    w = weight.detach().contiguous()
+    w = _f32(weight)
     if w.dim() == 3:
         w = w.unsqueeze(-1)
     cout, cin, kh, kw = w.shape
     assert kh == kw and kh in (1, 3)
     L = hip.lib()
-    nbytes = L.otp_conv2d_x3_weight_bytes(cout, cin, kh, stride)
-    if not nbytes:
-        raise ValueError(f"otp_conv2d_x3: unsupported channel counts ({cout}, {cin})")
-    u = torch.empty(nbytes // 4, dtype=torch.int32, device=w.device)
+    u = _image(L.otp_conv2d_x3_weight_bytes(cout, cin, kh, stride), torch.int32, w.device,
+               ValueError, f"otp_conv2d_x3: unsupported channel counts ({cout}, {cin})")
     sc = _scaled_vec(scale, k, cout, w.device)
     hip.check(L.otp_conv2d_x3_pack_weight(hip.ptr(w), hip.ptr(sc), hip.ptr(u), cout, cin, kh, stride, hip.stream_of(w)),
               "otp_conv2d_x3_pack_weight")
@@ -554,8 +558,7 @@ def conv2d_x3(x, weight, scale=None, shift=None, act=ACT_NONE, res=None, pad=1, 
     _require_gpu(x, weight)
     n, cin, h, w = x.shape
     cout, k = weight.shape[0], weight.shape[2]
-    ke = dil * (k - 1)
-    ho, wo = (h + 2 * pad - ke - 1) // stride + 1, (w + 2 * pad - ke - 1) // stride + 1
+    ho, wo = _out_hw(h, w, k, k, stride, pad, dil)
     out = torch.empty(n, cout, ho, wo, dtype=torch.float32, device=x.device)
     iv, ov = View(x.contiguous()), View(out)
     rv = View(res.contiguous()) if res is not None else None
@@ -567,7 +570,7 @@ def conv2d_x3(x, weight, scale=None, shift=None, act=ACT_NONE, res=None, pad=1, 
 
 
 # ---- split-record (S8) activations and the LDS-DMA fed 3x3 convolution (csrc/convs.hip) --------------------------------
-S8_F32_C4, S8_F32_NCHW = 1, 2
+S8_F32_C4, S8_F32_NCHW = _K["OTP_S8_F32_C4"], _K["OTP_S8_F32_NCHW"]
 
 
 def s8_empty(n, c, h, w, device):
@@ -675,14 +678,12 @@ def pack_s8_weight(weight, scale=None, k=0):
     :func:`conv3x3_s2_s8`; the descriptor's ``out_scale`` must then be 2^-k (:func:`x3_weight_exponent`)."""
     _require_gpu(weight)
     _check_f32(weight)
-    w = weight.detach().contiguous()
+    w = _f32(weight)
     cout, cin, kh, kw = w.shape
     assert kh == kw == 3
     L = hip.lib()
-    nbytes = L.otp_conv3x3_s8_weight_bytes(cout, cin)
-    if not nbytes:
-        raise ValueError(f"otp_conv3x3_s8: unsupported channel counts ({cout}, {cin})")
-    u = torch.empty(nbytes // 4, dtype=torch.int32, device=w.device)
+    u = _image(L.otp_conv3x3_s8_weight_bytes(cout, cin), torch.int32, w.device,
+               ValueError, f"otp_conv3x3_s8: unsupported channel counts ({cout}, {cin})")
     sc = _scaled_vec(scale, k, cout, w.device)
     hip.check(L.otp_conv3x3_s8_pack_weight(hip.ptr(w), hip.ptr(sc), hip.ptr(u), cout, cin, hip.stream_of(w)),
               "otp_conv3x3_s8_pack_weight")
@@ -758,14 +759,11 @@ def pack_dense_cc(weight, scale=None, shift=None, x3=False, grad=False):
     _require_gpu(weight)
     c = weight.shape[0]
     L = hip.lib()
-    nbytes = (L.otp_dense_x3_weight_bytes if x3 else L.otp_dense_cc_weight_bytes)(c)
-    if not nbytes or weight.shape[1] != c:
-        raise RuntimeError(f"otp_dense_cc: unsupported weight shape {tuple(weight.shape)}")
-    f = lambda t: None if t is None else t.detach().to(weight.device, torch.float32).contiguous()   # noqa: E731
-    w, sc, sh = f(weight), f(scale), f(shift)
-    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=weight.device)
-    pack = (L.otp_dense_x3_pack_bf16p if grad else L.otp_dense_x3_pack) if x3 else L.otp_dense_cc_pack
-    hip.check(pack(hip.ptr(w), hip.ptr(sc), hip.ptr(sh), hip.ptr(packed), c, hip.stream_of(w)), "otp_dense_cc_pack")
+    entry = ("otp_dense_x3_pack_bf16p" if grad else "otp_dense_x3_pack") if x3 else "otp_dense_cc_pack"
+    nbytes = (L.otp_dense_x3_weight_bytes if x3 else L.otp_dense_cc_weight_bytes)(c) if weight.shape[1] == c else 0
+    packed = _image(nbytes, torch.float32, weight.device, RuntimeError, f"otp_dense_cc: unsupported weight shape {tuple(weight.shape)}")
+    w, sc, sh = (_f32(t, weight.device) for t in (weight, scale, shift))
+    hip.check(getattr(L, entry)(hip.ptr(w), hip.ptr(sc), hip.ptr(sh), hip.ptr(packed), c, hip.stream_of(w)), entry)
     return packed
 
 
@@ -783,9 +781,8 @@ def dense_cc(xs, packs, ress=None, outs=None, stream=None, x3=False, grad=False,
     b, c, t = xs[0].shape
     outs = [torch.empty_like(x) for x in xs] if outs is None else outs
     ax, ap, ar, ao = dense_cc_args(xs, packs, ress, outs)
-    fn = (hip.lib().otp_dense_x3_bf16p if grad else (hip.lib().otp_dense_h1 if half else hip.lib().otp_dense_x3)) if x3 \
-        else hip.lib().otp_dense_cc
-    hip.check(fn(ax, ap, ar, ao, len(xs), b, c, t, stream if stream is not None else hip.stream_of(xs[0])), "otp_dense_cc")
+    entry = ("otp_dense_x3_bf16p" if grad else "otp_dense_h1" if half else "otp_dense_x3") if x3 else "otp_dense_cc"
+    hip.check(getattr(hip.lib(), entry)(ax, ap, ar, ao, len(xs), b, c, t, stream if stream is not None else hip.stream_of(xs[0])), entry)
     return outs
 
 
@@ -798,12 +795,9 @@ def pack_stem_conv_x3(weight, scale=None, shift=None):
     _require_gpu(weight)
     cout = weight.shape[0]
     L = hip.lib()
-    nbytes = L.otp_stem_conv_x3_weight_bytes(cout)
-    if not nbytes or tuple(weight.shape[1:]) != (3, 3, 3):
-        raise RuntimeError(f"otp_stem_conv_x3: unsupported weight shape {tuple(weight.shape)}")
-    f = lambda t: None if t is None else t.detach().to(weight.device, torch.float32).contiguous()   # noqa: E731
-    w, sc, sh = f(weight), f(scale), f(shift)
-    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=weight.device)
+    nbytes = L.otp_stem_conv_x3_weight_bytes(cout) if tuple(weight.shape[1:]) == (3, 3, 3) else 0
+    packed = _image(nbytes, torch.float32, weight.device, RuntimeError, f"otp_stem_conv_x3: unsupported weight shape {tuple(weight.shape)}")
+    w, sc, sh = (_f32(t, weight.device) for t in (weight, scale, shift))
     hip.check(L.otp_stem_conv_x3_pack(hip.ptr(w), hip.ptr(sc), hip.ptr(sh), hip.ptr(packed), cout, hip.stream_of(w)),
               "otp_stem_conv_x3_pack")
     return packed
@@ -831,20 +825,24 @@ def pointwise_x3_supported(cin, cout, t) -> bool:
     return bool(hip.lib().otp_pointwise_x3_supported(int(cin), int(cout), int(t)))
 
 
+def _pointwise_operands(weight, scale, shift, cout, cin, device):
+    """fp32 (cout, cin) weight, scale, shift of a pointwise packer on ``device``: the weights stored times 2^e
+    (:func:`x3_weight_exponent`), undone by the kernel's per-channel epilogue scale."""
+    w, sc, sh = _f32(weight, device).reshape(cout, cin), _f32(scale, device), _f32(shift, device)
+    e = x3_weight_exponent(w)
+    if e:
+        w, sc = w * float(2.0 ** e), _scaled_vec(sc, -e, cout, w.device)
+    return w, sc, sh
+
+
 def _pack_pointwise(entry, weight, scale, shift):
     """(Cout, Cin[, 1, 1]) weight (+ per-output-channel scale / shift) -> the image ``<entry>_pack`` writes."""
     _require_gpu(weight)
     cout, cin = weight.shape[:2]
     L = hip.lib()
-    nbytes = getattr(L, entry + "_weight_bytes")(cin, cout)
-    if not nbytes:
-        raise RuntimeError(f"{entry}: unsupported weight shape {tuple(weight.shape)}")
-    f = lambda t: None if t is None else t.detach().to(weight.device, torch.float32).contiguous()   # noqa: E731
-    w, sc, sh = f(weight).reshape(cout, cin), f(scale), f(shift)
-    e = x3_weight_exponent(w)                     # weights stored times 2^e, undone by the kernel's per-channel epilogue scale
-    if e:
-        w, sc = w * float(2.0 ** e), _scaled_vec(sc, -e, cout, w.device)
-    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=weight.device)
+    packed = _image(getattr(L, entry + "_weight_bytes")(cin, cout), torch.float32, weight.device,
+                    RuntimeError, f"{entry}: unsupported weight shape {tuple(weight.shape)}")
+    w, sc, sh = _pointwise_operands(weight, scale, shift, cout, cin, weight.device)
     hip.check(getattr(L, entry + "_pack")(hip.ptr(w), hip.ptr(sc), hip.ptr(sh), hip.ptr(packed), cin, cout, hip.stream_of(w)),
               entry + "_pack")
     return packed
@@ -889,7 +887,7 @@ def pointwise_x3_s8(x: View, packed, cout, out_s8=None, relu=False, stream=None,
     _require_gpu(x.t)
     b, _, h, w = x.t.shape
     out_s8 = s8_empty(b, cout, h, w, x.t.device) if out_s8 is None else out_s8
-    _launch(hip.lib().otp_pointwise_x3_s8_res, "otp_pointwise_x3_s8", pointwise_x3_s8_res_args(x, packed, cout, out_s8, res, relu),
+    _launch(hip.lib().otp_pointwise_x3_s8_res, "otp_pointwise_x3_s8_res", pointwise_x3_s8_res_args(x, packed, cout, out_s8, res, relu),
             x.t, stream)
     return out_s8
 
@@ -906,17 +904,10 @@ def pack_pointwise_x3_pair(weight1, scale1, shift1, weight2, scale2=None, shift2
     cout2 = weight2.shape[0]
     L = hip.lib()
     nbytes = L.otp_pointwise_x3_pair_weight_bytes(cin, cmid, cout2) if weight2.shape[1] == cmid else 0
-    if not nbytes:
-        raise RuntimeError(f"otp_pointwise_x3_pair: unsupported weight shapes {tuple(weight1.shape)}, {tuple(weight2.shape)}")
-    f = lambda t: None if t is None else t.detach().to(weight1.device, torch.float32).contiguous()   # noqa: E731
-    ws = []
-    for wt, sc, sh, co, ci in ((weight1, scale1, shift1, cmid, cin), (weight2, scale2, shift2, cout2, cmid)):
-        w, sc, sh = f(wt).reshape(co, ci), f(sc), f(sh)
-        e = x3_weight_exponent(w)                 # weights stored times 2^e, undone by the kernel's per-channel epilogue scale
-        if e:
-            w, sc = w * float(2.0 ** e), _scaled_vec(sc, -e, co, w.device)
-        ws += [w, sc, sh]
-    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=weight1.device)
+    packed = _image(nbytes, torch.float32, weight1.device, RuntimeError,
+                    f"otp_pointwise_x3_pair: unsupported weight shapes {tuple(weight1.shape)}, {tuple(weight2.shape)}")
+    ws = [*_pointwise_operands(weight1, scale1, shift1, cmid, cin, weight1.device),
+          *_pointwise_operands(weight2, scale2, shift2, cout2, cmid, weight1.device)]
     hip.check(L.otp_pointwise_x3_pair_pack(*[hip.ptr(t) for t in ws], hip.ptr(packed), cin, cmid, cout2, hip.stream_of(ws[0])),
               "otp_pointwise_x3_pair_pack")
     return packed
@@ -942,7 +933,7 @@ def pointwise_x3_pair(x: View, packed, out: View, cout2, res: View = None, out_s
 def pack_qkv_table(dwq, dwk, dwv, gq, bq, gk, bk, gv, bv):
     """Depthwise (C, 1, 3) weights and LayerNorm (C) gamma / beta of MaskedMHCA's query / key / value paths
     (model/blocks.py:359-381) -> the per-channel table of :func:`qkv_front`."""
-    ts = [t.detach().float().contiguous() for t in (dwq, dwk, dwv, gq, bq, gk, bk, gv, bv)]
+    ts = [_f32(t) for t in (dwq, dwk, dwv, gq, bq, gk, bk, gv, bv)]
     _require_gpu(*ts)
     c = ts[3].numel()
     L = hip.lib()
@@ -963,8 +954,8 @@ def qkv_front(x, table, packs, eps=1e-5, outs=None, stream=None, x3=False, half=
     (``half`` with ``x3``: operands rounded to half once, otp_qkv_front_h1)."""
     _require_gpu(x, table)
     outs = [torch.empty_like(x) for _ in range(3)] if outs is None else outs
-    fn = (hip.lib().otp_qkv_front_h1 if half else hip.lib().otp_qkv_front_x3) if x3 else hip.lib().otp_qkv_front
-    _launch(fn, "otp_qkv_front", qkv_front_args(x, table, packs, outs, eps), x, stream)
+    entry = ("otp_qkv_front_h1" if half else "otp_qkv_front_x3") if x3 else "otp_qkv_front"
+    _launch(getattr(hip.lib(), entry), entry, qkv_front_args(x, table, packs, outs, eps), x, stream)
     return outs
 
 
@@ -978,11 +969,9 @@ def pack_mlp_weights(w1, b1, w2):
     _require_gpu(w1, b1, w2)
     hid, c = w1.shape[:2]
     L = hip.lib()
-    nbytes = L.otp_mlp_fused_weight_bytes(c, hid)
-    if not nbytes:
-        raise RuntimeError(f"otp_mlp_fused: unsupported widths C={c}, HID={hid}")
-    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=w1.device)
-    w1c, w2c, b1c = (t.detach().contiguous().float() for t in (w1, w2, b1))
+    packed = _image(L.otp_mlp_fused_weight_bytes(c, hid), torch.float32, w1.device,
+                    RuntimeError, f"otp_mlp_fused: unsupported widths C={c}, HID={hid}")
+    w1c, w2c, b1c = (_f32(t) for t in (w1, w2, b1))
     hip.check(L.otp_mlp_fused_pack(hip.ptr(w1c), hip.ptr(b1c), hip.ptr(w2c), hip.ptr(packed), c, hid, hip.stream_of(w1c)),
               "otp_mlp_fused_pack")
     return packed
@@ -1011,14 +1000,10 @@ def pack_dcn_fused(w_offs, w_masks, w_dcns, biases):
     nd, j = len(w_offs), w_dcns[0].shape[0]
     dev = w_offs[0].device
     _require_gpu(*w_offs, *w_masks, *w_dcns)
-    keep = [[t.detach().contiguous().float() for t in ts] for ts in (w_offs, w_masks, w_dcns)]
-    keep.append([None if b is None else b.detach().contiguous().float() for b in biases])
+    keep = [[_f32(t) for t in ts] for ts in (w_offs, w_masks, w_dcns, biases)]
     ptrs = [torch.tensor([0 if t is None else t.data_ptr() for t in ts], dtype=torch.int64, device=dev) for ts in keep]
     L = hip.lib()
-    nbytes = L.otp_dcn_fused_weight_bytes(nd, j)
-    if not nbytes:
-        raise RuntimeError(f"otp_dcn_fused: unsupported ND={nd}, J={j}")
-    packed = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    packed = _image(L.otp_dcn_fused_weight_bytes(nd, j), torch.int32, dev, RuntimeError, f"otp_dcn_fused: unsupported ND={nd}, J={j}")
     hip.check(L.otp_dcn_fused_pack(*[hip.ptr(t) for t in ptrs], hip.ptr(packed), nd, j, hip.stream_of(packed)),
               "otp_dcn_fused_pack")
     torch.cuda.current_stream(dev).synchronize()          # the pointer arrays and fp32 copies die with this frame
@@ -1053,13 +1038,12 @@ def pack_mlp_x3_weights(w1, b1, w2, half=False):
     _require_gpu(w1, b1, w2)
     hid, c = w1.shape[:2]
     L = hip.lib()
-    nbytes = (L.otp_mlp_h1_weight_bytes if half else L.otp_mlp_x3_weight_bytes)(c, hid)
-    if not nbytes:
-        raise RuntimeError(f"otp_mlp_x3: unsupported widths C={c}, HID={hid}")
-    packed = torch.empty(nbytes // 4, dtype=torch.int32, device=w1.device)
-    w1c, w2c, b1c = (t.detach().contiguous().float() for t in (w1, w2, b1))
-    hip.check((L.otp_mlp_h1_pack if half else L.otp_mlp_x3_pack)(hip.ptr(w1c), hip.ptr(b1c), hip.ptr(w2c), hip.ptr(packed), c, hid,
-                                                                 hip.stream_of(w1c)), "otp_mlp_x3_pack")
+    entry = "otp_mlp_h1" if half else "otp_mlp_x3"
+    packed = _image(getattr(L, entry + "_weight_bytes")(c, hid), torch.int32, w1.device,
+                    RuntimeError, f"otp_mlp_x3: unsupported widths C={c}, HID={hid}")
+    w1c, w2c, b1c = (_f32(t) for t in (w1, w2, b1))
+    hip.check(getattr(L, entry + "_pack")(hip.ptr(w1c), hip.ptr(b1c), hip.ptr(w2c), hip.ptr(packed), c, hid, hip.stream_of(w1c)),
+              entry + "_pack")
     return packed
 
 
@@ -1103,8 +1087,7 @@ def conv2d(x, weight, scale=None, shift=None, stride=1, pad=0, dil=1, act=ACT_NO
     w4 = weight if weight.dim() == 4 else weight.unsqueeze(-1)
     cout, cin, kh, kw = w4.shape
     h, w = x.shape[2:]
-    ho = (h + 2 * pad - (dil * (kh - 1) + 1)) // stride + 1
-    wo = (w + 2 * pad - (dil * (kw - 1) + 1)) // stride + 1
+    ho, wo = _out_hw(h, w, kh, kw, stride, pad, dil)
     out = torch.empty((x.shape[0], cout, ho * max(res_up, 1), wo * max(res_up, 1)), dtype=torch.float32, device=x.device)
     iv, ov = View(x.contiguous()), View(out)
     rv = View(res.contiguous()) if res is not None else None
@@ -1280,7 +1263,7 @@ def flip_test_merge(hm_pair, flip_pairs=FLIP_PAIRS, shift_heatmap=False, center=
     if center is not None:
         c = torch.as_tensor(center, dtype=torch.float32, device=hm_pair.device).reshape(n, 2).contiguous()
         s_ = torch.as_tensor(scale, dtype=torch.float32, device=hm_pair.device).reshape(n, 2).contiguous()
-    hip.check(hip.lib().otp_heatmap_flip_decode(hip.ptr(hm_pair), perm.ctypes.data_as(ctypes.c_void_p), hip.ptr(merged),
+    hip.check(hip.lib().otp_heatmap_flip_decode(hip.ptr(hm_pair), perm.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), hip.ptr(merged),
                                                 hip.ptr(preds), hip.ptr(maxvals), hip.ptr(c), hip.ptr(s_), n, j, h, w,
                                                 int(bool(shift_heatmap)), hip.stream_of(hm_pair)),
               "otp_heatmap_flip_decode")
@@ -1322,9 +1305,7 @@ def accuracy(output, target, hm_type="gaussian", thr=0.5):
     return acc, acc[0], cnt[0], pred
 
 
-POSEVAL_JOINTS = 15          # OTP_POSEVAL_* of include/otpose_hip.h
-POSEVAL_MAX_PR = 64
-POSEVAL_MAX_GT = 64
+POSEVAL_JOINTS, POSEVAL_MAX_PR, POSEVAL_MAX_GT = _K["OTP_POSEVAL_JOINTS"], _K["OTP_POSEVAL_MAX_PR"], _K["OTP_POSEVAL_MAX_GT"]
 
 
 def _poseval_arg(t, dtype, shape, name):
@@ -1852,15 +1833,13 @@ def h16_conv_supported(desc) -> bool:
 def pack_h16_conv_weight(weight, scale=None, k=0):
     """(Cout, Cin, 3, 3) fp32 (x scale[cout] x 2^k) -> the half A-fragment image of csrc/h16.hip."""
     _require_gpu(weight)
-    w = weight.detach().contiguous().float()
+    w = _f32(weight)
     cout, cin, kh, kw = w.shape
     assert (kh, kw) == (3, 3)
     L = hip.lib()
-    nbytes = L.otp_h16_conv3x3_weight_bytes(cout, cin)
-    if not nbytes:
-        raise RuntimeError(f"otp_h16_conv3x3: unsupported widths {cin} -> {cout}")
-    packed = torch.zeros(nbytes // 4, dtype=torch.int32, device=w.device)
-    sc = scale.detach().to(w.device, torch.float32).contiguous() if scale is not None else None
+    packed = _image(L.otp_h16_conv3x3_weight_bytes(cout, cin), torch.int32, w.device,
+                    RuntimeError, f"otp_h16_conv3x3: unsupported widths {cin} -> {cout}", zero=True)
+    sc = _f32(scale, w.device)
     hip.check(L.otp_h16_conv3x3_pack_weight(hip.ptr(w), hip.ptr(sc), hip.ptr(packed), cout, cin, float(2.0 ** k), hip.stream_of(w)),
               "otp_h16_conv3x3_pack_weight")
     return packed
@@ -1886,15 +1865,12 @@ def h16_pointwise_supported(cin, cout) -> bool:
 def pack_h16_pointwise(weight, scale=None, shift=None, k=0):
     """(Cout, Cin[, 1, 1]) fp32 (x scale x 2^k) + shift -> the packed image of otp_h16_pointwise."""
     _require_gpu(weight)
-    w = weight.detach().reshape(weight.shape[0], -1).contiguous().float()
+    w = _f32(weight.reshape(weight.shape[0], -1))
     cout, cin = w.shape
     L = hip.lib()
-    nbytes = L.otp_h16_pointwise_weight_bytes(cin, cout)
-    if not nbytes:
-        raise RuntimeError(f"otp_h16_pointwise: unsupported widths {cin} -> {cout}")
-    packed = torch.zeros(nbytes // 4, dtype=torch.int32, device=w.device)
-    sc = scale.detach().to(w.device, torch.float32).contiguous() if scale is not None else None
-    sh = shift.detach().to(w.device, torch.float32).contiguous() if shift is not None else None
+    packed = _image(L.otp_h16_pointwise_weight_bytes(cin, cout), torch.int32, w.device,
+                    RuntimeError, f"otp_h16_pointwise: unsupported widths {cin} -> {cout}", zero=True)
+    sc, sh = _f32(scale, w.device), _f32(shift, w.device)
     hip.check(L.otp_h16_pointwise_pack(hip.ptr(w), hip.ptr(sc), hip.ptr(sh), hip.ptr(packed), cin, cout, float(2.0 ** k),
                                        hip.stream_of(w)), "otp_h16_pointwise_pack")
     return packed
@@ -1916,15 +1892,12 @@ def h16_pointwise(x: H8, packed, cout, relu=False, res: H8 = None, out=None, k=0
 
 def pack_h16_stem(weight, scale=None, shift=None):
     _require_gpu(weight)
-    w = weight.detach().contiguous().float()
+    w = _f32(weight)
     cout = w.shape[0]
     L = hip.lib()
-    nbytes = L.otp_h16_stem_weight_bytes(cout)
-    if not nbytes:
-        raise RuntimeError(f"otp_h16_stem: unsupported width {cout}")
-    packed = torch.zeros(nbytes // 4, dtype=torch.int32, device=w.device)
-    sc = scale.detach().to(w.device, torch.float32).contiguous() if scale is not None else None
-    sh = shift.detach().to(w.device, torch.float32).contiguous() if shift is not None else None
+    packed = _image(L.otp_h16_stem_weight_bytes(cout), torch.int32, w.device,
+                    RuntimeError, f"otp_h16_stem: unsupported width {cout}", zero=True)
+    sc, sh = _f32(scale, w.device), _f32(shift, w.device)
     hip.check(L.otp_h16_stem_pack(hip.ptr(w), hip.ptr(sc), hip.ptr(sh), hip.ptr(packed), cout, hip.stream_of(w)), "otp_h16_stem_pack")
     return packed
 

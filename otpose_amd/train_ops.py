@@ -14,7 +14,7 @@ import torch
 from torch.autograd import Function
 
 from . import hip
-from .ops import (ACT_NONE, View, _check_f32, _require_gpu, conv2d_launch, conv2d_wino_launch, conv_desc,
+from .ops import (ACT_NONE, View, _check_f32, _out_hw, _require_gpu, conv2d_launch, conv2d_wino_launch, conv_desc,
                   pack_conv_weight, pack_wino_weight, wino_supported)
 
 
@@ -42,13 +42,9 @@ def grad_slot(param):
     return slot.view(slot.shape)
 
 
-def _out_hw(h, w, k, stride, pad, dil):
-    return (h + 2 * pad - (dil * (k - 1) + 1)) // stride + 1, (w + 2 * pad - (dil * (k - 1) + 1)) // stride + 1
-
-
 def conv2d_forward(x, weight, bias, stride, pad, dil):
     cout, cin, kh, kw = weight.shape
-    ho, wo = _out_hw(x.shape[2], x.shape[3], kh, stride, pad, dil)
+    ho, wo = _out_hw(x.shape[2], x.shape[3], kh, kw, stride, pad, dil)
     out = torch.empty((x.shape[0], cout, ho, wo), dtype=torch.float32, device=x.device)
     iv, ov = View(x), View(out)
     d = conv_desc(iv, ov, cout, kh, kw, stride, pad, dil, ACT_NONE)
@@ -528,14 +524,14 @@ class ChanAttnFunction(Function):
         ns = L.otp_chan_attn_splits(bh, t)
         slabs = new(bh * ns * hsp * hsp)
         # (every product of the backward has a gradient operand: bfloat16 pieces - csrc/transformer_grad.hip)
-        hip.check(L.otp_chan_attn_scores_bf16p(hip.ptr(d_o), hip.ptr(v), hip.ptr(slabs), bh, hs, t, st), "otp_chan_attn_scores")
+        hip.check(L.otp_chan_attn_scores_bf16p(hip.ptr(d_o), hip.ptr(v), hip.ptr(slabs), bh, hs, t, st), "otp_chan_attn_scores_bf16p")
         d_s, d_st, p_t = new(bh, hsp, hsp), new(bh, hsp, hsp), new(bh, hsp, hsp)
         hip.check(L.otp_softmax_backward(hip.ptr(slabs), hip.ptr(p), hip.ptr(d_s), hip.ptr(d_st), hip.ptr(p_t), bh, hs, ns,
                                          st), "otp_softmax_backward")
         tmp = new(bh, t, hs)
         grads = []
         for src, mat, sc in ((k, d_s, scale), (q, d_st, scale), (d_o, p_t, 1.0)):
-            hip.check(L.otp_chan_attn_apply_bf16p(hip.ptr(src), hip.ptr(mat), hip.ptr(tmp), bh, hs, t, st), "otp_chan_attn_apply")
+            hip.check(L.otp_chan_attn_apply_bf16p(hip.ptr(src), hip.ptr(mat), hip.ptr(tmp), bh, hs, t, st), "otp_chan_attn_apply_bf16p")
             g = new(b, c, t)
             hip.check(L.otp_transpose_scale(hip.ptr(tmp), hip.ptr(g), bh, t, hs, sc, st), "otp_transpose_scale")
             grads.append(g)

@@ -652,12 +652,21 @@ int otp_pck_accuracy(const void* pred_coords, const void* target_coords, void* a
  * second launch adds in a fixed order (no float atomics: the clip coefficient is the same bits on every run).
  * otp_adamw_step: torch.optim.AdamW update of one hyper-parameter group, step >= 1 = the 1-based step count; the
  * gradient is first scaled by min(1, max_norm / (sqrt(*gradnorm_sq_f64) + 1e-6)) read on the device
- * (gradnorm_sq_f64 == NULL or max_norm <= 0: no clipping). */
+ * (gradnorm_sq_f64 == NULL or max_norm <= 0: no clipping).
+ * otp_sgd_step: torch.optim.SGD update of one hyper-parameter group (TRAIN.OPTIMIZER = SGD, train_utils.py:123-128) behind
+ * the same clip: d = clip * g; weight_decay != 0: d += weight_decay * p; momentum != 0: buf = first_step ? d :
+ * momentum * buf + (1 - dampening) * d, then d = nesterov ? d + momentum * buf : buf; p -= lr * d.  first_step != 0 writes
+ * momentum_buf without reading it.  momentum == 0 takes a NULL momentum_buf and touches none.  OTP_ERR_BAD_ARG: NULL param /
+ * grad, n == 0, momentum != 0 with a NULL buffer, nesterov with momentum <= 0 or dampening != 0 (torch: ValueError),
+ * negative lr / momentum / weight_decay; OTP_ERR_UNSUPPORTED: a pointer that is not 16-byte aligned.  No atomics: every
+ * element belongs to one thread, the same bits on every run. */
 size_t otp_grad_sumsq_scratch(void);
 int otp_grad_sumsq(const void* grad, size_t n, void* acc_f64, void* stream);
 int otp_adamw_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, size_t n, float lr, float beta1,
                    float beta2, float eps, float weight_decay, int step, const void* gradnorm_sq_f64, float max_norm,
                    void* stream);
+int otp_sgd_step(void* param, const void* grad, void* momentum_buf, size_t n, float lr, float momentum, float dampening,
+                 float weight_decay, int nesterov, int first_step, const void* gradnorm_sq_f64, float max_norm, void* stream);
 
 /* ---- input assembly (the step before the path: dataset/PoseTrackDataset.py:397-406 transform per frame =
  * utils/transform.py:7-15 ToTensor + Normalize, script/Common.py:117 torch.cat over the frames) ---------------------

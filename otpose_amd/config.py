@@ -123,7 +123,11 @@ def make_cfg(width: int = 48, image_size: Tuple[int, int] = (288, 384),
             },
         },
         "LOSS": {"NAME": "ST_OHKW_MSELoss", "USE_TARGET_WEIGHT": True, "TOPK": 8},
-        "TRAIN": {"LR": 1e-4, "WD": 0.0, "OPTIMIZER": "AdamW"},
+        # optimizer / schedule keys read by optim.make_optimizer and schedule.make_scheduler: reference configs/default.py:136-160
+        # overridden by configs/Base_PoseTrack17.yaml:106-120
+        "TRAIN": {"LR": 1e-4, "WD": 0.0, "OPTIMIZER": "AdamW", "MOMENTUM": 0.9, "NESTEROV": False,
+                  "LR_SCHEDULER": "CosineAnnealingLR", "WARMUP": True, "WARMUP_EPOCHS": 12, "END_EPOCH": 38, "EPOCHS": 30,
+                  "GAMMA": 0.9},
     })
 
 

@@ -4,6 +4,7 @@
 // Two HBM-bound passes: sum of squares (fp64 partials per workgroup, added in a fixed order: no atomics, the same bits on
 // every run) and the fused clip + update, which reads the
 // clip coefficient from device memory - no host synchronisation between backward and the next forward.
+// TRAIN.OPTIMIZER = SGD (train_utils.py:123-128, torch.optim.SGD semantics) is a second update kernel behind the same clip.
 #include "common.h"
 
 namespace {
@@ -81,6 +82,53 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
             adamw_one(p[i], g[i], m[i], v[i], clip, lr_wd, b1, b2, step_size, inv_sqrt_bc2, eps);
 }
 
+// torch.optim.SGD on one element: d = clip * g (+ wd * p); with momentum the buffer recurrence, then p -= lr * d
+__device__ __forceinline__ void sgd_one(float& p, float g, float& buf, float clip, float lr, float mom, float one_m_damp,
+                                        float wd, bool use_wd, bool use_mom, bool nesterov, bool first) {
+    float d = clip * g;
+    if (use_wd) d += wd * p;
+    if (use_mom) {
+        buf = first ? d : mom * buf + one_m_damp * d;
+        d = nesterov ? d + mom * buf : buf;
+    }
+    p -= lr * d;
+}
+
+// buf == nullptr <=> momentum == 0: the buffer is neither read nor written
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                   size_t n4, size_t n, float lr, float mom, float damp, float wd, int nesterov,
+                                                   int first, const double* __restrict__ gradnorm_sq, float max_norm) {
+    float clip = 1.f;
+    if (gradnorm_sq && max_norm > 0.f) {
+        const float c = max_norm / ((float)sqrt(*gradnorm_sq) + 1e-6f);      // clip_grad_norm_: clamped to 1
+        clip = c < 1.f ? c : 1.f;
+    }
+    const bool use_wd = wd != 0.f, use_mom = buf != nullptr, nest = nesterov != 0, fst = first != 0;
+    const float one_m_damp = 1.f - damp;
+    otp_f32x4* p4 = reinterpret_cast<otp_f32x4*>(p);
+    otp_f32x4* b4 = reinterpret_cast<otp_f32x4*>(buf);
+    const otp_f32x4* g4 = reinterpret_cast<const otp_f32x4*>(g);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        otp_f32x4 pp = p4[i], bb = {0.f, 0.f, 0.f, 0.f};
+        const otp_f32x4 gg = g4[i];
+        if (use_mom && !fst) bb = b4[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float pe = pp[e], be = bb[e];
+            sgd_one(pe, gg[e], be, clip, lr, mom, one_m_damp, wd, use_wd, use_mom, nest, fst);
+            pp[e] = pe; bb[e] = be;
+        }
+        p4[i] = pp;
+        if (use_mom) b4[i] = bb;
+    }
+    if (blockIdx.x == 0)
+        for (size_t i = n4 * 4 + threadIdx.x; i < n; i += 256) {
+            float be = (use_mom && !fst) ? buf[i] : 0.f;
+            sgd_one(p[i], g[i], be, clip, lr, mom, one_m_damp, wd, use_wd, use_mom, nest, fst);
+            if (use_mom) buf[i] = be;
+        }
+}
+
 unsigned grid_for(size_t n4) {
     const size_t b = (n4 + 255) / 256;
     return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
@@ -113,6 +161,23 @@ extern "C" int otp_adamw_step(void* param, const void* grad, void* exp_avg, void
     hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<float*>(param), static_cast<const float*>(grad), static_cast<float*>(exp_avg),
                        static_cast<float*>(exp_avg_sq), n / 4, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
+                       static_cast<const double*>(gradnorm_sq_f64), max_norm);
+    return otp_launch_status();
+}
+
+extern "C" int otp_sgd_step(void* param, const void* grad, void* momentum_buf, size_t n, float lr, float momentum,
+                            float dampening, float weight_decay, int nesterov, int first_step, const void* gradnorm_sq_f64,
+                            float max_norm, void* stream) {
+    if (!param || !grad || n == 0) return OTP_ERR_BAD_ARG;
+    if (!(lr >= 0.f) || !(momentum >= 0.f) || !(weight_decay >= 0.f)) return OTP_ERR_BAD_ARG;      // (NaN is rejected, too)
+    if (momentum != 0.f && !momentum_buf) return OTP_ERR_BAD_ARG;
+    if (nesterov && (momentum <= 0.f || dampening != 0.f)) return OTP_ERR_BAD_ARG;                  // torch: ValueError
+    if (momentum == 0.f) momentum_buf = nullptr;                                                    // no buffer is touched
+    if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(momentum_buf)) & 15)
+        return OTP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n / 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<float*>(param), static_cast<const float*>(grad), static_cast<float*>(momentum_buf), n / 4, n,
+                       lr, momentum, dampening, weight_decay, nesterov, first_step,
                        static_cast<const double*>(gradnorm_sq_f64), max_norm);
     return otp_launch_status();
 }

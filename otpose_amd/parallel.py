@@ -337,7 +337,8 @@ def joint_flags(target: torch.Tensor) -> torch.Tensor:
     return (target.amax(dim=(0, 2, 3)) == 1).to(torch.int32)
 
 
-def train_step_dp(model, optimizer, x, margin, target, target_weight, forward=None, criterion=None, stats=None):
+def train_step_dp(model, optimizer, x, margin, target, target_weight, forward=None, criterion=None, stats=None,
+                  scheduler=None):
     """One data-parallel training step on this rank's clips - the reference's ``nn.DataParallel`` iteration
     (train.py:78-79, script/Common.py:118-144) as one process per GPU:
 
@@ -352,7 +353,10 @@ def train_step_dp(model, optimizer, x, margin, target, target_weight, forward=No
     ``stats`` (a dict, optional): filled with ``comm_ms`` - the wall time of the gradient exchange, bracketed by device
     synchronisations, i.e. the time between the last backward kernel and the optimizer that a scaling run loses to the collective -
     its payload ``comm_bytes`` and ``overlap`` (what of the exchange runs under the backward pass: nothing in the flat-buffer form).
-    Asking for it serialises the step; bench.py measures it in an extra, untimed step."""
+    Asking for it serialises the step; bench.py measures it in an extra, untimed step.
+
+    ``scheduler`` (optional, e.g. :func:`otpose_amd.schedule.make_scheduler`'s): stepped right after ``optimizer.step()``, once
+    per iteration as at script/Common.py:143-144."""
     if forward is None or criterion is None:
         from . import train as _train
         forward = forward or _train.forward_train
@@ -385,4 +389,6 @@ def train_step_dp(model, optimizer, x, margin, target, target_weight, forward=No
         stats.update(comm_ms=1e3 * (time.perf_counter() - t0), comm_bytes=nbytes if collectives_on() else 0, world=world_size(),
                      overlap="none: the gradients are reduced after the backward pass (flat fp32 buffers / buckets in one go)")
     optimizer.step()
+    if scheduler is not None:
+        scheduler.step()
     return allreduce_mean_(loss.detach().clone())

@@ -41,6 +41,7 @@ extern "C" {
 #define OTP_DTYPE_F16 1          /* the reference dispatches f64 / f32 / f16 (AT_DISPATCH_FLOATING_TYPES_AND_HALF,      */
 #define OTP_DTYPE_BF16 2         /* deform_conv_cuda_kernel.cu:719,751,784); f16 / bf16 compute in fp32, f64 in fp64     */
 #define OTP_DTYPE_F64 3
+#define OTP_DTYPE_I64 4          /* int64 entries of otp_ema_update_table only (BatchNorm's num_batches_tracked) */
 
 #define OTP_ACT_NONE 0
 #define OTP_ACT_RELU 1
@@ -667,6 +668,29 @@ int otp_adamw_step(void* param, const void* grad, void* exp_avg, void* exp_avg_s
                    void* stream);
 int otp_sgd_step(void* param, const void* grad, void* momentum_buf, size_t n, float lr, float momentum, float dampening,
                  float weight_decay, int nesterov, int first_step, const void* gradnorm_sq_f64, float max_norm, void* stream);
+
+/* ---- weight EMA (thirdparty/utils/train_utils.py:240-262 ModelEma: ema_v.copy_(decay * ema_v + (1. - decay) * model_v) over
+ * every entry of state_dict()) ---------------------------------------------------------------------------------------------
+ * ema[i] = decay * ema[i] + one_minus_decay * src[i] in float32 with the two products and the sum each rounded (never an FMA):
+ * the bits of the reference's three PyTorch operations.  The caller passes one_minus_decay = (float)(1.0 - (double)decay), the
+ * subtraction in double as Python does it.  decay = 0, one_minus_decay = 1 copies src (for finite values).  ema and src must not
+ * overlap.  No atomics, no workspace: every element belongs to one thread, the same bits on every run.
+ * otp_ema_update: one flat float32 buffer of n elements; any n and any 4-byte-aligned pointers (16-byte accesses on the part of
+ * ema that is 16-byte aligned, element by element before and behind it).  OTP_ERR_BAD_ARG: NULL pointer; OTP_ERR_UNSUPPORTED: a
+ * pointer that is not 4-byte aligned; n == 0 is OTP_OK and launches nothing.
+ * otp_ema_update_table: the same update of every job of a table in ONE launch (BatchNorm running statistics, the int64
+ * counters, parameters outside a flat buffer: hundreds of tensors of 1 .. 10^6 elements).  otp_ema_job writes the
+ * otp_ema_job_bytes() bytes of one job (opaque to the caller) to HOST memory: `count` elements of `dtype` OTP_DTYPE_F32
+ * (4-byte-aligned pointers) or OTP_DTYPE_I64 (8-byte-aligned; value -> float32, the same two products and sum, back by truncation
+ * toward zero - Tensor.copy_ from float into long; |value| < 2^63).  prev_job_host: the job written just before this one in the
+ * same table (NULL for the first): a job carries the running sum of the work before it, by which the kernel deals 1024-element
+ * units to its workgroups, so a table is written front to back and a job is not moved to another place.  The caller keeps the
+ * jobs as one contiguous table in device memory (8-byte aligned).  OTP_ERR_BAD_ARG: NULL pointer, n_jobs < 0 (n_jobs == 0 is
+ * OTP_OK and launches nothing); OTP_ERR_UNSUPPORTED: another dtype code, a misaligned pointer, count > 2^48. */
+int otp_ema_update(void* ema, const void* src, size_t n, float decay, float one_minus_decay, void* stream);
+size_t otp_ema_job_bytes(void);
+int otp_ema_job(void* ema, const void* src, size_t count, int dtype, const void* prev_job_host, void* job_host);
+int otp_ema_update_table(const void* jobs_device, int n_jobs, float decay, float one_minus_decay, void* stream);
 
 /* ---- input assembly (the step before the path: dataset/PoseTrackDataset.py:397-406 transform per frame =
  * utils/transform.py:7-15 ToTensor + Normalize, script/Common.py:117 torch.cat over the frames) ---------------------

@@ -7,6 +7,8 @@
 // TRAIN.OPTIMIZER = SGD (train_utils.py:123-128, torch.optim.SGD semantics) is a second update kernel behind the same clip.
 #include "common.h"
 
+#include <string.h>
+
 namespace {
 
 constexpr int SUMSQ_PARTS = 1024;       // most workgroups of one sum-of-squares launch = scratch doubles behind the accumulator
@@ -129,6 +131,96 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
         }
 }
 
+// ---- weight EMA (thirdparty/utils/train_utils.py:240-262 ModelEma) ------------------------------------------------------------
+// ema = decay * ema + one_minus_decay * src, the two products and the sum each rounded to fp32: the bits of the reference's
+// three PyTorch operations (mul by a Python scalar, mul, add).  Never an FMA.
+__device__ __forceinline__ float ema_one(float e, float m, float d, float omd) {
+#pragma clang fp contract(off)
+    const float a = d * e;
+    const float b = omd * m;
+    return a + b;
+}
+
+// int64 entries (BatchNorm's num_batches_tracked): to fp32, the same arithmetic, back by truncation toward zero - what
+// `long_tensor.copy_(decay * long_tensor + (1 - decay) * long_tensor)` does
+__device__ __forceinline__ long long ema_one_i64(long long e, long long m, float d, float omd) {
+    return (long long)ema_one((float)e, (float)m, d, omd);
+}
+
+typedef float ema_f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));       // a 16-byte load from a 4-byte-aligned address
+
+// Elements live at positions q = shift + index, shift = the floats between the preceding 16-byte boundary and `ema`, so that
+// q % 4 == 0 is a 16-byte-aligned address of ema: ema_al = ema - shift, src_al = src - shift, valid positions [lo, hi).  One
+// quad of positions: a 16-byte load / store where it lies inside [lo, hi) (src may sit at another offset from its own boundary:
+// its load asks for 4-byte alignment only), element by element at the two ends (the scalar head and tail).
+__device__ __forceinline__ void ema_quad(float* __restrict__ ema_al, const float* __restrict__ src_al, size_t q, size_t lo,
+                                         size_t hi, float d, float omd) {
+    if (q >= lo && q + 4 <= hi) {
+        otp_f32x4 e = *reinterpret_cast<const otp_f32x4*>(ema_al + q);
+        const otp_f32x4 m = *reinterpret_cast<const ema_f32x4_a4*>(src_al + q);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) e[k] = ema_one(e[k], m[k], d, omd);
+        *reinterpret_cast<otp_f32x4*>(ema_al + q) = e;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (q + k >= lo && q + k < hi) ema_al[q + k] = ema_one(ema_al[q + k], src_al[q + k], d, omd);
+    }
+}
+
+__global__ __launch_bounds__(256) void ema_flat_kernel(float* __restrict__ ema_al, const float* __restrict__ src_al, size_t lo,
+                                                        size_t hi, float d, float omd) {
+    const size_t quads = (hi + 3) / 4;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < quads; i += (size_t)gridDim.x * 256)
+        ema_quad(ema_al, src_al, i * 4, lo, hi, d, omd);
+}
+
+// One entry of otp_ema_update_table's device table, written by otp_ema_job.  The work of a table is cut into units of
+// EMA_UNIT positions (one 16-byte access per thread of a workgroup); unit0 / unit_end are the running sum of the units of the
+// jobs before / up to this one, so the last job's unit_end is the table's total and a unit number finds its job by bisection.
+struct EmaJob {
+    void* ema;
+    const void* src;
+    unsigned long long count;
+    unsigned long long unit0, unit_end;
+    int dtype;
+    int shift;                            // fp32: floats between the preceding 16-byte boundary and ema (0 .. 3); int64: 0
+};
+constexpr unsigned long long EMA_UNIT = 1024;
+constexpr unsigned EMA_TABLE_GRID = 2048;
+
+// Workgroup b takes the units [b * total / grid, (b + 1) * total / grid): one bisection for its first unit, then it walks the
+// table forward - a tensor of a million elements is spread over many workgroups, a hundred 64-element ones share one.
+__global__ __launch_bounds__(256) void ema_table_kernel(const EmaJob* __restrict__ jobs, int n_jobs, float d, float omd) {
+    const unsigned long long total = jobs[n_jobs - 1].unit_end;
+    const unsigned long long per = total / gridDim.x, rem = total % gridDim.x, b = blockIdx.x;
+    unsigned long long u = b * per + (b < rem ? b : rem);
+    const unsigned long long u_end = u + per + (b < rem ? 1 : 0);
+    if (u >= u_end) return;
+    int lo = 0, hi = n_jobs - 1;          // the first job with unit_end > u
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (jobs[mid].unit_end > u) hi = mid; else lo = mid + 1;
+    }
+    int j = lo;
+    EmaJob job = jobs[j];
+    for (; u < u_end; ++u) {
+        while (u >= job.unit_end) job = jobs[++j];             // (jobs without elements own no unit and are stepped over)
+        const unsigned long long first = (u - job.unit0) * EMA_UNIT;
+        if (job.dtype == OTP_DTYPE_F32) {
+            const size_t vlo = (size_t)job.shift, vhi = vlo + (size_t)job.count;
+            float* ema_al = reinterpret_cast<float*>(reinterpret_cast<uintptr_t>(job.ema) - 4 * vlo);
+            const float* src_al = reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(job.src) - 4 * vlo);
+            ema_quad(ema_al, src_al, (size_t)first + 4 * threadIdx.x, vlo, vhi, d, omd);
+        } else {
+            long long* e = static_cast<long long*>(job.ema);
+            const long long* m = static_cast<const long long*>(job.src);
+            for (unsigned long long i = first + threadIdx.x; i < first + EMA_UNIT && i < job.count; i += 256)
+                e[i] = ema_one_i64(e[i], m[i], d, omd);
+        }
+    }
+}
+
 unsigned grid_for(size_t n4) {
     const size_t b = (n4 + 255) / 256;
     return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
@@ -179,5 +271,48 @@ extern "C" int otp_sgd_step(void* param, const void* grad, void* momentum_buf, s
                        static_cast<float*>(param), static_cast<const float*>(grad), static_cast<float*>(momentum_buf), n / 4, n,
                        lr, momentum, dampening, weight_decay, nesterov, first_step,
                        static_cast<const double*>(gradnorm_sq_f64), max_norm);
+    return otp_launch_status();
+}
+
+extern "C" size_t otp_ema_job_bytes(void) { return sizeof(EmaJob); }
+
+extern "C" int otp_ema_job(void* ema, const void* src, size_t count, int dtype, const void* prev_job_host, void* job_host) {
+    if (!job_host || !ema || !src) return OTP_ERR_BAD_ARG;
+    if (dtype != OTP_DTYPE_F32 && dtype != OTP_DTYPE_I64) return OTP_ERR_UNSUPPORTED;
+    const uintptr_t align = dtype == OTP_DTYPE_F32 ? 3 : 7;
+    if ((reinterpret_cast<uintptr_t>(ema) | reinterpret_cast<uintptr_t>(src)) & align) return OTP_ERR_UNSUPPORTED;
+    if (count > ((size_t)1 << 48)) return OTP_ERR_UNSUPPORTED;
+    EmaJob job;
+    memset(&job, 0, sizeof(job));
+    job.ema = ema;
+    job.src = src;
+    job.count = count;
+    job.dtype = dtype;
+    job.shift = dtype == OTP_DTYPE_F32 ? (int)((reinterpret_cast<uintptr_t>(ema) & 15) / 4) : 0;
+    job.unit0 = prev_job_host ? static_cast<const EmaJob*>(prev_job_host)->unit_end : 0;
+    job.unit_end = job.unit0 + (count ? ((unsigned long long)job.shift + count + EMA_UNIT - 1) / EMA_UNIT : 0);
+    memcpy(job_host, &job, sizeof(job));
+    return OTP_OK;
+}
+
+extern "C" int otp_ema_update(void* ema, const void* src, size_t n, float decay, float one_minus_decay, void* stream) {
+    if (!ema || !src) return OTP_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(ema) | reinterpret_cast<uintptr_t>(src)) & 3) return OTP_ERR_UNSUPPORTED;
+    if (n == 0) return OTP_OK;
+    const size_t shift = (reinterpret_cast<uintptr_t>(ema) & 15) / 4;
+    float* ema_al = reinterpret_cast<float*>(reinterpret_cast<uintptr_t>(ema) - 4 * shift);
+    const float* src_al = reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(src) - 4 * shift);
+    hipLaunchKernelGGL(ema_flat_kernel, dim3(grid_for((shift + n + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), ema_al,
+                       src_al, shift, shift + n, decay, one_minus_decay);
+    return otp_launch_status();
+}
+
+extern "C" int otp_ema_update_table(const void* jobs_device, int n_jobs, float decay, float one_minus_decay, void* stream) {
+    if (n_jobs < 0 || (n_jobs > 0 && !jobs_device)) return OTP_ERR_BAD_ARG;
+    if (n_jobs == 0) return OTP_OK;
+    if (reinterpret_cast<uintptr_t>(jobs_device) & 7) return OTP_ERR_UNSUPPORTED;
+    // the table is device memory: its total is not known here, so the grid is fixed and a workgroup without a unit returns
+    hipLaunchKernelGGL(ema_table_kernel, dim3(EMA_TABLE_GRID), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const EmaJob*>(jobs_device), n_jobs, decay, one_minus_decay);
     return otp_launch_status();
 }

@@ -338,7 +338,7 @@ def joint_flags(target: torch.Tensor) -> torch.Tensor:
 
 
 def train_step_dp(model, optimizer, x, margin, target, target_weight, forward=None, criterion=None, stats=None,
-                  scheduler=None):
+                  scheduler=None, ema=None):
     """One data-parallel training step on this rank's clips - the reference's ``nn.DataParallel`` iteration
     (train.py:78-79, script/Common.py:118-144) as one process per GPU:
 
@@ -356,7 +356,10 @@ def train_step_dp(model, optimizer, x, margin, target, target_weight, forward=No
     Asking for it serialises the step; bench.py measures it in an extra, untimed step.
 
     ``scheduler`` (optional, e.g. :func:`otpose_amd.schedule.make_scheduler`'s): stepped right after ``optimizer.step()``, once
-    per iteration as at script/Common.py:143-144."""
+    per iteration as at script/Common.py:143-144.
+
+    ``ema`` (optional, an :class:`otpose_amd.ema.ModelEma`): ``ema.update(model)`` right after ``optimizer.step()``.  No
+    communication: after the gradient all-reduce the weights, and so their average, are the same on every rank."""
     if forward is None or criterion is None:
         from . import train as _train
         forward = forward or _train.forward_train
@@ -389,6 +392,8 @@ def train_step_dp(model, optimizer, x, margin, target, target_weight, forward=No
         stats.update(comm_ms=1e3 * (time.perf_counter() - t0), comm_bytes=nbytes if collectives_on() else 0, world=world_size(),
                      overlap="none: the gradients are reduced after the backward pass (flat fp32 buffers / buckets in one go)")
     optimizer.step()
+    if ema is not None:
+        ema.update(model)
     if scheduler is not None:
         scheduler.step()
     return allreduce_mean_(loss.detach().clone())

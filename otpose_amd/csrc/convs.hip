@@ -57,120 +57,162 @@ struct SPlan {
 // and one 16-byte store per image and part - every store instruction of a wave writes 1 KB of consecutive records.  (Round 3's
 // form gave a thread 4 consecutive pixels: its stores were 16-byte pieces 64 bytes apart, and the pass ran at 2.4 TB/s;
 // "store-run length is worth a factor on this chip")
+// Index decode: blockIdx.z / blockIdx.y are the plane pair (n, g), blockIdx.x walks the 256-pixel pieces of one; every plane base and the
+// piece's offset are wave-uniform 64-bit values (scalar registers), a lane adds its own threadIdx.x - no division.
 __global__ __launch_bounds__(256) void s8_pack_kernel(const float* __restrict__ in, otp_u32x4* __restrict__ out, float* __restrict__ c4,
                                                        int N, int C, int HW, int ctot, int coff, unsigned* rflag) {
     const int G8 = C >> 3;
-    const size_t items = (size_t)N * G8 * HW;
+    const size_t p0 = (size_t)blockIdx.x * 256;
+    if (p0 + threadIdx.x >= (size_t)HW) return;
     bool bad = false;                                               // range guard (common.h): a value its half pieces cannot hold
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < items; i += (size_t)gridDim.x * 256) {
-        const int p = (int)(i % HW);
-        const size_t r = i / HW;
-        const int g = (int)(r % G8), n = (int)(r / G8);
-        const float* src = in + ((size_t)n * ctot + coff + 8 * g) * HW + p;
+    for (int n = blockIdx.z; n < N; n += gridDim.z)
+    for (int g = blockIdx.y; g < G8; g += gridDim.y) {              // (both loops run once unless a dimension exceeds the grid's limit)
+        const int ng = n * G8 + g;
+        const float* src = in + ((size_t)n * ctot + coff + 8 * g) * HW + p0;
         float f[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = src[(size_t)e * HW];
+        for (int e = 0; e < 8; ++e) f[e] = (src + (size_t)e * HW)[threadIdx.x];
 #pragma unroll
         for (int e = 0; e < 8; ++e) bad |= otp_out_of_range(f[e]);
         otp_u32x4 hi, lo;
         otp_x3_split8(f, hi, lo);
-        otp_u32x4* dst = out + ((size_t)(n * G8 + g) * 2) * HW + p;
-        dst[0] = hi;
-        dst[HW] = lo;
+        otp_u32x4* dst = out + (size_t)ng * 2 * HW + p0;
+        dst[threadIdx.x] = hi;
+        (dst + HW)[threadIdx.x] = lo;
         if (c4) {
-            otp_f32x4* d4 = reinterpret_cast<otp_f32x4*>(c4) + ((size_t)n * (C >> 2) + 2 * g) * HW + p;
-            d4[0] = (otp_f32x4){f[0], f[1], f[2], f[3]};
-            d4[HW] = (otp_f32x4){f[4], f[5], f[6], f[7]};
+            otp_f32x4* d4 = reinterpret_cast<otp_f32x4*>(c4) + ((size_t)n * (C >> 2) + 2 * g) * HW + p0;
+            d4[threadIdx.x] = (otp_f32x4){f[0], f[1], f[2], f[3]};
+            (d4 + HW)[threadIdx.x] = (otp_f32x4){f[4], f[5], f[6], f[7]};
         }
     }
     otp_range_report(rflag, bad, OTP_RANGE_S8PASS);
 }
 
 // A fuse row's upsampled terms (HRNet.py:487-494; otp_upsample_add_multi: out = act(res + up_f0(low0) + up_f1(low1) + ...), added
-// in that order) written as the images the next module's branch reads: S8 + C4 (and the NCHW tensor only when somebody else
-// needs it).  Same additions in the same order as upsample_add_multi_kernel: bit-identical values.  A thread owns 4
-// consecutive pixels of one 8-channel group.
+// in that order) written as the images the next module's branch reads: S8, C4 when asked for (and the NCHW tensor only when
+// somebody else needs it).  Same additions in the same order as upsample_add_multi_kernel: bit-identical values.
+// `res`: the fp32 NCHW residual, or (RES_S8) its S8 image - hi + lo of the records, the same 4 bytes per element.
 struct S8Up {
     const float* low[3];
     int f[3];
     int n;
 };
-// the round-3 form: a thread owns 4 consecutive pixels of one 8-channel group - a quarter of the low-resolution loads per pixel
-// (kept for rows with three upsampled terms, where those loads outweigh the short store runs: 117 against 138 us at 48 channels
-// @96x72 with terms at 1/2, 1/4, 1/8 resolution; with one or two terms the one-pixel form below is 25 % faster)
-// `res`: the fp32 NCHW residual, or (res_s8 != 0) its S8 image - hi + lo of the records, the same 4 bytes per element
-__global__ __launch_bounds__(256) void s8_upsample_add4_kernel(S8Up U, const float* __restrict__ res, float* out_nchw,
-                                                               otp_u32x4* __restrict__ out_s8, float* __restrict__ out_c4, int N, int C,
-                                                               int Hh, int Wh, int relu, int res_ctot, int res_coff, int out_ctot,
-                                                               int out_coff, int res_s8, unsigned* rflag) {
-    const int HW = Hh * Wh, q4 = HW >> 2, G8 = C >> 3, Wh4 = Wh >> 2;
-    const size_t items = (size_t)N * G8 * q4;
-    bool bad = false;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < items; i += (size_t)gridDim.x * 256) {
-        const int q = (int)(i % q4);
-        const size_t r = i / q4;
-        const int g = (int)(r % G8), n = (int)(r / G8);
-        const int y = q / Wh4, x4 = q - y * Wh4;
-        otp_f32x4 v[8];
-        if (res_s8) {                                               // (uniform) records of the four pixels -> v[channel][pixel]
-            const otp_u32x4* rs = reinterpret_cast<const otp_u32x4*>(res) + ((size_t)(n * G8 + g) * 2) * HW + 4 * q;
+struct S8Fuse {
+    const float* low[3];
+    int sh[3];                            // log2 of the factors (each >= 1)
+    int N, C, Hh, Wh, relu, res_ctot, res_coff, out_ctot, out_coff;
+    uint32_t mW;                          // otp_magic(Wh)
+    unsigned* rflag;
+};
+
+// A thread owns column x of the two rows (2 r, 2 r + 1) of one 8-channel group's plane pair: every factor is >= 2, so both
+// pixels read the SAME low-resolution value of every term - one gather and one index decode per 128 bytes moved.  Loads and
+// stores of the S8 / C4 records keep the one-pixel shape (a lane's 16 bytes next to its neighbour's: 1 KB runs per wave
+// instruction, which is what the one-pixel form won over a four-pixel one with).  Index decode: blockIdx.z / blockIdx.y are the
+// plane pair (n, g); inside one, pixel -> (row pair, column) is one magic multiply (exact: the launcher checks (HW / 2) * Wh <
+// 2^32) and factors are shifts.  Every access is a buffer instruction: the descriptor holds the wave-uniform 64-bit base of the
+// group's planes (and their exact size, so no lane can reach outside them), the lane gives ONE 32-bit byte offset per image,
+// and channel / part / second-row strides are the instruction's scalar offset (HW <= 2^26: checked by the launcher) - no
+// per-access address arithmetic in the vector unit.  All loads are issued before the first add.
+template <int NLOW, bool RES_S8, bool NCHW_OUT, bool C4_OUT>
+__global__ __launch_bounds__(256) void s8_fuse_pass_kernel(S8Fuse U, const void* __restrict__ res, float* __restrict__ out_nchw,
+                                                           otp_u32x4* __restrict__ out_s8, float* __restrict__ out_c4) {
+    const uint32_t Wh = (uint32_t)U.Wh, HW = (uint32_t)(U.Hh * U.Wh);
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;             // (row pair, column) of the plane pair
+    if (t >= (HW >> 1)) return;
+    const uint32_t r = otp_magic_div(t, U.mW), x = t - r * Wh;
+    const int pa = (int)(t + r * Wh);                               // pixel (2 r, x); (2 r + 1, x) = pa + Wh
+    int lo_off[NLOW];                                               // byte offset of the pixels' value in a term's plane
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const otp_u32x4 h = rs[k], l = rs[(size_t)HW + k];
+    for (int k = 0; k < NLOW; ++k) lo_off[k] = (int)((((r >> (U.sh[k] - 1)) * (Wh >> U.sh[k])) + (x >> U.sh[k])) * 4u);
+    const int G8 = U.C >> 3;
+    const int rowB = (int)(Wh * 16u), partB = (int)(HW * 16u);      // S8 / C4 records: the row below, the other part / half
+    bool bad = false;
+    for (int n = blockIdx.z; n < U.N; n += gridDim.z)
+    for (int g = blockIdx.y; g < G8; g += gridDim.y) {              // (both loops run once unless a dimension exceeds the grid's limit)
+        const size_t ng = (size_t)n * G8 + g;
+        float v[2][8], l[NLOW][8];
+        otp_u32x4 rh[2], rl[2];
+        if constexpr (RES_S8) {                                     // the two pixels' record pairs of this channel group
+            const otp_rsrc rr = make_rsrc32(static_cast<const char*>(res) + ng * 2 * HW * 16, 2u * HW * 16u);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                rh[j] = __builtin_bit_cast(otp_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, pa * 16, j * rowB, 0));
+                rl[j] = __builtin_bit_cast(otp_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, pa * 16, partB + j * rowB, 0));
+            }
+        } else {
+            const otp_rsrc rr = make_rsrc32(static_cast<const float*>(res) + ((size_t)n * U.res_ctot + U.res_coff + 8 * g) * HW, 8u * HW * 4u);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                v[0][e] = bload(rr, pa * 4, (int)(e * HW * 4u));
+                v[1][e] = bload(rr, pa * 4, (int)((e * HW + Wh) * 4u));
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NLOW; ++k) {
+            const uint32_t plane = HW >> (2 * U.sh[k]);             // pixels of a channel of term k
+            const otp_rsrc rk = make_rsrc32(U.low[k] + ((size_t)n * U.C + 8 * g) * plane, 8u * plane * 4u);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) l[k][e] = bload(rk, lo_off[k], (int)(e * plane * 4u));
+        }
+        if constexpr (RES_S8) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int e2 = 0; e2 < 4; ++e2) {
-                    const otp_f32x2 a = otp_x3_widen(h[e2]) + otp_x3_widen(l[e2]);
-                    v[2 * e2][k] = a.x;
-                    v[2 * e2 + 1][k] = a.y;
+                    const otp_f32x2 a = otp_x3_widen(rh[j][e2]) + otp_x3_widen(rl[j][e2]);
+                    v[j][2 * e2] = a.x;
+                    v[j][2 * e2 + 1] = a.y;
                 }
-            }
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const int c = 8 * g + e;
-            otp_f32x4 o = res_s8 ? v[e] : *reinterpret_cast<const otp_f32x4*>(res + ((size_t)n * res_ctot + res_coff + c) * HW + 4 * q);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                if (k < U.n) {
-                    const int f = U.f[k], Wl = Wh / f, Hl = Hh / f;
-                    const float* lrow = U.low[k] + (((size_t)n * C + c) * Hl + y / f) * Wl;
-                    if (f >= 4) {
-                        o = o + lrow[(4 * x4) / f];
-                    } else {
-                        const float l0 = lrow[2 * x4], l1 = lrow[2 * x4 + 1];
-                        o = o + (otp_f32x4){l0, l0, l1, l1};
-                    }
-                }
+            for (int j = 0; j < 2; ++j) {
+                float o = v[j][e];
+#pragma unroll
+                for (int k = 0; k < NLOW; ++k) o = o + l[k][e];
+                bad |= otp_out_of_range(o);
+                v[j][e] = o;
             }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bad |= otp_out_of_range(o[j]);
-            if (relu) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = fmaxf(o[j], 0.f);
-            }
-            v[e] = o;
-            if (out_nchw) *reinterpret_cast<otp_f32x4*>(out_nchw + ((size_t)n * out_ctot + out_coff + c) * HW + 4 * q) = o;
         }
-        otp_u32x4* dst = out_s8 + ((size_t)(n * G8 + g) * 2) * HW + 4 * q;
+        if (U.relu) {                                               // (uniform: one branch, not a select per value)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float f[8];
+            for (int e = 0; e < 8; ++e) {
+                v[0][e] = otp_relu(v[0][e]);                        // (a sum is never a signalling NaN: = fmaxf(., 0.f) bit for bit)
+                v[1][e] = otp_relu(v[1][e]);
+            }
+        }
+        if constexpr (NCHW_OUT) {
+            const otp_rsrc ro = make_rsrc32(out_nchw + ((size_t)n * U.out_ctot + U.out_coff + 8 * g) * HW, 8u * HW * 4u);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) f[e] = v[e][k];
+            for (int e = 0; e < 8; ++e) {
+                bstore(v[0][e], ro, pa * 4, (int)(e * HW * 4u));
+                bstore(v[1][e], ro, pa * 4, (int)((e * HW + Wh) * 4u));
+            }
+        }
+        const otp_rsrc rs = make_rsrc32(reinterpret_cast<char*>(out_s8) + ng * 2 * HW * 16, 2u * HW * 16u);
+        otp_rsrc rc;
+        if constexpr (C4_OUT) rc = make_rsrc32(reinterpret_cast<char*>(out_c4) + ((size_t)n * (U.C >> 2) + 2 * g) * HW * 16, 2u * HW * 16u);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
             otp_u32x4 hi, lo;
-            otp_x3_split8(f, hi, lo);
-            dst[k] = hi;
-            dst[(size_t)HW + k] = lo;
-            if (out_c4) {
-                otp_f32x4* d4 = reinterpret_cast<otp_f32x4*>(out_c4) + ((size_t)n * (C >> 2) + 2 * g) * HW + 4 * q + k;
-                d4[0] = (otp_f32x4){f[0], f[1], f[2], f[3]};
-                d4[HW] = (otp_f32x4){f[4], f[5], f[6], f[7]};
+            otp_x3_split8(v[j], hi, lo);
+            __builtin_amdgcn_raw_buffer_store_b128(hi, rs, pa * 16, j * rowB, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(lo, rs, pa * 16, partB + j * rowB, 0);
+            if constexpr (C4_OUT) {
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(otp_u32x4, (otp_f32x4){v[j][0], v[j][1], v[j][2], v[j][3]}), rc,
+                                                       pa * 16, j * rowB, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(otp_u32x4, (otp_f32x4){v[j][4], v[j][5], v[j][6], v[j][7]}), rc,
+                                                       pa * 16, partB + j * rowB, 0);
             }
         }
     }
-    otp_range_report(rflag, bad, OTP_RANGE_S8PASS);
+    otp_range_report(U.rflag, bad, OTP_RANGE_S8PASS);
 }
 
+// The one-pixel form the template replaced, kept ONLY for maps beyond the template's 32-bit index arithmetic ((Hh Wh / 2) Wh >=
+// 2^32 or Hh Wh > 2^26): a thread owns one pixel of one 8-channel group, 64-bit index decode per item.
 __global__ __launch_bounds__(256) void s8_upsample_add_kernel(S8Up U, const float* __restrict__ res, float* out_nchw,
                                                                otp_u32x4* __restrict__ out_s8, float* __restrict__ out_c4, int N, int C,
                                                                int Hh, int Wh, int relu, int res_ctot, int res_coff, int out_ctot,
@@ -794,9 +836,9 @@ extern "C" int otp_s8_pack(const void* in, void* out, void* out_c4, int N, int C
     if (C % 8 || ((H * W) & 3) ||
         ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(out_c4)) & 15))
         return OTP_ERR_UNSUPPORTED;
-    const size_t items = (size_t)N * (C / 8) * (H * W);
-    const int grid = (int)((items + 255) / 256 > 16384 ? 16384 : (items + 255) / 256);
-    hipLaunchKernelGGL(s8_pack_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const float*>(in),
+    const int G8 = C / 8;
+    const dim3 grid((unsigned)((H * W + 255) / 256), (unsigned)(G8 > 65535 ? 65535 : G8), (unsigned)(N > 65535 ? 65535 : N));
+    hipLaunchKernelGGL(s8_pack_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const float*>(in),
                        static_cast<otp_u32x4*>(out), static_cast<float*>(out_c4), N, C, H * W, in_ctot, in_coff, otp_range_word());
     return otp_launch_status();
 }
@@ -817,30 +859,52 @@ extern "C" int otp_s8_upsample_add_ex(const void* const* lows, const int* factor
     const int res_s8 = res_layout;                      // 1: `res` is the S8 image of the (N, C, Hh, Wh) residual
     if (Wh % 4 || C % 8 || (!res_s8 && res_ctot < res_coff + C) || (out_nchw && out_ctot < out_coff + C)) return OTP_ERR_UNSUPPORTED;
     S8Up U{};
+    S8Fuse F{};
     U.n = nlow;
     for (int k = 0; k < nlow; ++k) {
         const int f = factors[k];
         if (!lows[k]) return OTP_ERR_BAD_ARG;
         if (f < 2 || (f & (f - 1)) || Hh % f || Wh % f) return OTP_ERR_UNSUPPORTED;
-        U.low[k] = static_cast<const float*>(lows[k]);
+        U.low[k] = F.low[k] = static_cast<const float*>(lows[k]);
         U.f[k] = f;
+        F.sh[k] = __builtin_ctz((unsigned)f);
     }
     if ((reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(out_nchw) | reinterpret_cast<uintptr_t>(out_s8) |
          reinterpret_cast<uintptr_t>(out_c4)) & 15)
         return OTP_ERR_UNSUPPORTED;
-    if (nlow >= 3) {
-        const size_t items4 = (size_t)N * (C / 8) * (Hh * Wh / 4);
-        const int grid4 = (int)((items4 + 255) / 256 > 8192 ? 8192 : (items4 + 255) / 256);
-        hipLaunchKernelGGL(s8_upsample_add4_kernel, dim3(grid4), dim3(256), 0, static_cast<hipStream_t>(stream), U,
-                           static_cast<const float*>(res), static_cast<float*>(out_nchw), static_cast<otp_u32x4*>(out_s8),
-                           static_cast<float*>(out_c4), N, C, Hh, Wh, relu, res_ctot, res_coff, out_ctot, out_coff, res_s8, otp_range_word());
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t HW = (size_t)Hh * Wh;
+    // the template's index arithmetic: the magic division of a (row pair, column) index by Wh, 32-bit byte offsets inside a plane pair
+    if ((HW / 2) * (size_t)Wh < (1ull << 32) && HW <= (1u << 26)) {
+        F.N = N; F.C = C; F.Hh = Hh; F.Wh = Wh; F.relu = relu;
+        F.res_ctot = res_ctot; F.res_coff = res_coff; F.out_ctot = out_ctot; F.out_coff = out_coff;
+        F.mW = otp_magic((uint32_t)Wh);
+        F.rflag = otp_range_word();
+        const int G8 = C / 8;
+        const dim3 grid((unsigned)((HW / 2 + 255) / 256), (unsigned)(G8 > 65535 ? 65535 : G8), (unsigned)(N > 65535 ? 65535 : N));
+        // instantiation = (number of terms, residual layout, NCHW output, C4 output): 24 kernels, each without the others' branches
+        const int pick = ((nlow - 1) * 2 + res_s8) * 4 + (out_nchw ? 2 : 0) + (out_c4 ? 1 : 0);
+        switch (pick) {
+#define OTP_FUSE_CASE(I, NL, RS, NC, C4)                                                                                          \
+    case I:                                                                                                                        \
+        hipLaunchKernelGGL((s8_fuse_pass_kernel<NL, RS, NC, C4>), grid, dim3(256), 0, st, F, res, static_cast<float*>(out_nchw), \
+                           static_cast<otp_u32x4*>(out_s8), static_cast<float*>(out_c4));                                          \
+        break;
+#define OTP_FUSE_CASES4(I, NL, RS)                                                                                                \
+    OTP_FUSE_CASE(I, NL, RS, false, false) OTP_FUSE_CASE(I + 1, NL, RS, false, true) OTP_FUSE_CASE(I + 2, NL, RS, true, false)     \
+    OTP_FUSE_CASE(I + 3, NL, RS, true, true)
+            OTP_FUSE_CASES4(0, 1, false) OTP_FUSE_CASES4(4, 1, true) OTP_FUSE_CASES4(8, 2, false) OTP_FUSE_CASES4(12, 2, true)
+            OTP_FUSE_CASES4(16, 3, false) OTP_FUSE_CASES4(20, 3, true)
+#undef OTP_FUSE_CASES4
+#undef OTP_FUSE_CASE
+        }
         return otp_launch_status();
     }
-    const size_t items = (size_t)N * (C / 8) * (Hh * Wh);
+    const size_t items = (size_t)N * (C / 8) * HW;
     const int grid = (int)((items + 255) / 256 > 16384 ? 16384 : (items + 255) / 256);
-    hipLaunchKernelGGL(s8_upsample_add_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), U,
-                       static_cast<const float*>(res), static_cast<float*>(out_nchw), static_cast<otp_u32x4*>(out_s8),
-                       static_cast<float*>(out_c4), N, C, Hh, Wh, relu, res_ctot, res_coff, out_ctot, out_coff, res_s8, otp_range_word());
+    hipLaunchKernelGGL(s8_upsample_add_kernel, dim3(grid), dim3(256), 0, st, U, static_cast<const float*>(res),
+                       static_cast<float*>(out_nchw), static_cast<otp_u32x4*>(out_s8), static_cast<float*>(out_c4), N, C, Hh, Wh, relu,
+                       res_ctot, res_coff, out_ctot, out_coff, res_s8, otp_range_word());
     return otp_launch_status();
 }
 

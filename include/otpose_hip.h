@@ -931,6 +931,60 @@ int otp_pose_nms(const void* pr_off, const void* pr_sample, const void* preds, c
                  int mode, int max_dets, void* keep, void* person_score, void* rank, void* oks, int F, int NP, int N,
                  void* stream);
 
+/* ---- Person detector: the kernels around the Darknet convolutions of the reference's object_detector/YOLOv3 (csrc/detect.hip,
+ * DESIGN.md section 3.12).  The convolutions themselves are otp_conv2d with OTP_ACT_NONE and BatchNorm folded into scale / shift.
+ * All float32 arithmetic below is uncontracted: every product, quotient and sum is rounded on its own.  No allocation, no
+ * synchronisation: graph-capturable.
+ *
+ * otp_letterbox_u8: frames (B, H, W, 3) uint8 -> out (B, 3, S, S) float32, the network input of detector_utils.py:12-38 in one
+ * pass.  With D = max(H, W) the frame is padded to D x D by |H - W| / 2 (rounded down) rows before and the rest after when
+ * H <= W, columns otherwise, with the level 127 (what np.pad stores for 127.5 in a uint8 image); output pixel (oy, ox) is the
+ * coverage-weighted mean of the padded square over [ox D / S, (ox + 1) D / S) x [oy D / S, (oy + 1) D / S) (the meaning of
+ * INTER_AREA), evaluated exactly in integers, rounded to the nearest level (a tie up), converted to float32 and divided by 255.
+ * OTP_ERR_UNSUPPORTED for D < S (no longer an area average), D > 16384 or S > 4096.
+ *
+ * otp_leaky_pass: out = up2?( leaky?(in) + shortcut? ) on channel slices of (N, *_ctot, H, W) tensors (out: (N, out_ctot,
+ * up H, up W)): leaky != 0 applies x > 0 ? x : 0.1f * x, shortcut may be NULL, up is 1 or 2 (nearest).  Darknet's [shortcut]
+ * adds after the activation and [upsample] follows it, so one pass serves conv -> shortcut and conv -> upsample; with
+ * leaky = 0 it is a plain add / upsample / slice copy.  out must not overlap in.
+ *
+ * otp_yolo_decode: one [yolo] layer in eval mode (models.py:123-165).  in (B, A (5 + C), G, G) float32; rows
+ * row_off + (a G + gy) G + gx of pred (B, N, 5 + C) receive ((sigmoid(tx) + gx) s, (sigmoid(ty) + gy) s, (exp(tw) aw) s,
+ * (exp(th) ah) s, sigmoid(conf), sigmoid(cls...)) with s = float(img_size / G) and aw = float(anchor_w / (img_size / G)).
+ * anchors: 2 A doubles (w, h in input pixels) in HOST memory, passed on by value.  A <= OTP_YOLO_MAX_ANCHORS, C <= 250.
+ *
+ * otp_box_nms_merge: detector_utils.py:253-291 and detector_yolov3.py:79-98 for every image of pred (B, N, 5 + C), one
+ * workgroup per image, no limit on the number of candidates (workspace: otp_box_nms_merge_workspace(B, N) bytes of device memory,
+ * contents irrelevant).
+ *   candidates     the rows with conf >= conf_thres; score = conf * max(cls), class = the first arg-max of cls,
+ *                  box = (cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2).
+ *   order          descending score, equal scores by ascending row (the reference's argsort leaves ties open); a NaN score last.
+ *   loop           the first live candidate h is kept.  It takes every live candidate p (itself too) of its class with
+ *                  iou(h, p) > nms_thres, iou = inter / (area_h + area_p - inter + 1e-16f) with the +1 pixel convention of
+ *                  bbox_iou (detector_utils.py:211-218) on the unmerged boxes; the kept box is sum(conf_p box_p) / sum(conf_p)
+ *                  over the taken rows, conf and class stay h's.  The sums run in a fixed order (per thread over p = h + t,
+ *                  h + t + 1024, ..., then a butterfly over the 64 lanes, then the 16 waves in turn), not the reference's.
+ *   outputs        counts (B) int32; dets (B, max_out, 6) float32 rows (x1, y1, x2, y2, conf, class) in keep order;
+ *                  person_counts (B) int32, person_boxes (B, max_out, 4) float64 and person_scores (B, max_out) float32: of the
+ *                  kept rows of class person_class, in keep order, x = ((double(x1) - pad_x2) / unpad_w) * frame_w,
+ *                  y = ((double(y1) - pad_y2) / unpad_h) * frame_h, w = ((double(x2) - double(x1)) / unpad_w) * frame_w,
+ *                  h likewise, and conf.  The caller evaluates pad_x2 = pad_x // 2, pad_y2, unpad_w, unpad_h in float64 as
+ *                  detector_yolov3.py:79-83 does.  Rows past a count are zero.  Kept rows past max_out are dropped (max_out = N
+ *                  never drops one).
+ * -1 for null pointers or non-positive sizes or a zero unpad_w / unpad_h, OTP_ERR_WORKSPACE for a short workspace. */
+#define OTP_YOLO_MAX_ANCHORS 16
+#define OTP_BOX_NMS_WS_WORDS 15
+int otp_letterbox_u8(const void* frames_u8, void* out, int B, int H, int W, int S, void* stream);
+int otp_leaky_pass(const void* in, const void* shortcut, void* out, int N, int C, int H, int W, int leaky, int up,
+                   int in_ctot, int in_coff, int sc_ctot, int sc_coff, int out_ctot, int out_coff, void* stream);
+int otp_yolo_decode(const void* in, void* pred, const double* anchors, int B, int A, int C, int G, int img_size, int N,
+                    int row_off, void* stream);
+size_t otp_box_nms_merge_workspace(int B, int N);
+int otp_box_nms_merge(const void* pred, int B, int N, int C, float conf_thres, float nms_thres, int person_class,
+                      double pad_x2, double pad_y2, double unpad_w, double unpad_h, double frame_w, double frame_h,
+                      int max_out, void* workspace, size_t workspace_bytes, void* counts, void* dets, void* person_counts,
+                      void* person_boxes, void* person_scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -768,7 +768,9 @@ typedef struct otp_nhwc_conv_desc {
     int out_mode;                /* 0: NHWC bf16 (+ per-tile channel statistics), 1: NCHW fp32 (+ bias), no statistics */
 } otp_nhwc_conv_desc;
 /* bytes of the packed bf16 weights / rows of the per-tile statistics buffer ([rows][2][CoutS] floats: sum, sum of squares
- * of the bf16-rounded outputs) / {MB, NB, CK, chunks, m-tiles, grid, LDS bytes, k-steps} of the launch (host only) */
+ * of the bf16-rounded outputs) / {MB, NB, CK, chunks, m-tiles, grid, LDS bytes, k-steps} of the launch (host only).
+ * The byte count, the statistics row count, the packer (direct and batched) and the launch share one route decision, made per
+ * call from the descriptor and OTPOSE_NHWC_HB / OTPOSE_NHWC_HBPW: pack and launch under the same settings. */
 size_t otp_nhwc_conv_weight_bytes(const otp_nhwc_conv_desc* desc);
 int otp_nhwc_conv_stats_rows(const otp_nhwc_conv_desc* desc);
 int otp_nhwc_conv_plan(const otp_nhwc_conv_desc* desc, int* out8);

@@ -63,6 +63,9 @@ def to_nchw(x: torch.Tensor, c: int) -> torch.Tensor:
 
 
 def _pack(weight, d, dgrad, packs=None):
+    """The packed bf16 operator of ``weight`` for descriptor ``d``: from ``packs`` (a :class:`PackCache`) when given, else one
+    ``otp_nhwc_conv_pack`` launch.  Both run the library's one packer (``pack_unit`` of ``csrc/nhwc.hip``) under the one route
+    decision that also sizes the buffer and picks the kernel of the launch."""
     if packs is not None:
         return packs.get(weight, d, dgrad)
     L = hip.lib()
@@ -81,9 +84,9 @@ class PackCache:
     host, which bounds the forward once the branches overlap on the device).
 
     The first step packs every operator where it is first needed and records a job for it (weight pointer, destination,
-    launch plan - ``otp_nhwc_conv_pack_job``); from then on :meth:`repack` at the start of a forward rewrites all
-    destinations from the current fp32 master weights (``otp_nhwc_conv_pack_batch``) and the uses only look their tensor
-    up.  The input-gradient operators are therefore those of the weights the forward saw.  Entries keep the weight storage
+    route and layout - ``otp_nhwc_conv_pack_job``, the same job ``otp_nhwc_conv_pack`` builds for itself); from then on
+    :meth:`repack` at the start of a forward rewrites all destinations from the current fp32 master weights
+    (``otp_nhwc_conv_pack_batch``: the same packer over the table of jobs) and the uses only look their tensor up.  The input-gradient operators are therefore those of the weights the forward saw.  Entries keep the weight storage
     alive, so a job never reads freed memory; a weight that moved (``model.to(...)``, FusedAdamW re-homing ``p.data`` into
     its flat buffer) gets new entries, and :meth:`repack` RETIRES every entry the previous forward did not look up (their
     old storage is released, they are no longer re-packed each step) and drops the whole table when the device changed."""

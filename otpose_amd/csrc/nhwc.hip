@@ -7,7 +7,8 @@
 // innermost both the activations (k = input channel) and the packed weights deliver a fragment as ONE 16-byte LDS
 // read, taps shift whole pixels (16-byte aligned), and nothing is transposed on the way in or out.
 //
-//   nhwc_conv_kernel<MB,NB>   implicit GEMM  out[px][co] = sum_{tap,ci} W[co][tap][ci] * x[px+tap][ci]   (forward and,
+//   nhwc_conv_kernel<MB,NB,K7,PIPE>
+//                             implicit GEMM  out[px][co] = sum_{tap,ci} W[co][tap][ci] * x[px+tap][ci]   (forward and,
 //                             with flipped / transposed weights, the input gradient); the epilogue also leaves the
 //                             per-tile sum / sum of squares of every output channel (BatchNorm batch statistics)
 //   nhwc_wgrad_kernel         dW[co][tap][ci] = sum_px gy[px][co] * x[px+tap][ci]: both operands are read from their
@@ -112,10 +113,13 @@ bool size_plan(const otp_nhwc_conv_desc* d, ConvPlan* p, int ck, int nb) {
     return p->lds <= OTP_LDS_LIMIT;
 }
 
+bool valid_desc(const otp_nhwc_conv_desc* d) {
+    return d && d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->kh > 0 && d->kw > 0 && d->stride > 0 &&
+           d->dil > 0 && d->pad >= 0;
+}
+
 bool make_plan(const otp_nhwc_conv_desc* d, ConvPlan* p) {
-    if (!d || d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->kh <= 0 || d->kw <= 0 ||
-        d->stride <= 0 || d->dil <= 0 || d->pad < 0)
-        return false;
+    if (!valid_desc(d)) return false;
     p->N = d->N, p->Cin = d->Cin, p->Cout = d->Cout;
     p->kh = d->kh, p->kw = d->kw, p->stride = d->stride, p->pad = d->pad, p->dil = d->dil, p->out_mode = d->out_mode;
     p->CinS = round_up(d->Cin, 8), p->CoutS = round_up(d->Cout, 8);
@@ -162,91 +166,21 @@ bool make_plan(const otp_nhwc_conv_desc* d, ConvPlan* p) {
 // element (o, i, dy, dx) of the EFFECTIVE conv is w[base + o*so + i*si + dy*sdy + dx*sdx] (the input-gradient conv
 // reads the same tensor with o <-> i swapped and the taps flipped)
 // ---------------------------------------------------------------------------------------------------------------------
-struct PackJob {                       // one weight re-layout: everything nhwc_pack_kernel takes by value
+struct PackJob {                       // one weight re-layout: what pack_unit reads, by value (otp_nhwc_conv_pack) or from a device table
     const float* w;
     bf16* out;
     long so, si, sdy, sdx, base;
-    size_t total;
-    ConvPlan p;
-    int hb, hbNTW, hbChunks;           // hb = 1: the operator of csrc/hb.hip's 3x3 kernel (layout: csrc/hb.h), p only carries Cin / Cout
+    size_t total;                      // packed elements = NhwcRoute::wbytes / 2
+    ConvPlan p;                        // hb = 0: the plan of nhwc_conv_kernel; else only Cin / Cout are set
+    int hb, hbNTW, hbChunks;           // hb = NhwcRoute::kind; 1: the operator of csrc/hb.hip's 3x3 kernel (layout: csrc/hb.h)
     int hbKS;                          // hb = 2: of its 1x1 kernel, hbKS k-steps
 };
 
-// 3x3 / pad 1 / stride 1 or 2 convolutions with Cin % 16 == 0 run on csrc/hb.hip's kernel (the fp16 engine's conv for bfloat16
-// NHWC tensors: whole-Cin window by LDS-DMA, weights streamed through registers, three workgroups per CU) where that is faster
-// than nhwc_conv_kernel (otp_hb_pays: 96 / 192-channel branches, the stride-2 fuse convs).  OTPOSE_NHWC_HB=0 keeps every layer on nhwc_conv_kernel, =2 sends every
-// shape the window kernel covers to it, whether it pays or not (A/B, tests).
-bool use_hb(const otp_nhwc_conv_desc* d) {
-    const char* e = getenv("OTPOSE_NHWC_HB");                      // (read per call: the tests switch it inside one process)
-    const int mode = e ? atoi(e) : 1;
-    return mode != 0 && d && (mode == 2 || otp_hb_pays(d)) && otp_hb_supported(d);
-}
-
-// 1x1 convolutions - the two projections of a TransformerBlock's MLP on (N, 1, T, C) sequences, HRNet's bottleneck / fuse 1x1s, and
-// their input gradients - run on csrc/hb.hip's pointwise kernel (the input register-resident, the weights streamed through the LDS): nhwc_conv_kernel re-stages
-// 46 KB of weights per 128-token tile and 136-channel chunk with one workgroup per CU (134 / 214 us per projection at cfg2).
-// Image-shaped 1x1 layers (HRNet's bottleneck and fuse 1x1s, with BatchNorm statistics) too: forward / input gradient at 80 frames
-// (tools/bf16_conv_bench.py, OTPOSE_NHWC_HB=2 against =0) 256 -> 64 @96x72 80.8 / 94.2 us against 174 / 141, 64 -> 256 106.7 / 81.7 against
-// 156 / 176, 96 -> 48 @48x36 12.1 against 30.0, 384 -> 48 @12x9 8.9 against 31.7 - every shape measured.
-bool hbpw_pays(const otp_nhwc_conv_desc*) { return true; }
-bool use_hbpw(const otp_nhwc_conv_desc* d) {
-    const char* e = getenv("OTPOSE_NHWC_HB");
-    const char* e2 = getenv("OTPOSE_NHWC_HBPW");                   // (=0: only the 1x1 kernel off)
-    const int mode = e ? atoi(e) : 1;
-    if (mode == 0 || (e2 && atoi(e2) == 0) || !d) return false;
-    return (mode == 2 || d->H == 1 || hbpw_pays(d)) && otp_hbpw_supported(d);
-}
-
-__device__ __forceinline__ float pack_hbpw_value(const float* __restrict__ w, const PackJob& jb, size_t i) {
-    const int j = (int)(i & 7);
-    const size_t r = i >> 3;
-    const int units = otp_hbpw_blkb(jb.hbKS) / 16;
-    const int blk = (int)(r / units), u = (int)(r % units);
-    if (u >= 2 * jb.hbKS * 64) return 0.f;
-    const int frag = u >> 6, lane = u & 63, m = frag / jb.hbKS, ks = frag - m * jb.hbKS, r16 = lane & 15, kq = lane >> 4;
-    const int o = 32 * blk + 8 * (r16 >> 2) + 4 * m + (r16 & 3), ci = 32 * ks + 8 * kq + j;
-    if (o >= jb.p.Cout || ci >= jb.p.Cin) return 0.f;
-    return w[jb.base + o * jb.so + ci * jb.si];
-}
-
-// element i of the packed operator of csrc/hb.hip's kernel: [cout block][16-channel chunk][16-byte unit (csrc/hb.h)][8 channels]
-__device__ __forceinline__ float pack_hb_value(const float* __restrict__ w, const PackJob& jb, size_t i) {
-    const int j = (int)(i & 7);
-    size_t r = i >> 3;
-    const int WU = otp_hb_wb(jb.hbNTW) / 16;
-    const int u = (int)(r % WU); r /= WU;
-    const int chunk = (int)(r % jb.hbChunks), cb = (int)(r / jb.hbChunks);
-    int s, t, lane;
-    otp_hb_unit(u, jb.hbNTW, &s, &t, &lane);
-    const int o = otp_row2ch(cb * jb.hbNTW * 16, t, lane & 15, jb.hbNTW, jb.p.Cout);
-    const int q = 4 * s + (lane >> 4), tap = q >> 1, ci = chunk * 16 + 8 * (q & 1) + j;
-    if (tap > 8 || o >= jb.p.Cout || ci >= jb.p.Cin) return 0.f;
-    return w[jb.base + o * jb.so + ci * jb.si + (tap / 3) * jb.sdy + (tap % 3) * jb.sdx];
-}
-
-__device__ __forceinline__ void pack_range(const float* __restrict__ w, bf16* __restrict__ out, const ConvPlan& p, long so, long si,
-                                           long sdy, long sdx, long base, size_t total, size_t first, size_t step) {
-    for (size_t i = first; i < total; i += step) {
-        size_t r = i;
-        const int j = r % 8; r /= 8;
-        const int co = r % p.BM; r /= p.BM;
-        const int kg = r % (p.KS * 4); r /= (p.KS * 4);
-        const int mt = r % p.nM; r /= p.nM;
-        const int ch = (int)r;
-        float v = 0.f;
-        if (kg < p.KGc) {
-            const int tap = kg / p.CK8, cgi = kg % p.CK8;
-            const int ci = ch * p.CK + cgi * 8 + j, o = mt * p.BM + co;
-            if (ci < p.Cin && o < p.Cout) v = w[base + o * so + ci * si + (tap / p.kw) * sdy + (tap % p.kw) * sdx];
-        }
-        out[i] = (bf16)v;
-    }
-}
-
 // One 16-byte unit (8 consecutive input channels of one (output channel, tap)) of a packed operator: the index arithmetic once per unit,
-// the eight weight loads in flight together, one 16-byte store.  The element-wise forms above cost the batched pack 741 us at the head
-// of every training step (a dependent scalar load per element, six integer divisions each; 160 iterations per thread on the 384 x 384
-// layers).
+// the eight weight loads in flight together, one 16-byte store.  This is the ONLY statement of the three packed layouts (hb = 0:
+// [chunk][m-tile][k-group (KS*4)][BM][8] of nhwc_conv_kernel; 1 / 2: csrc/hb.h); an element-wise form cost the batched pack 741 us
+// at the head of every training step (a dependent scalar load per element, six integer divisions each; 160 iterations per thread
+// on the 384 x 384 layers).
 __device__ __forceinline__ void pack_unit(const PackJob& jb, size_t unit) {
     const float* __restrict__ w = jb.w;
     long off = -1;                       // offset of the unit's first weight; consecutive input channels are jb.si apart
@@ -293,22 +227,17 @@ __device__ __forceinline__ void pack_unit(const PackJob& jb, size_t unit) {
     *reinterpret_cast<bf16x8*>(jb.out + unit * 8) = o8;
 }
 
-__global__ void nhwc_pack_kernel(const float* __restrict__ w, bf16* __restrict__ out, ConvPlan p, long so, long si, long sdy,
-                                 long sdx, long base, size_t total) {
-    pack_range(w, out, p, so, si, sdy, sdx, base, total, blockIdx.x * (size_t)blockDim.x + threadIdx.x,
-               (size_t)gridDim.x * blockDim.x);
-}
-
-__global__ void nhwc_pack_hb_kernel(PackJob jb) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < jb.total; i += (size_t)gridDim.x * blockDim.x)
-        jb.out[i] = (bf16)(jb.hb == 2 ? pack_hbpw_value(jb.w, jb, i) : pack_hb_value(jb.w, jb, i));
+// one weight (otp_nhwc_conv_pack): the job arrives by value, the grid strides over its 16-byte units
+__global__ __launch_bounds__(1024) void nhwc_pack_one_kernel(PackJob jb) {
+    const size_t units = jb.total >> 3;                              // (every layout is whole 16-byte units)
+    for (size_t u = blockIdx.x * (size_t)blockDim.x + threadIdx.x; u < units; u += (size_t)gridDim.x * blockDim.x) pack_unit(jb, u);
 }
 
 // every weight of a training step in one launch: blockIdx.y = job (the table lives in device memory, its fields arrive
-// through the scalar cache), blockIdx.x strides over the job's elements
+// through the scalar cache), blockIdx.x strides over the job's units
 __global__ void nhwc_pack_batch_kernel(const PackJob* __restrict__ jobs) {
     const PackJob& jb = jobs[blockIdx.y];
-    const size_t units = jb.total >> 3;                              // (every layout is whole 16-byte units)
+    const size_t units = jb.total >> 3;
     for (size_t u = blockIdx.x * (size_t)blockDim.x + threadIdx.x; u < units; u += (size_t)gridDim.x * blockDim.x) pack_unit(jb, u);
 }
 
@@ -1599,27 +1528,99 @@ int grid_for(size_t units) {
 // C ABI
 // =====================================================================================================================
 namespace {
-size_t hb_weight_bytes(const otp_nhwc_conv_desc* d) {
-    const int ntw = otp_hb_ntw(d->Cout), nN = ((d->Cout + 15) / 16 + ntw - 1) / ntw;
-    return (size_t)nN * (d->Cin / 16) * otp_hb_wb(ntw);
+// Which kernel runs a descriptor, and the sizes that follow from it.  Every otp_nhwc_conv_* entry point below reads ONE resolve() of
+// its descriptor, so the byte count, the statistics rows, the packer and the launch cannot disagree.
+//
+// hb 3x3: 3x3 / pad 1 / stride 1 or 2 convolutions with Cin % 16 == 0 run on csrc/hb.hip's window kernel (the fp16 engine's conv for
+// bfloat16 NHWC tensors: whole-Cin window by LDS-DMA, weights streamed through registers, three workgroups per CU) where that is
+// faster than nhwc_conv_kernel (otp_hb_pays: 96 / 192-channel branches, the stride-2 fuse convs).
+//
+// hb pointwise: every 1x1 convolution the pointwise kernel of csrc/hb.hip covers - the two projections of a TransformerBlock's MLP on
+// (N, 1, T, C) sequences, HRNet's bottleneck / fuse 1x1s, and their input gradients (the input register-resident, the weights
+// streamed through the LDS): nhwc_conv_kernel re-stages 46 KB of weights per 128-token tile and 136-channel chunk with one workgroup
+// per CU (134 / 214 us per projection at cfg2).  Image-shaped 1x1 layers pay too: forward / input gradient at 80 frames
+// (tools/bf16_conv_bench.py, OTPOSE_NHWC_HB=2 against =0) 256 -> 64 @96x72 80.8 / 94.2 us against 174 / 141, 64 -> 256 106.7 / 81.7
+// against 156 / 176, 96 -> 48 @48x36 12.1 against 30.0, 384 -> 48 @12x9 8.9 against 31.7 - every shape measured.
+//
+// OTPOSE_NHWC_HB=0 keeps every layer on nhwc_conv_kernel, =2 sends every shape the window kernel covers to it, whether it pays or not
+// (A/B, tests); OTPOSE_NHWC_HBPW=0 turns only the pointwise kernel off.  Both are read per call: the tests switch them inside one
+// process.
+enum { ROUTE_NONE = -1, ROUTE_PLAIN = 0, ROUTE_HB = 1, ROUTE_HBPW = 2 };      // (the non-negative values are PackJob::hb)
+struct NhwcRoute {
+    int kind;
+    ConvPlan plan;                     // ROUTE_PLAIN only
+    size_t wbytes;                     // packed bf16 weights
+    int rows;                          // per-tile statistics rows
+};
+
+void resolve(const otp_nhwc_conv_desc* d, NhwcRoute* r) {
+    r->kind = ROUTE_NONE, r->wbytes = 0, r->rows = 0;
+    if (!valid_desc(d)) return;
+    const char* e = getenv("OTPOSE_NHWC_HB");
+    const char* e2 = getenv("OTPOSE_NHWC_HBPW");
+    const int mode = e ? atoi(e) : 1;
+    if (mode != 0 && (mode == 2 || otp_hb_pays(d)) && otp_hb_supported(d)) {
+        const int ntw = otp_hb_ntw(d->Cout), nN = ((d->Cout + 15) / 16 + ntw - 1) / ntw;
+        r->kind = ROUTE_HB, r->wbytes = (size_t)nN * (d->Cin / 16) * otp_hb_wb(ntw), r->rows = otp_hb_stats_rows(d);
+    } else if (mode != 0 && !(e2 && atoi(e2) == 0) && otp_hbpw_supported(d)) {
+        r->kind = ROUTE_HBPW, r->wbytes = (size_t)((d->Cout + 31) / 32) * otp_hbpw_blkb(otp_hbpw_ks(d->Cin));
+        r->rows = otp_hbpw_stats_rows(d);
+    } else if (make_plan(d, &r->plan)) {
+        r->kind = ROUTE_PLAIN, r->wbytes = r->plan.wbytes, r->rows = r->plan.N * r->plan.tilesPerImg;
+    }
 }
-size_t hbpw_weight_bytes(const otp_nhwc_conv_desc* d) { return (size_t)((d->Cout + 31) / 32) * otp_hbpw_blkb(otp_hbpw_ks(d->Cin)); }
+
+bool make_pack_job(const void* weight, void* wpacked, const otp_nhwc_conv_desc* d, int dgrad, PackJob* jb) {
+    NhwcRoute r;
+    resolve(d, &r);
+    if (r.kind == ROUTE_NONE) return false;
+    memset(jb, 0, sizeof(*jb));        // (the caller stores a job as an opaque record: no indeterminate bytes)
+    jb->hb = r.kind;
+    if (r.kind == ROUTE_PLAIN) jb->p = r.plan;
+    jb->p.Cin = d->Cin, jb->p.Cout = d->Cout;
+    jb->hbNTW = otp_hb_ntw(d->Cout), jb->hbChunks = d->Cin / 16, jb->hbKS = otp_hbpw_ks(d->Cin);
+    const long taps = (long)d->kh * d->kw;
+    if (!dgrad) {
+        jb->so = d->Cin * taps, jb->si = taps, jb->sdy = d->kw, jb->sdx = 1, jb->base = 0;
+    } else {      // original weight is (O = d->Cin, I = d->Cout, kh, kw); this conv maps O -> I with flipped taps
+        jb->so = taps, jb->si = (long)d->Cout * taps, jb->sdy = -d->kw, jb->sdx = -1, jb->base = taps - 1;
+    }
+    jb->total = r.wbytes / 2;
+    jb->w = static_cast<const float*>(weight);
+    jb->out = static_cast<bf16*>(wpacked);
+    return true;
+}
+
+int launch_route(const NhwcRoute& r, const void* x, const void* wpacked, const void* bias, const void* res, void* out, void* stats,
+                 const otp_nhwc_conv_desc* d, hipStream_t st) {
+    if (r.kind == ROUTE_NONE) return OTP_ERR_UNSUPPORTED;
+    if (res && (d->out_mode != 0 || stats)) return OTP_ERR_BAD_ARG;   // the sum is an NHWC bf16 tensor; statistics are of conv(x)
+    if (r.kind == ROUTE_HB) return otp_hb_conv(x, wpacked, bias, res, out, stats, d, st);
+    if (r.kind == ROUTE_HBPW) return otp_hbpw_conv(x, wpacked, bias, res, out, stats, d, st);
+    const ConvPlan& p = r.plan;
+#define OTP_NHWC_CASE(mb, nb) \
+    if (p.MB == mb && p.NB == nb) return launch_conv<mb, nb>(p, x, wpacked, bias, res, out, stats, st)
+    OTP_NHWC_CASE(1, 2); OTP_NHWC_CASE(2, 2); OTP_NHWC_CASE(3, 2); OTP_NHWC_CASE(4, 2); OTP_NHWC_CASE(5, 2); OTP_NHWC_CASE(6, 2);
+    OTP_NHWC_CASE(7, 2); OTP_NHWC_CASE(8, 2); OTP_NHWC_CASE(9, 2);
+    OTP_NHWC_CASE(1, 4); OTP_NHWC_CASE(2, 4); OTP_NHWC_CASE(3, 4); OTP_NHWC_CASE(4, 4); OTP_NHWC_CASE(5, 4); OTP_NHWC_CASE(6, 4);
+#undef OTP_NHWC_CASE
+    return OTP_ERR_UNSUPPORTED;
+}
 }  // namespace
 
 extern "C" size_t otp_nhwc_conv_weight_bytes(const otp_nhwc_conv_desc* d) {
-    ConvPlan p;
-    if (use_hb(d)) return hb_weight_bytes(d);
-    if (use_hbpw(d)) return hbpw_weight_bytes(d);
-    return make_plan(d, &p) ? p.wbytes : 0;
+    NhwcRoute r;
+    resolve(d, &r);
+    return r.wbytes;
 }
 
 extern "C" int otp_nhwc_conv_stats_rows(const otp_nhwc_conv_desc* d) {
-    ConvPlan p;
-    if (use_hb(d)) return otp_hb_stats_rows(d);
-    if (use_hbpw(d)) return otp_hbpw_stats_rows(d);
-    return make_plan(d, &p) ? p.N * p.tilesPerImg : 0;
+    NhwcRoute r;
+    resolve(d, &r);
+    return r.rows;
 }
 
+// tool interface of nhwc_conv_kernel: its plan for the descriptor, whichever kernel the route picks
 extern "C" int otp_nhwc_conv_plan(const otp_nhwc_conv_desc* d, int* out8) {
     ConvPlan p;
     if (!out8) return OTP_ERR_BAD_ARG;
@@ -1629,35 +1630,13 @@ extern "C" int otp_nhwc_conv_plan(const otp_nhwc_conv_desc* d, int* out8) {
     return OTP_OK;
 }
 
-namespace {
-bool make_pack_job(const void* weight, void* wpacked, const otp_nhwc_conv_desc* d, int dgrad, PackJob* jb) {
-    if (!make_plan(d, &jb->p)) return false;
-    const ConvPlan& p = jb->p;
-    const long taps = (long)p.kh * p.kw;
-    jb->hb = use_hb(d) ? 1 : (use_hbpw(d) ? 2 : 0);
-    jb->hbNTW = otp_hb_ntw(d->Cout), jb->hbChunks = d->Cin / 16, jb->hbKS = otp_hbpw_ks(d->Cin);
-    if (!dgrad) {
-        jb->so = p.Cin * taps, jb->si = taps, jb->sdy = p.kw, jb->sdx = 1, jb->base = 0;
-    } else {      // original weight is (O = d->Cin, I = d->Cout, kh, kw); this conv maps O -> I with flipped taps
-        jb->so = taps, jb->si = (long)p.Cout * taps, jb->sdy = -p.kw, jb->sdx = -1, jb->base = taps - 1;
-    }
-    jb->total = (jb->hb == 1 ? hb_weight_bytes(d) : (jb->hb == 2 ? hbpw_weight_bytes(d) : p.wbytes)) / 2;
-    jb->w = static_cast<const float*>(weight);
-    jb->out = static_cast<bf16*>(wpacked);
-    return true;
-}
-}  // namespace
-
 extern "C" int otp_nhwc_conv_pack(const void* weight, void* wpacked, const otp_nhwc_conv_desc* d, int dgrad, void* stream) {
     PackJob jb;
     if (!weight || !wpacked) return OTP_ERR_BAD_ARG;
     if (!make_pack_job(weight, wpacked, d, dgrad, &jb)) return OTP_ERR_UNSUPPORTED;
-    if (jb.hb) {
-        nhwc_pack_hb_kernel<<<grid_for(jb.total), 256, 0, static_cast<hipStream_t>(stream)>>>(jb);
-        return otp_launch_status();
-    }
-    nhwc_pack_kernel<<<grid_for(jb.total), 256, 0, static_cast<hipStream_t>(stream)>>>(jb.w, jb.out, jb.p, jb.so, jb.si, jb.sdy,
-                                                                                      jb.sdx, jb.base, jb.total);
+    // one unit per thread in 1024-thread workgroups: a launch of this size is bound by workgroup dispatch (384 x 384 x 9: 10.1 us
+    // from event to event against 12.7 with 256-thread workgroups, profiles/r10_nhwc_route_refactor.txt)
+    nhwc_pack_one_kernel<<<(unsigned)(((jb.total >> 3) + 1023) / 1024), 1024, 0, static_cast<hipStream_t>(stream)>>>(jb);
     return otp_launch_status();
 }
 
@@ -1666,7 +1645,6 @@ extern "C" size_t otp_nhwc_conv_pack_job_bytes(void) { return sizeof(PackJob); }
 extern "C" int otp_nhwc_conv_pack_job(const void* weight, void* wpacked, const otp_nhwc_conv_desc* d, int dgrad, void* job_host) {
     if (!weight || !wpacked || !job_host) return OTP_ERR_BAD_ARG;
     PackJob jb;
-    memset(&jb, 0, sizeof(jb));
     if (!make_pack_job(weight, wpacked, d, dgrad, &jb)) return OTP_ERR_UNSUPPORTED;
     memcpy(job_host, &jb, sizeof(jb));
     return OTP_OK;
@@ -1675,7 +1653,7 @@ extern "C" int otp_nhwc_conv_pack_job(const void* weight, void* wpacked, const o
 extern "C" int otp_nhwc_conv_pack_batch(const void* jobs_device, int n_jobs, void* stream) {
     if (!jobs_device || n_jobs < 0) return OTP_ERR_BAD_ARG;
     if (n_jobs == 0) return OTP_OK;
-    // 32 workgroups per job: the largest weight of the path (384 x 384 x 9 -> 1.5 M packed elements) takes ~180 iterations
+    // 32 workgroups per job: the largest weight of the path (384 x 384 x 9 -> 1.5 M packed elements) takes ~23 units
     // per thread, a 48 x 48 x 9 one finishes in the first
     nhwc_pack_batch_kernel<<<dim3(32, (unsigned)n_jobs), 256, 0, static_cast<hipStream_t>(stream)>>>(
         static_cast<const PackJob*>(jobs_device));
@@ -1684,20 +1662,10 @@ extern "C" int otp_nhwc_conv_pack_batch(const void* jobs_device, int n_jobs, voi
 
 extern "C" int otp_nhwc_conv_bf16_res(const void* x, const void* wpacked, const void* bias, const void* res, void* out,
                                       void* stats, const otp_nhwc_conv_desc* d, void* stream) {
-    ConvPlan p;
     if (!x || !wpacked || !out) return OTP_ERR_BAD_ARG;
-    if (!make_plan(d, &p)) return OTP_ERR_UNSUPPORTED;
-    if (res && (p.out_mode != 0 || stats)) return OTP_ERR_BAD_ARG;   // the sum is an NHWC bf16 tensor; statistics are of conv(x)
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (use_hb(d)) return otp_hb_conv(x, wpacked, bias, res, out, stats, d, st);
-    if (use_hbpw(d)) return otp_hbpw_conv(x, wpacked, bias, res, out, stats, d, st);
-#define OTP_NHWC_CASE(mb, nb) \
-    if (p.MB == mb && p.NB == nb) return launch_conv<mb, nb>(p, x, wpacked, bias, res, out, stats, st)
-    OTP_NHWC_CASE(1, 2); OTP_NHWC_CASE(2, 2); OTP_NHWC_CASE(3, 2); OTP_NHWC_CASE(4, 2); OTP_NHWC_CASE(5, 2); OTP_NHWC_CASE(6, 2);
-    OTP_NHWC_CASE(7, 2); OTP_NHWC_CASE(8, 2); OTP_NHWC_CASE(9, 2);
-    OTP_NHWC_CASE(1, 4); OTP_NHWC_CASE(2, 4); OTP_NHWC_CASE(3, 4); OTP_NHWC_CASE(4, 4); OTP_NHWC_CASE(5, 4); OTP_NHWC_CASE(6, 4);
-#undef OTP_NHWC_CASE
-    return OTP_ERR_UNSUPPORTED;
+    NhwcRoute r;
+    resolve(d, &r);
+    return launch_route(r, x, wpacked, bias, res, out, stats, d, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int otp_nhwc_conv_bf16(const void* x, const void* wpacked, const void* bias, void* out, void* stats,
@@ -1791,9 +1759,11 @@ extern "C" int otp_nhwc_conv_bn_bf16(const void* x, const void* wpacked, const v
                                      const void* gamma, const void* beta, void* running_mean, void* running_var, float eps,
                                      float momentum, void* y, void* relu_mask, int relu, const otp_nhwc_conv_desc* d, void* stream) {
     if (!x || !wpacked || !conv_out || !stats || !vec || !gamma || !beta || !y || !d) return OTP_ERR_BAD_ARG;
-    const int rows = otp_nhwc_conv_stats_rows(d);
+    NhwcRoute r;
+    resolve(d, &r);
+    const int rows = r.rows;
     if (rows <= 0) return OTP_ERR_UNSUPPORTED;
-    int rc = otp_nhwc_conv_bf16_res(x, wpacked, nullptr, nullptr, conv_out, stats, d, stream);
+    int rc = launch_route(r, x, wpacked, nullptr, nullptr, conv_out, stats, d, static_cast<hipStream_t>(stream));
     if (rc != OTP_OK) return rc;
     const int CS = (d->Cout + 7) / 8 * 8;
     const int Ho = (d->H + 2 * d->pad - d->dil * (d->kh - 1) - 1) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->dil * (d->kw - 1) - 1) / d->stride + 1;
@@ -1934,7 +1904,11 @@ extern "C" int otp_gelu_bf16_forward(const void* x, void* y, size_t n, void* str
 // up: pre = bf16(W1 x + b1) AND act = dropout(gelu(pre), p) (+ keep bits) in one launch; the down-projection's input gradient times
 // gelu'(pre) and the dropout factor in one launch.  desc: the (N, 1, T, C) convolution of that launch (for the gradient: the input-gradient
 // convolution, channels swapped).  OTP_ERR_UNSUPPORTED when the shape is not on the pointwise kernel - the caller keeps the separate launches.
-extern "C" int otp_nhwc_mlp_fused_supported(const otp_nhwc_conv_desc* d) { return (d && d->out_mode == 0 && use_hbpw(d)) ? 1 : 0; }
+extern "C" int otp_nhwc_mlp_fused_supported(const otp_nhwc_conv_desc* d) {
+    NhwcRoute r;
+    resolve(d, &r);
+    return (r.kind == ROUTE_HBPW && d->out_mode == 0) ? 1 : 0;
+}
 
 extern "C" int otp_nhwc_mlp_up_bf16(const void* x, const void* wpacked, const void* bias, void* pre, void* act, void* keep_bits, float p,
                                     unsigned long long seed, const otp_nhwc_conv_desc* d, void* stream) {

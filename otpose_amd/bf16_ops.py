@@ -9,14 +9,13 @@ kernels in both directions; PyTorch supplies memory, streams and the tape.  CPU 
 from __future__ import annotations
 
 import ctypes
-import os
 
 import torch
 from torch.autograd import Function
 
 from . import hip
 from .ops import _out_hw, _require_gpu
-from .train_ops import grad_slot
+from .train_ops import TrainRoutes, channel_sum, current_routes, grad_slot
 
 BF16 = torch.bfloat16
 
@@ -244,13 +243,13 @@ def join_wgrad_streams():
         torch.cuda.current_stream(side.device).wait_stream(side)
 
 
-def conv_wgrad(x, gy, weight_shape, stride, pad, dil, out=None):
+def conv_wgrad(x, gy, weight_shape, stride, pad, dil, out=None, routes=None):
     """dL/dW of a convolution (fp32, summed over the batch).  A weight gradient is a LEAF of the backward pass - nothing of
     the pass waits for it - while the input gradient next to it is on the critical chain: when the result goes straight
     into the optimizer's flat gradient buffer (``out`` = :func:`otpose_amd.train_ops.grad_slot`, so autograd launches
     nothing on it) the two kernels of the weight gradient are enqueued on a side stream of the launching stream and overlap
-    with the chain (``OTPOSE_WGRAD_STREAM=0``: same stream).  ``x`` / ``gy`` are registered with the caching allocator for
-    that stream; :func:`join_wgrad_streams` orders the consumers."""
+    with the chain (``TrainRoutes.wgrad_stream`` off: same stream; ``routes`` None: a call by hand, the environment as it is
+    now).  ``x`` / ``gy`` are registered with the caching allocator for that stream; :func:`join_wgrad_streams` orders the consumers."""
     cout, cin, kh, kw = weight_shape
     n, h, w, _ = x.shape
     d = _desc(n, h, w, cin, cout, kh, kw, stride, pad, dil, 0)
@@ -258,7 +257,7 @@ def conv_wgrad(x, gy, weight_shape, stride, pad, dil, out=None):
     nbytes = L.otp_nhwc_wgrad_workspace(ctypes.byref(d))
     if nbytes == 0:
         raise RuntimeError("otp_nhwc_wgrad: unsupported convolution shape")
-    if out is not None and os.environ.get("OTPOSE_WGRAD_STREAM", "1") != "0":
+    if out is not None and (routes or TrainRoutes.from_env()).wgrad_stream:
         cur, side = _wgrad_side_stream(x.device)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
@@ -353,7 +352,7 @@ class ConvBnFunction(Function):
         _require_gpu(x, weight, gamma, beta)
         x = x.contiguous()
         cout = weight.shape[0]
-        ctx.packs = _ACTIVE_PACKS
+        ctx.packs, ctx.routes = _ACTIVE_PACKS, current_routes()
         r = res.contiguous() if res is not None else None
         c, mask, vec, y = conv_bn_forward(x, weight, gamma, beta, r, running_mean, running_var, stride, pad, relu, momentum, eps, ctx.packs)
         ctx.save_for_backward(x, weight, gamma, c, mask, vec)
@@ -370,7 +369,7 @@ class ConvBnFunction(Function):
         gc, gres, dg, db = bn_backward(gy, y, c, vec[0], vec[1], gamma, weight.shape[0], relu, has_res, grad_slot(pg),
                                        grad_slot(pb))
         gx = conv_dgrad(gc, weight, x.shape[1:3], stride, pad, 1, ctx.packs) if ctx.needs_input_grad[0] else None
-        gw = conv_wgrad(x, gc, weight.shape, stride, pad, 1, grad_slot(pw)) if ctx.needs_input_grad[1] else None
+        gw = conv_wgrad(x, gc, weight.shape, stride, pad, 1, grad_slot(pw), ctx.routes) if ctx.needs_input_grad[1] else None
         return gx, gw, dg, db, gres, None, None, None, None, None, None, None
 
 
@@ -390,7 +389,7 @@ class BasicBlockFunction(Function):
     def forward(ctx, x, w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, momentum, eps):
         _require_gpu(x, w1, w2)
         x = x.contiguous()
-        ctx.packs = _ACTIVE_PACKS
+        ctx.packs, ctx.routes = _ACTIVE_PACKS, current_routes()
         c1, m1, vec1, y1 = conv_bn_forward(x, w1, g1, b1, None, rm1, rv1, 1, 1, True, momentum, eps, ctx.packs)
         c2, m2, vec2, y2 = conv_bn_forward(y1, w2, g2, b2, x, rm2, rv2, 1, 1, True, momentum, eps, ctx.packs)
         ctx.save_for_backward(x, w1, g1, c1, m1, vec1, y1, w2, g2, c2, m2, vec2)
@@ -405,13 +404,13 @@ class BasicBlockFunction(Function):
         gc2, gres, dg2, db2 = bn_backward(gy, m2, c2, vec2[0], vec2[1], g2, w2.shape[0], True, True, grad_slot(pg2),
                                           grad_slot(pb2))
         gy1 = conv_dgrad(gc2, w2, y1.shape[1:3], 1, 1, 1, ctx.packs)
-        gw2 = conv_wgrad(y1, gc2, w2.shape, 1, 1, 1, grad_slot(pw2))
+        gw2 = conv_wgrad(y1, gc2, w2.shape, 1, 1, 1, grad_slot(pw2), ctx.routes)
         del gc2
         gc1, _, dg1, db1 = bn_backward(gy1, m1, c1, vec1[0], vec1[1], g1, w1.shape[0], True, False, grad_slot(pg1),
                                        grad_slot(pb1))
         del gy1
         gx = conv_dgrad(gc1, w1, x.shape[1:3], 1, 1, 1, ctx.packs, res=gres)
-        gw1 = conv_wgrad(x, gc1, w1.shape, 1, 1, 1, grad_slot(pw1))
+        gw1 = conv_wgrad(x, gc1, w1.shape, 1, 1, 1, grad_slot(pw1), ctx.routes)
         return gx, gw1, dg1, db1, None, None, gw2, dg2, db2, None, None, None, None
 
 
@@ -427,7 +426,7 @@ class ConvOutFunction(Function):
     def forward(ctx, x, weight, bias, stride, pad, dil):
         _require_gpu(x, weight)
         x = x.contiguous()
-        ctx.packs = _ACTIVE_PACKS
+        ctx.packs, ctx.routes = _ACTIVE_PACKS, current_routes()
         out, _, _ = conv_forward(x, weight, bias, stride, pad, dil, out_mode=1, packs=ctx.packs)
         ctx.save_for_backward(x, weight)
         ctx.cfg = (stride, pad, dil, bias is not None)
@@ -436,13 +435,12 @@ class ConvOutFunction(Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from .train_ops import channel_sum
         x, weight = ctx.saved_tensors
         stride, pad, dil, has_bias = ctx.cfg
         gy = gy.contiguous()
         g = to_nhwc(gy)
         gx = conv_dgrad(g, weight, x.shape[1:3], stride, pad, dil, ctx.packs) if ctx.needs_input_grad[0] else None
-        gw = conv_wgrad(x, g, weight.shape, stride, pad, dil, grad_slot(ctx.params[0])) if ctx.needs_input_grad[1] else None
+        gw = conv_wgrad(x, g, weight.shape, stride, pad, dil, grad_slot(ctx.params[0]), ctx.routes) if ctx.needs_input_grad[1] else None
         gb = channel_sum(gy, grad_slot(ctx.params[1])) if has_bias and ctx.needs_input_grad[2] else None
         return gx, gw, gb, None, None, None
 
@@ -505,7 +503,7 @@ class ConvBiasFunction(Function):
     def forward(ctx, x, weight, bias, stride, pad, dil):
         _require_gpu(x, weight)
         x = x.contiguous()
-        ctx.packs = _ACTIVE_PACKS
+        ctx.packs, ctx.routes = _ACTIVE_PACKS, current_routes()
         out, _, _ = conv_forward(x, weight, bias, stride, pad, dil, out_mode=0, want_stats=False, packs=ctx.packs)
         ctx.save_for_backward(x, weight)
         ctx.cfg = (stride, pad, dil, bias is not None)
@@ -518,7 +516,7 @@ class ConvBiasFunction(Function):
         stride, pad, dil, has_bias = ctx.cfg
         gy = gy.contiguous()
         gx = conv_dgrad(gy, weight, x.shape[1:3], stride, pad, dil, ctx.packs) if ctx.needs_input_grad[0] else None
-        gw = conv_wgrad(x, gy, weight.shape, stride, pad, dil, grad_slot(ctx.params[0])) if ctx.needs_input_grad[1] else None
+        gw = conv_wgrad(x, gy, weight.shape, stride, pad, dil, grad_slot(ctx.params[0]), ctx.routes) if ctx.needs_input_grad[1] else None
         gb = (channel_sum_nhwc(gy, weight.shape[0], grad_slot(ctx.params[1]))
               if has_bias and ctx.needs_input_grad[2] else None)
         return gx, gw, gb, None, None, None
@@ -608,7 +606,7 @@ class MlpInteriorFunction(Function):
         hid, cin = w1.shape[:2]
         cout = w2.shape[0]
         L = hip.lib()
-        ctx.packs = _ACTIVE_PACKS
+        ctx.packs, ctx.routes = _ACTIVE_PACKS, current_routes()
         d1 = _desc(n, h, w, cin, hid, 1, 1, 1, 0, 1, 0)
         wp1 = _pack(w1.contiguous(), d1, 0, ctx.packs)
         pre = _new((n, h, w, cs(hid)), BF16, x)
@@ -624,7 +622,6 @@ class MlpInteriorFunction(Function):
 
     @staticmethod
     def backward(ctx, go):
-        from .train_ops import channel_sum
         x, pre, act, keep, w1, w2 = ctx.saved_tensors
         pw1, pb1, pw2, pb2 = ctx.params
         n, h, w, _ = x.shape
@@ -639,10 +636,10 @@ class MlpInteriorFunction(Function):
         dpre = torch.empty_like(pre)
         hip.check(L.otp_nhwc_mlp_down_dgrad_bf16(hip.ptr(g), hip.ptr(wpd), hip.ptr(pre), hip.ptr(keep), hip.ptr(dpre), ctx.p,
                                                  ctypes.byref(dd), hip.stream_of(g)), "otp_nhwc_mlp_down_dgrad_bf16")
-        gw2 = conv_wgrad(act, g, w2.shape, 1, 0, 1, grad_slot(pw2)) if ctx.needs_input_grad[3] else None
+        gw2 = conv_wgrad(act, g, w2.shape, 1, 0, 1, grad_slot(pw2), ctx.routes) if ctx.needs_input_grad[3] else None
         gb2 = channel_sum(go, grad_slot(pb2)) if pb2 is not None and ctx.needs_input_grad[4] else None
         gx = conv_dgrad(dpre, w1, (h, w), 1, 0, 1, ctx.packs) if ctx.needs_input_grad[0] else None
-        gw1 = conv_wgrad(x, dpre, w1.shape, 1, 0, 1, grad_slot(pw1)) if ctx.needs_input_grad[1] else None
+        gw1 = conv_wgrad(x, dpre, w1.shape, 1, 0, 1, grad_slot(pw1), ctx.routes) if ctx.needs_input_grad[1] else None
         gb1 = channel_sum_nhwc(dpre, hid, grad_slot(pb1)) if pb1 is not None and ctx.needs_input_grad[2] else None
         return gx, gw1, gb1, gw2, gb2, None, None
 

@@ -234,14 +234,7 @@ class InferenceEngine:
         self._keep.append(t)
         return t
 
-    @staticmethod
-    def winograd_pays(cin, cout):
-        """Shapes on which the Winograd kernel measured faster than the direct one (tools/conv_bench.py --wino): whole
-        8-channel chunks and output-channel counts that fill its 48-row tiles (64 -> 64 would compute 96 rows)."""
-        cout16 = (cout + 15) // 16 * 16
-        if cin == 64 and cout16 == 64:
-            return True                                   # layer1 Bottleneck conv2: 0.463 -> 0.408 ms despite the ragged 2nd tile
-        return cin >= 32 and cin % 8 == 0 and cout16 >= 48 and ((cout16 + 47) // 48) * 48 <= 1.15 * cout16
+    winograd_pays = staticmethod(ops.winograd_pays)            # (kept under this name for its callers)
 
     # ---- op emitters ----------------------------------------------------------------------------
     def _emit(self, fn):
@@ -330,29 +323,22 @@ class InferenceEngine:
         d = ops.conv_desc(inp, out, cout, kh, kw, stride, pad, dil, act, in2, res, res_up, frame_split, cin)
         self._keep.append(d)
         L = self.lib
+        route = self._conv_route(d, inp, cin_w, res, in2)
         if r.conv_log:                                              # development aid: one line per emitted convolution
-            route = ("x3" if r.use_x3 and in2 is None and (kh, kw) in ((3, 3), (1, 1)) and ops.x3_supported(d) else
-                     "wino" if r.use_winograd and in2 is None and self.winograd_pays(cin_w, cout) and ops.wino_supported(d)
-                     else "direct")
             print(f"conv {d.N}x{d.Cin}->{cout} k{kh} s{stride} p{pad} d{dil} {d.H}x{d.W} in2={in2 is not None} "
                   f"res={res is not None} up={res_up} fs={frame_split} {route}", file=sys.stderr)
-        if r.use_small_conv and in2 is not None and res is None and (kh, kw) == (3, 3) and ops.small_conv_supported(d):
+        if route == "small":
             # RSB staircase convs (a few channels, pre-added second input): one thread per pixel, exact fp32 (csrc/conv_small.hip)
             wc = ops.pack_small_conv_weight(w)
             self._keep.append(wc)
             self.call(L.otp_conv3x3_small, "otp_conv3x3_small", *ops.conv3x3_small_args(inp, in2, wc, sc, sh, out, d))
-            return out
-        if (r.use_pointx and not self._exact and in2 is None and (kh, kw) == (1, 1) and stride == 1 and pad == 0 and res_up <= 1
-                and not frame_split and act in (ACT_NONE, ACT_RELU) and inp.C == cin_w
-                and (cin_w in (64, 128, 256) or (r.pointx_fuse and cin_w % 16 == 0) or r.pointx_any)
-                and ops.pointwise_x3_supported(cin_w, cout, inp.t.shape[2] * inp.t.shape[3])):
+        elif route == "pointx":
             # HRNet layer1's and the fuse layers' 1x1 convs (<= 256 channels in and out): register-resident pixels, streamed weights
             # (csrc/pointx.hip) - bound by their HBM streams, which the implicit-GEMM kernel ran at a third of the rate
             pk = ops.pack_pointwise_x3(w, sc, sh)
             self._keep.append(pk)
             self.call(L.otp_pointwise_x3, "otp_pointwise_x3", *ops.pointwise_x3_args(inp, pk, out, res, act == ACT_RELU))
-            return out
-        if r.use_x3 and not self._exact and in2 is None and (kh, kw) in ((3, 3), (1, 1)) and ops.x3_supported(d):
+        elif route == "x3":
             # 3x3 / stride 1 with Cin % 16 == 0: split-half (f16x3) products on the 16-bit matrix cores, fp32 storage and
             # accumulation (csrc/convx.hip); the per-channel scale is folded into the packed weights
             e = ops.x3_weight_exponent(w, sc)         # weights stored times 2^e, the sum multiplied by 2^-e (otp_conv_desc.out_scale)
@@ -360,17 +346,33 @@ class InferenceEngine:
             xp = ops.pack_x3_weight(w, sc, stride, e)
             self._keep.append(xp)
             self.call(L.otp_conv2d_x3, "otp_conv2d_x3", *ops.conv2d_x3_args(inp, xp, sh, out, d, res))
-            return out
-        if r.use_winograd and in2 is None and self.winograd_pays(cin_w, cout) and ops.wino_supported(d):
+        elif route == "wino":
             # 3x3 / stride 1 / pad 1 with enough channels: Winograd F(2x2,3x3) kernel (csrc/wino.hip), same epilogue
             up = ops.pack_wino_weight(w)
             self._keep.append(up)
             self.call(L.otp_conv2d_wino, "otp_conv2d_wino", *ops.conv2d_wino_args(inp, up, sc, sh, out, d, res))
-            return out
-        wp = ops.pack_conv_weight(w)
-        self._keep.append(wp)
-        self.call(L.otp_conv2d, "otp_conv2d", *ops.conv2d_args(inp, wp, sc, sh, out, d, in2, res))
+        else:
+            wp = ops.pack_conv_weight(w)
+            self._keep.append(wp)
+            self.call(L.otp_conv2d, "otp_conv2d", *ops.conv2d_args(inp, wp, sc, sh, out, d, in2, res))
         return out
+
+    def _conv_route(self, d, inp: View, cin_w, res: View, in2: View):
+        """Which kernel runs the convolution ``d``: "small" | "pointx" | "x3" | "wino" | "direct", first match wins."""
+        r = self.routes
+        k, cout = (d.kh, d.kw), d.Cout
+        if r.use_small_conv and in2 is not None and res is None and k == (3, 3) and ops.small_conv_supported(d):
+            return "small"
+        if (r.use_pointx and not self._exact and in2 is None and k == (1, 1) and d.stride == 1 and d.pad == 0 and d.res_up <= 1
+                and not d.frame_split and d.act in (ACT_NONE, ACT_RELU) and inp.C == cin_w
+                and (cin_w in (64, 128, 256) or (r.pointx_fuse and cin_w % 16 == 0) or r.pointx_any)
+                and ops.pointwise_x3_supported(cin_w, cout, inp.t.shape[2] * inp.t.shape[3])):
+            return "pointx"
+        if r.use_x3 and not self._exact and in2 is None and k in ((3, 3), (1, 1)) and ops.x3_supported(d):
+            return "x3"
+        if in2 is None and ops.runs_winograd(r.use_winograd, cin_w, cout, d):
+            return "wino"
+        return "direct"
 
     def conv_bn(self, inp: View, conv_mod, bn_mod, act=ACT_NONE, res=None, out=None, res_up=1, **kw):
         n, _, h, w = inp.t.shape

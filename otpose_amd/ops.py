@@ -1061,6 +1061,22 @@ def wino_supported(desc) -> bool:
     return bool(hip.lib().otp_conv2d_wino_supported(desc))
 
 
+def winograd_pays(cin, cout):
+    """Shapes on which the Winograd kernel measured faster than the direct one (tools/conv_bench.py --wino): whole
+    8-channel chunks and output-channel counts that fill its 48-row tiles (64 -> 64 would compute 96 rows)."""
+    cout16 = (cout + 15) // 16 * 16
+    if cin == 64 and cout16 == 64:
+        return True                                   # layer1 Bottleneck conv2: 0.463 -> 0.408 ms despite the ragged 2nd tile
+    return cin >= 32 and cin % 8 == 0 and cout16 >= 48 and ((cout16 + 47) // 48) * 48 <= 1.15 * cout16
+
+
+def runs_winograd(enabled, cin, cout, desc) -> bool:
+    """The one rule for "this convolution runs on the Winograd kernel" (inference engine and training operators alike): the
+    OTPOSE_WINOGRAD switch is on (``enabled``), 3x3 / stride 1 / pad 1 / dilation 1, the shape pays and the kernel takes it."""
+    return bool(enabled and (desc.kh, desc.kw, desc.stride, desc.pad, desc.dil) == (3, 3, 1, 1, 1)
+                and winograd_pays(cin, cout) and wino_supported(desc))
+
+
 def conv2d_wino_args(inp: View, upacked, scale, shift, out: View, desc, res: View = None):
     return (_vp(inp), hip.ptr(upacked), hip.ptr(scale), hip.ptr(shift), _vp(res), _vp(out), desc)
 

@@ -14,7 +14,6 @@ pooling, up-sampling, DCN and loss kernel is in libotpose_hip.so.
 from __future__ import annotations
 
 import math
-import os
 
 import torch
 import torch.utils.checkpoint
@@ -183,6 +182,7 @@ class TrainGraph:
                 if v is not None:
                     self.Bf[pre + k] = v
         self.cfg = model.cfg
+        self.routes = T.TrainRoutes.from_env()    # the OTPOSE_* switches of this forward and of its backward nodes, read once
         self.taps = None                      # dict -> forward() records named intermediates (tools/grad_noise.py)
         self.stochastic = bool(getattr(model, "train_dropout", True))
         self._nbt = []
@@ -242,7 +242,7 @@ class TrainGraph:
         """The launching stream plus n - 1 side streams (one per HRNet branch).  ``OTPOSE_TRAIN_STREAMS=0`` keeps the whole
         step on one stream."""
         main = torch.cuda.current_stream(like.device)
-        if os.environ.get("OTPOSE_TRAIN_STREAMS", "1") == "0" or n < 2:
+        if not self.routes.train_streams or n < 2:
             return [main] * n
         return [main] + hip.side_streams(like.device, n - 1)
 
@@ -356,7 +356,7 @@ class TrainGraph:
         c = x.shape[1]
         hs = c // n_head
         names = ("query", "key", "value")
-        if torch.is_grad_enabled() and os.environ.get("OTPOSE_TRAIN_RECOMPUTE", "1") != "0":
+        if torch.is_grad_enabled() and self.routes.recompute:
             branches = [(self.P[f"{p}.{n}_conv.weight"], self.P[f"{p}.{n}_norm.weight"], self.P[f"{p}.{n}_norm.bias"],
                          self._w4(f"{p}.{n}.weight"), self.P.get(f"{p}.{n}.bias")) for n in names]
             q, k, v = T.attn_front(x, stride, 1e-5, (self.P[ln1 + ".weight"], self.P[ln1 + ".bias"]), branches)
@@ -452,6 +452,10 @@ class TrainGraph:
 
     # ---- whole forward (model/OTPose.py:307-394) ---------------------------------------------------------------
     def forward(self, x, margin):
+        with T.active_routes(self.routes):             # what the Functions built by the walk read and keep for their backward
+            return self.walk(x, margin)
+
+    def walk(self, x, margin):
         m = self.cfg["MODEL"]
         J = m["NUM_JOINTS"]
         pe_w, pe_h = m["HEATMAP_SIZE"]
@@ -558,7 +562,7 @@ class TrainGraphBF16(TrainGraph):
     def forward(self, x, margin):
         """One launch refreshes every packed bf16 operator from the fp32 master weights (:class:`bf16_ops.PackCache`, kept on
         the model; ``OTPOSE_PACK_BATCH=0`` packs at every use instead), then the walk of :meth:`TrainGraph.forward`."""
-        if os.environ.get("OTPOSE_PACK_BATCH", "1") == "0":
+        if not self.routes.pack_batch:
             return super().forward(x, margin)
         cache = self.model.__dict__.get("_otp_pack_cache")
         if cache is None:
@@ -591,7 +595,7 @@ class TrainGraphBF16(TrainGraph):
         return y
 
     def basic_block(self, p, x):
-        if (x.dtype != B16.BF16 or self.has(p + ".downsample.0.weight") or os.environ.get("OTPOSE_BLOCK_FUSE", "1") == "0"
+        if (x.dtype != B16.BF16 or self.has(p + ".downsample.0.weight") or not self.routes.block_fuse
                 or (self.taps is not None and self.taps.get("layers") is not None)):     # layer taps: two conv + BN nodes
             return super().basic_block(p, x)
         self.count_batch(p + ".bn1")
@@ -613,7 +617,7 @@ class TrainGraphBF16(TrainGraph):
     def offset_mask_input(self, trans):
         """The 32-channel feature map feeds ten dilated 3x3 convs (32 -> 306 / 153): one conversion to NHWC bf16, every
         conv on the bf16 matrix cores, offsets / masks handed to the DCN as fp32 NCHW."""
-        if os.environ.get("OTPOSE_BF16_OFFSETS", "1") == "0":
+        if not self.routes.bf16_offsets:
             return trans
         return B16.to_nhwc_grad(trans)
 
@@ -626,12 +630,12 @@ class TrainGraphBF16(TrainGraph):
         """The MLP interior in bf16: the (B, C, T) fp32 LayerNorm output enters as a (B, 1, T, CS) NHWC bf16 view, the 4C-wide
         hidden activation (the largest tensor of a block: 240 MB at cfg2 in fp32) exists only in bf16, both projections
         and their gradients run on the bf16 matrix cores, and the down-projection hands back fp32 (B, C, T)."""
-        if yn.shape[1] % 8 or yn.shape[2] % 32 or os.environ.get("OTPOSE_BF16_MLP", "1") == "0":
+        if yn.shape[1] % 8 or yn.shape[2] % 32 or not self.routes.bf16_mlp:
             return super().mlp(p, yn, pdrop)                  # the C = 17 flow encoder / odd lengths stay on the fp32 path
         x = B16.to_nhwc_grad(yn.unsqueeze(2))
         w1, w2 = self._w4(p + ".0.weight"), self._w4(p + ".3.weight")
         rate = pdrop if self.stochastic else 0.0
-        if os.environ.get("OTPOSE_MLP_FUSED_TRAIN", "0") == "1" and B16.mlp_interior_supported(x, w1, w2):
+        if self.routes.mlp_fused_train and B16.mlp_interior_supported(x, w1, w2):
             # GELU / dropout and their derivatives inside the projections' launches (bf16_ops.MlpInteriorFunction): built, tested and
             # measured NEUTRAL (123.4 against 122.7 ms per step on one box) - the epilogues' ~20 vector instructions per hidden element
             # cost the pointwise kernel what the two element-wise passes cost the HBM - so the three-node chain stays the default

@@ -8,14 +8,16 @@ PyTorch supplies memory, streams and the autograd tape only; CPU tensors raise l
 """
 from __future__ import annotations
 
+import contextlib
+import dataclasses
 import os
 
 import torch
 from torch.autograd import Function
 
-from . import hip
+from . import hip, ops
 from .ops import (ACT_NONE, View, _check_f32, _out_hw, _require_gpu, conv2d_launch, conv2d_wino_launch, conv_desc,
-                  pack_conv_weight, pack_wino_weight, wino_supported)
+                  pack_conv_weight, pack_wino_weight)
 
 
 def grad_slot(param):
@@ -42,49 +44,87 @@ def grad_slot(param):
     return slot.view(slot.shape)
 
 
-def conv2d_forward(x, weight, bias, stride, pad, dil):
+@dataclasses.dataclass(frozen=True)
+class TrainRoutes:
+    """The ``OTPOSE_*`` switches of the training step, read once per forward (:meth:`from_env`, ``train.TrainGraph``); the field
+    defaults are the switches'.  A Function keeps them on ``ctx``: its backward follows the routes its forward was built with."""
+    train_streams: bool = True        # OTPOSE_TRAIN_STREAMS: HRNet branches, def_fuse and encoder 1 on side streams
+    recompute: bool = True            # OTPOSE_TRAIN_RECOMPUTE: the attention front as one node that rebuilds its intermediates
+    pack_batch: bool = True           # OTPOSE_PACK_BATCH: one launch re-packs every bf16 conv operator (bf16_ops.PackCache)
+    block_fuse: bool = True           # OTPOSE_BLOCK_FUSE: a bf16 BasicBlock as one autograd node
+    bf16_offsets: bool = True         # OTPOSE_BF16_OFFSETS: the offset / mask convs in front of the DCNs on the bf16 path
+    bf16_mlp: bool = True             # OTPOSE_BF16_MLP: the transformer MLP interior on the bf16 path
+    mlp_fused_train: bool = False     # OTPOSE_MLP_FUSED_TRAIN=1 (opt-in): GELU / dropout inside the projections' launches
+    use_dense_cc: bool = True         # OTPOSE_DENSE_CC: pointwise C -> C layers via csrc/dense.hip, forward and input gradient
+    use_x3: bool = True               # OTPOSE_CONV_MATH != "f32": those layers on split products (csrc/densex.hip)
+    use_winograd: bool = True         # OTPOSE_WINOGRAD: 3x3 stride-1 convs via csrc/wino.hip, forward and input gradient
+    wgrad_stream: bool = True         # OTPOSE_WGRAD_STREAM: bf16 weight gradients on a side stream of the launching stream
+
+    @classmethod
+    def from_env(cls) -> "TrainRoutes":
+        env = os.environ.get
+        on = lambda name: env("OTPOSE_" + name, "1") != "0"                         # noqa: E731
+        return cls(train_streams=on("TRAIN_STREAMS"), recompute=on("TRAIN_RECOMPUTE"), pack_batch=on("PACK_BATCH"),
+                   block_fuse=on("BLOCK_FUSE"), bf16_offsets=on("BF16_OFFSETS"), bf16_mlp=on("BF16_MLP"),
+                   mlp_fused_train=env("OTPOSE_MLP_FUSED_TRAIN", "0") == "1", use_dense_cc=on("DENSE_CC"),
+                   use_x3=env("OTPOSE_CONV_MATH", "x3") != "f32", use_winograd=on("WINOGRAD"), wgrad_stream=on("WGRAD_STREAM"))
+
+
+_ACTIVE_ROUTES = []           # the routes of the training forward(s) being built (train.TrainGraph.forward), innermost last
+
+
+@contextlib.contextmanager
+def active_routes(routes):
+    _ACTIVE_ROUTES.append(routes)
+    try:
+        yield
+    finally:
+        _ACTIVE_ROUTES.pop()
+
+
+def current_routes():
+    """For ``Function.forward`` only: the active routes, else (a direct call from a test or tool) the environment as it is now.  A
+    backward passes what its ``ctx`` holds; the helpers below take routes as an argument (None: called by hand, as above)."""
+    return _ACTIVE_ROUTES[-1] if _ACTIVE_ROUTES else TrainRoutes.from_env()
+
+
+def conv_route(routes, cin, cout, d, hw):
+    """The kernel of the fp32 convolution ``d``, forward or (``cin`` / ``cout`` exchanged) input gradient: "dense" - pointwise C -> C
+    layers of the temporal encoders (query / key / value / proj) on csrc/dense.hip; "wino" - ops.runs_winograd; else "direct"."""
+    if routes.use_dense_cc and d.kh == 1 and d.stride == 1 and d.pad == 0 and cin == cout and ops.dense_cc_supported(cin, hw):
+        return "dense"
+    return "wino" if ops.runs_winograd(routes.use_winograd, cin, cout, d) else "direct"
+
+
+def conv2d_forward(x, weight, bias, stride, pad, dil, routes=None):
+    routes = routes or TrainRoutes.from_env()
     cout, cin, kh, kw = weight.shape
     ho, wo = _out_hw(x.shape[2], x.shape[3], kh, kw, stride, pad, dil)
     out = torch.empty((x.shape[0], cout, ho, wo), dtype=torch.float32, device=x.device)
     iv, ov = View(x), View(out)
     d = conv_desc(iv, ov, cout, kh, kw, stride, pad, dil, ACT_NONE)
-    if _dense_cc(cin, cout, kh, stride, pad, x.shape[2] * x.shape[3]):
-        _dense_cc_launch(x, weight.reshape(cout, cin), bias, out)
-    elif _winograd(cin, cout, d):
+    route = conv_route(routes, cin, cout, d, x.shape[2] * x.shape[3])
+    if route == "dense":
+        _dense_cc_launch(routes, x, weight.reshape(cout, cin), bias, out)
+    elif route == "wino":
         conv2d_wino_launch(iv, pack_wino_weight(weight), None, bias, ov, d)
     else:
         conv2d_launch(iv, pack_conv_weight(weight), None, bias, ov, d)
     return out
 
 
-def _dense_cc(cin, cout, k, stride, pad, hw):
-    """Pointwise C -> C layers of the temporal encoders (query / key / value / proj): the register-resident-input kernel of
-    csrc/dense.hip, forward and input gradient alike (same rule as the inference engine)."""
-    from . import ops
-    return (os.environ.get("OTPOSE_DENSE_CC", "1") != "0" and k == 1 and stride == 1 and pad == 0 and cin == cout
-            and ops.dense_cc_supported(cin, hw))
-
-
-def _dense_cc_launch(x4, w2, bias, out4, grad=False):
-    from . import ops
+def _dense_cc_launch(routes, x4, w2, bias, out4, grad=False):
     n, c = x4.shape[:2]
     # split products (csrc/densex.hip) unless the exact-fp32 kernels are asked for, as in the inference engine; ``grad``: x4 is a
     # gradient - bfloat16 pieces (csrc/densex_grad.hip), an IEEE-half piece would flush the small ones to zero
-    x3 = os.environ.get("OTPOSE_CONV_MATH", "x3") != "f32" and ops.dense_x3_supported(c, x4.shape[2] * x4.shape[3])
+    x3 = routes.use_x3 and ops.dense_x3_supported(c, x4.shape[2] * x4.shape[3])
     pk = ops.pack_dense_cc(w2, None, bias, x3=x3, grad=grad)
     ops.dense_cc([x4.view(n, c, -1)], [pk], None, [out4.view(n, c, -1)], x3=x3, grad=grad)
 
 
-def _winograd(cin, cout, d):
-    """3x3 / stride 1 / pad 1 layers with enough channels run on the Winograd kernel, forward and input gradient alike
-    (same rule as the inference engine)."""
-    from .engine import InferenceEngine
-    return (os.environ.get("OTPOSE_WINOGRAD", "1") != "0" and d.kh == 3 and d.stride == 1 and d.pad == 1 and d.dil == 1
-            and InferenceEngine.winograd_pays(cin, cout) and wino_supported(d))
-
-
-def conv2d_grad_input(grad_out, weight, in_shape, stride, pad, dil):
+def conv2d_grad_input(grad_out, weight, in_shape, stride, pad, dil, routes=None):
     """dL/dx: a stride-1 convolution of (zero-inserted) grad_out with the flipped, channel-transposed weights."""
+    routes = routes or TrainRoutes.from_env()
     cout, cin, kh, kw = weight.shape
     n, _, h, w = in_shape
     L = hip.lib()
@@ -97,21 +137,21 @@ def conv2d_grad_input(grad_out, weight, in_shape, stride, pad, dil):
                                hip.stream_of(g)), "otp_dilate")
         g = gd
     gx = torch.empty(in_shape, dtype=torch.float32, device=g.device)
-    if _dense_cc(cin, cout, kh, stride, pad, h * w):
-        _dense_cc_launch(g, weight.reshape(cout, cin).t(), None, gx, grad=True)         # dx = W^T . dy
-        return gx
     iv, ov = View(g), View(gx)
     d = conv_desc(iv, ov, cin, kh, kw, 1, dil * (kh - 1) - pad, dil, ACT_NONE)
-    if stride == 1 and _winograd(cout, cin, d):
+    route = conv_route(routes, cout, cin, d, h * w) if stride == 1 else "direct"
+    if route == "dense":
+        _dense_cc_launch(routes, g, weight.reshape(cout, cin).t(), None, gx, grad=True)         # dx = W^T . dy
+    elif route == "wino":
         # the transposed convolution as a Winograd conv: weights flipped and channel-transposed, then G g G^T
         wt = weight.flip(2, 3).transpose(0, 1).contiguous()
         conv2d_wino_launch(iv, pack_wino_weight(wt), None, None, ov, d)
-        return gx
-    cin16 = (cin + 15) // 16 * 16
-    wp = torch.empty(kh * kw * cout * cin16, dtype=torch.float32, device=g.device)
-    hip.check(L.otp_conv2d_pack_weight_dgrad(hip.ptr(weight.contiguous()), hip.ptr(wp), cout, cin, kh, kw,
-                                             hip.stream_of(g)), "otp_conv2d_pack_weight_dgrad")
-    conv2d_launch(iv, wp, None, None, ov, d)
+    else:
+        cin16 = (cin + 15) // 16 * 16
+        wp = torch.empty(kh * kw * cout * cin16, dtype=torch.float32, device=g.device)
+        hip.check(L.otp_conv2d_pack_weight_dgrad(hip.ptr(weight.contiguous()), hip.ptr(wp), cout, cin, kh, kw,
+                                                 hip.stream_of(g)), "otp_conv2d_pack_weight_dgrad")
+        conv2d_launch(iv, wp, None, None, ov, d)
     return gx
 
 
@@ -167,7 +207,8 @@ class Conv2dFunction(Function):
         ctx.save_for_backward(x, weight)
         ctx.cfg = (stride, pad, dil, bias is not None)
         ctx.params = (weight, bias)                    # gradient slots are looked up at backward time
-        return conv2d_forward(x, weight, bias, stride, pad, dil)
+        ctx.routes = current_routes()                  # ... and the input gradient follows the forward's routes
+        return conv2d_forward(x, weight, bias, stride, pad, dil, ctx.routes)
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -175,7 +216,8 @@ class Conv2dFunction(Function):
         stride, pad, dil, has_bias = ctx.cfg
         pw, pb = ctx.params
         grad_out = grad_out.contiguous()
-        gx = conv2d_grad_input(grad_out, weight, x.shape, stride, pad, dil) if ctx.needs_input_grad[0] else None
+        gx = (conv2d_grad_input(grad_out, weight, x.shape, stride, pad, dil, ctx.routes)
+              if ctx.needs_input_grad[0] else None)
         gw = (conv2d_grad_weight(x, grad_out, weight.shape, stride, pad, dil, grad_slot(pw))
               if ctx.needs_input_grad[1] else None)
         gb = channel_sum(grad_out, grad_slot(pb)) if has_bias and ctx.needs_input_grad[2] else None
@@ -359,12 +401,13 @@ class AttnFrontFunction(Function):
         x = x.contiguous()
         ctx.cfg = (stride, eps)
         ctx.params = (g1, b1) + tuple(bp)
+        ctx.routes = current_routes()
         xn = _ln_fwd(x, g1.reshape(-1).contiguous(), b1.reshape(-1).contiguous(), eps)
         outs = []
         for i in range(3):
             dw, lg, lb, w4, bias = bp[5 * i: 5 * i + 5]
             z = _ln_fwd(_dw_fwd(xn, dw.contiguous(), stride), lg.reshape(-1).contiguous(), lb.reshape(-1).contiguous(), eps)
-            outs.append(conv2d_forward(z.unsqueeze(2), w4.contiguous(), bias, 1, 0, 1).squeeze(2))
+            outs.append(conv2d_forward(z.unsqueeze(2), w4.contiguous(), bias, 1, 0, 1, ctx.routes).squeeze(2))
         ctx.save_for_backward(x)
         return tuple(outs)
 
@@ -385,7 +428,7 @@ class AttnFrontFunction(Function):
             lgf = lg.reshape(-1).contiguous()
             y = _dw_fwd(xn, dw.contiguous(), stride)
             z4 = _ln_fwd(y, lgf, lb.reshape(-1).contiguous(), eps).unsqueeze(2)
-            gz = conv2d_grad_input(g4, w4.contiguous(), z4.shape, 1, 0, 1).squeeze(2)
+            gz = conv2d_grad_input(g4, w4.contiguous(), z4.shape, 1, 0, 1, ctx.routes).squeeze(2)
             gw = conv2d_grad_weight(z4, g4, w4.shape, 1, 0, 1, grad_slot(w4))
             gb = channel_sum(g4, grad_slot(bias)) if bias is not None else None
             del z4

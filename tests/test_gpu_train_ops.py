@@ -59,6 +59,40 @@ def test_conv2d_backward_matches_autograd(case):
     _close(bs.grad, b.grad, 1e-4)
 
 
+def test_conv2d_backward_follows_the_routes_of_its_forward(monkeypatch):
+    """A node's backward uses the routes its forward was built with: a switch flipped between ``forward`` and ``backward()``
+    changes nothing, the same switch set throughout does."""
+    from otpose_amd import ops
+    from otpose_amd import train_ops as T
+    monkeypatch.delenv("OTPOSE_WINOGRAD", raising=False)
+    x = seeded((1, 48, 8, 8), 1).requires_grad_()
+    wt = seeded((48, 48, 3, 3), 2, 1.0 / math.sqrt(48 * 9)).requires_grad_()
+    go = seeded((1, 48, 8, 8), 4)
+    F.conv2d(x, wt, None, 1, 1, 1).backward(go)
+    xd, gd = x.detach().cuda(), go.cuda()
+    v = ops.View(xd)
+    assert ops.runs_winograd(True, 48, 48, ops.conv_desc(v, v, 48, 3, 3, 1, 1, 1))      # forward and input gradient: same descriptor
+
+    def winograd(on):
+        if on:
+            monkeypatch.delenv("OTPOSE_WINOGRAD", raising=False)              # the default environment
+        else:
+            monkeypatch.setenv("OTPOSE_WINOGRAD", "0")
+
+    def gx(in_forward, in_backward):
+        xs, ws = xd.clone().requires_grad_(), wt.detach().cuda().requires_grad_()
+        winograd(in_forward)
+        out = T.conv2d(xs, ws, None, 1, 1, 1)
+        winograd(in_backward)
+        out.backward(gd)
+        return xs.grad.cpu()
+
+    a, b, c = gx(True, True), gx(True, False), gx(False, False)
+    assert torch.equal(b, a)
+    assert not torch.equal(c, a)          # else the shape would not tell the two kernels apart
+    _close(c, x.grad)
+
+
 @pytest.mark.parametrize("relu,with_res", [(True, True), (True, False), (False, False)])
 def test_batch_norm_train_matches_autograd(relu, with_res):
     from otpose_amd import train_ops as T

@@ -987,6 +987,55 @@ int otp_box_nms_merge(const void* pred, int B, int N, int C, float conf_thres, f
                       int max_out, void* workspace, size_t workspace_bytes, void* counts, void* dets, void* person_counts,
                       void* person_boxes, void* person_scores, void* stream);
 
+/* ---- Temporal segment NMS: the reference's thirdparty/utils/csrc/nms_cpu.cpp and the Python layer of thirdparty/utils/nms.py
+ * (csrc/segnms.hip).  A segmented batch: G groups, one per (video, class) pair, given by offsets (G+1)
+ * int32 (ascending, offsets[0] >= 0, offsets[G] <= N) over flat segs (N, 2) float32 rows (x1, x2) and scores (N) float32.  One
+ * workgroup per group, every group in one launch.  A group whose offsets do not lie in [0, N] is answered with count 0 and
+ * nothing of it is read.  All float32 arithmetic is uncontracted: every product, quotient and sum is rounded on its own.  A
+ * group of up to OTP_SEG_NMS_LDS_CAP segments works in LDS, a larger one in the workspace (otp_seg_nms_workspace(G, N) bytes of
+ * device memory for either kernel, contents irrelevant); there is no limit on a group's size.  No allocation, no
+ * synchronisation: graph-capturable.  Indices written are relative to the group's first row.
+ *
+ * otp_seg_nms: hard NMS (nms_cpu.cpp:19-58) behind NMSop's pre-filter (nms.py:14-21).
+ *   candidates     every segment when min_score <= 0, else those with score > min_score.
+ *   area           (x2 - x1) + 1e-6f.
+ *   order          descending score, equal scores by ascending index (the reference's sort leaves ties open); a NaN score last.
+ *   loop           the first live candidate i is kept and suppresses every later live candidate j with ovr >= iou_threshold,
+ *                  inter = max(0, min(x2_i, x2_j) - max(x1_i, x1_j)), ovr = inter / (area_i + area_j - inter).
+ *   outputs        counts (G) int32; keep (N) int32: rows offsets[g] .. offsets[g] + counts[g] - 1 hold the kept segments'
+ *                  indices in the order above, cut at max_num when max_num > 0; the group's remaining rows hold -1.
+ *
+ * otp_seg_softnms: soft NMS (nms_cpu.cpp:67-160).  method 0 hard, 1 linear, 2 gaussian; sigma is read by method 2 only.
+ *   round          the live segment with the highest score is taken (of exactly equal scores the lowest index: the reference
+ *                  takes the first in its own array, which its swaps have permuted; a NaN orders as -inf); its (x1, x2,
+ *                  score now) and index are emitted; every other live score is multiplied by its weight against the taken
+ *                  segment - method 0: 0 where ovr >= iou_threshold; 1: (1 - ovr) where ovr >= iou_threshold; 2:
+ *                  expf(-(ovr * ovr) / sigma); otherwise 1 - and its segment leaves when the product is < min_score.  ovr as
+ *                  above.  Like the reference, the first segment taken is never tested against min_score, and with
+ *                  min_score <= 0 a score of 0 stays live.
+ *   outputs        counts (G) int32 = the rounds run, at most max_num when max_num > 0; dets (N, 3) float32 and inds (N) int32:
+ *                  rows offsets[g] + r of round r; the group's remaining rows hold zeros and -1.
+ *
+ * otp_seg_voting: seg_voting (nms.py:67-101) for K kept segments nms_segs (K, 2) float32 grouped by nms_offsets (G+1) int32,
+ * each against ALL segments of its group: iou = inter / (len_a + len_b - inter) with len = x2 - x1 and no 1e-6,
+ * w_j = (iou >= voting_thresh ? 1 : 0) * score_j (the raw score: the reference computes an offset score and never uses it),
+ * out (K, 2) row = sum_j (w_j / sum_j w_j) (x1_j, x2_j).  A row without a neighbour is 0 / 0 = NaN, as in the reference.  The
+ * sums run in a fixed order (lane l of a wave over j = l, l + 64, ..., then a butterfly over the 64 lanes), not the order of
+ * the reference's matrix product.
+ *
+ * -1 for null pointers, G, N or K <= 0, a NaN threshold, a method outside 0..2, a sigma of method 2 that is not finite and
+ * positive; OTP_ERR_UNSUPPORTED for N or K >= 2^28; OTP_ERR_WORKSPACE for a short workspace. */
+#define OTP_SEG_NMS_LDS_CAP 1024
+#define OTP_SEG_NMS_WS_WORDS 6
+size_t otp_seg_nms_workspace(int G, int N);
+int otp_seg_nms(const void* segs, const void* scores, const void* offsets, int G, int N, float iou_threshold, float min_score,
+                int max_num, void* workspace, size_t workspace_bytes, void* counts, void* keep, void* stream);
+int otp_seg_softnms(const void* segs, const void* scores, const void* offsets, int G, int N, float iou_threshold, float sigma,
+                    float min_score, int method, int max_num, void* workspace, size_t workspace_bytes, void* counts,
+                    void* dets, void* inds, void* stream);
+int otp_seg_voting(const void* nms_segs, const void* nms_offsets, const void* segs, const void* scores, const void* offsets,
+                   int G, int K, int N, float voting_thresh, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

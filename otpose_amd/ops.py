@@ -2052,3 +2052,80 @@ def box_nms_merge(pred, conf_thres=0.4, nms_thres=0.4, frame_hw=None, img_size=4
              *frame_rescale(frame_hw, img_size), n, hip.ptr(workspace), workspace.numel() * workspace.element_size(),
              hip.ptr(counts), hip.ptr(dets), hip.ptr(pcounts), hip.ptr(pboxes), hip.ptr(pscores)), pred)
     return counts, dets, pcounts, pboxes, pscores
+
+
+# ------------------------------------------------------------------------------------------------
+# temporal segment NMS (csrc/segnms.hip; the reference's thirdparty/utils nms_1d_cpu); the drop-in names are in segnms.py
+# ------------------------------------------------------------------------------------------------
+def _seg_batch(segs, scores, offsets):
+    """Checked contiguous ``(segs (N, 2) f32, scores (N) f32, offsets (G+1) i32)`` of a segmented batch, N >= 1 and G >= 1."""
+    _require_gpu(segs, scores, offsets)
+    _check_f32(segs, scores)
+    if segs.dim() != 2 or segs.shape[1] != 2 or scores.dim() != 1 or scores.shape[0] != segs.shape[0] or segs.shape[0] < 1:
+        raise ValueError(f"segs must be (N, 2) and scores (N) with N >= 1, got {tuple(segs.shape)} and {tuple(scores.shape)}")
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.shape[0] < 2:
+        raise ValueError("offsets must be a (G + 1) int32 tensor with G >= 1")
+    return segs.contiguous(), scores.contiguous(), offsets.contiguous()
+
+
+def _seg_workspace(g, n, device, workspace):
+    need = hip.lib().otp_seg_nms_workspace(g, n)
+    if workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.int32, device=device)
+    return workspace, workspace.numel() * workspace.element_size()
+
+
+def seg_nms(segs, scores, offsets, iou_threshold, min_score=0.0, max_num=0, workspace=None):
+    """Hard 1-D NMS (``nms_1d_cpu``, nms_cpu.cpp:19-58, behind ``NMSop``'s ``scores > min_score`` filter) of every group of a
+    segmented batch in one launch: group g is rows ``offsets[g] .. offsets[g + 1]`` of ``segs`` (N, 2) / ``scores`` (N).
+    Returns device tensors ``(counts (G,) int32, keep (N,) int32)``: rows ``offsets[g] ..`` of ``keep`` hold the group's kept
+    indices (relative to its first row) in descending-score order, cut at ``max_num`` when it is > 0, then -1."""
+    segs, scores, offsets = _seg_batch(segs, scores, offsets)
+    g, n, dev = offsets.shape[0] - 1, segs.shape[0], segs.device
+    workspace, nbytes = _seg_workspace(g, n, dev, workspace)
+    counts = torch.empty(g, dtype=torch.int32, device=dev)
+    keep = torch.empty(n, dtype=torch.int32, device=dev)
+    _launch(hip.lib().otp_seg_nms, "otp_seg_nms",
+            (hip.ptr(segs), hip.ptr(scores), hip.ptr(offsets), g, n, float(iou_threshold), float(min_score), int(max_num),
+             hip.ptr(workspace), nbytes, hip.ptr(counts), hip.ptr(keep)), segs)
+    return counts, keep
+
+
+def seg_softnms(segs, scores, offsets, iou_threshold, sigma=0.5, min_score=0.0, method=2, max_num=0, workspace=None):
+    """Soft 1-D NMS (``softnms_1d_cpu``, nms_cpu.cpp:67-160; ``method`` 0 hard, 1 linear, 2 gaussian) of every group of a
+    segmented batch in one launch.  Returns device tensors ``(counts (G,) int32, dets (N, 3) float32, inds (N,) int32)``: rows
+    ``offsets[g] + r`` hold the ``(x1, x2, decayed score)`` and the group-relative index of the segment taken in round r,
+    cut at ``max_num`` when it is > 0; the group's remaining rows hold zeros and -1."""
+    segs, scores, offsets = _seg_batch(segs, scores, offsets)
+    if int(method) not in (0, 1, 2):
+        raise ValueError(f"method must be 0 (hard), 1 (linear) or 2 (gaussian), got {method}")
+    g, n, dev = offsets.shape[0] - 1, segs.shape[0], segs.device
+    workspace, nbytes = _seg_workspace(g, n, dev, workspace)
+    counts = torch.empty(g, dtype=torch.int32, device=dev)
+    dets = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    inds = torch.empty(n, dtype=torch.int32, device=dev)
+    _launch(hip.lib().otp_seg_softnms, "otp_seg_softnms",
+            (hip.ptr(segs), hip.ptr(scores), hip.ptr(offsets), g, n, float(iou_threshold), float(sigma), float(min_score),
+             int(method), int(max_num), hip.ptr(workspace), nbytes, hip.ptr(counts), hip.ptr(dets), hip.ptr(inds)), segs)
+    return counts, dets, inds
+
+
+def seg_voting_groups(nms_segs, nms_offsets, segs, scores, offsets, voting_thresh):
+    """``seg_voting`` (nms.py:67-101) for the kept segments ``nms_segs`` (K, 2) of every group (``nms_offsets`` (G+1) int32)
+    against all segments of the same group of the batch ``segs`` / ``scores`` / ``offsets``: (K, 2) score-weighted means of
+    the segments with ``iou >= voting_thresh``; a row without such a segment is NaN, as in the reference."""
+    segs, scores, offsets = _seg_batch(segs, scores, offsets)
+    _require_gpu(nms_segs, nms_offsets)
+    _check_f32(nms_segs)
+    if nms_segs.dim() != 2 or nms_segs.shape[1] != 2:
+        raise ValueError(f"nms_segs must be (K, 2), got {tuple(nms_segs.shape)}")
+    if nms_offsets.dtype != torch.int32 or nms_offsets.shape != offsets.shape:
+        raise ValueError("nms_offsets must be a (G + 1) int32 tensor like offsets")
+    nms_segs, nms_offsets = nms_segs.contiguous(), nms_offsets.contiguous()
+    k = nms_segs.shape[0]
+    out = torch.empty((k, 2), dtype=torch.float32, device=segs.device)
+    if k:
+        _launch(hip.lib().otp_seg_voting, "otp_seg_voting",
+                (hip.ptr(nms_segs), hip.ptr(nms_offsets), hip.ptr(segs), hip.ptr(scores), hip.ptr(offsets),
+                 offsets.shape[0] - 1, k, segs.shape[0], float(voting_thresh), hip.ptr(out)), segs)
+    return out

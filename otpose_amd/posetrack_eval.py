@@ -5,7 +5,7 @@ checkpoint by (script/Common.py:442 -> dataset/PoseTrackDataset.py:453-608 ``eva
 tensors ``OTPose.predict`` returns and evaluates them with two kernels (``ops.pose_assign``, ``ops.ap_curve``; csrc/poseval.hip).
 With a ``PoseNMS`` the evaluator first rescores the persons and suppresses duplicate poses per frame by OKS, hard or soft
 (``ops.pose_nms``; csrc/posenms.hip) - the post-processing of predictions made on detector boxes.
-Out of scope: MOTA / tracking, the JSON directory layout of poseval, YOLO boxes, 1-D NMS, image dumps.
+Out of scope: MOTA / tracking, the JSON directory layout of poseval, YOLO boxes, image dumps.
 """
 from __future__ import annotations
 

@@ -41,6 +41,15 @@ __global__ __launch_bounds__(256) void ln_channel_bwd_kernel(const float* __rest
     }
 }
 
+// dy * gamma rounded on its own before the mean of these products is taken off it.  Contracted into fma(dy, gamma, -m1) the
+// difference keeps the product's rounding error, which 1 / sqrt(var + eps) then scales up: with one channel (m1 IS the rounded
+// product, var = 0, rstd = 316) dx must be 0 and came out as 4e-5 |dy| (tests/test_gpu_encoder_bwd.py, C = 1).
+template <typename V>
+__device__ __forceinline__ V ln_mul_rn(V dy, float gamma) {
+#pragma clang fp contract(off)
+    return dy * gamma;
+}
+
 // The same for C <= 4 * CW with every value read once: a workgroup owns 64 tokens, wave w keeps channels [w * cw, (w+1) * cw)
 // of x and dy in registers (cw = ceil(C / 4)), the three per-token reductions (mean, variance, the two dy moments) cross the
 // waves through LDS.  One HBM read of x and dy, one write of dx and dy * xhat (the one-thread-per-token form above re-reads
@@ -125,7 +134,7 @@ __global__ __launch_bounds__(256) void ln_channel_bwd_split_kernel(const float* 
     for (int i = 0; i < CW; ++i) {
         const int c = cbeg + i;
         if (i < cw && c < C) {
-            dx[base + (size_t)c * T] = r * (dv[i] * gamma[c] - m1 - xv[i] * m2);
+            dx[base + (size_t)c * T] = r * (ln_mul_rn(dv[i], gamma[c]) - m1 - xv[i] * m2);
             if (!SUMS) dyxh[base + (size_t)c * T] = dv[i] * xv[i];
         }
     }
@@ -226,7 +235,7 @@ __global__ __launch_bounds__(512) void ln_channel_bwd_wide_kernel(const float* _
 #pragma unroll
     for (int i = 0; i < CW; ++i) {
         const int c = cbeg + i;
-        if (i < cw && c < C) o4[base + (size_t)c * T4] = r * (dv[i] * gamma[c] - m1 - xv[i] * m2);
+        if (i < cw && c < C) o4[base + (size_t)c * T4] = r * (ln_mul_rn(dv[i], gamma[c]) - m1 - xv[i] * m2);
     }
 }
 
@@ -306,11 +315,11 @@ __global__ __launch_bounds__(256) void dwconv3_bwd_x_s1_kernel(const float* __re
 constexpr int DWW_THREADS = 1024;
 __global__ __launch_bounds__(DWW_THREADS) void dwconv3_bwd_w_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                      float* __restrict__ dw, int B, int C, int T, int To,
-                                                                     int stride) {
+                                                                     int stride, int vec) {
     __shared__ float red[3][DWW_THREADS / 64];
     const int c = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    if (stride == 1 && (T & 3) == 0) {
+    if (vec) {                       // the host's rule (otp_dwconv3_backward): stride 1, T % 4 == 0, 16-byte aligned x and dy
         // rows of T = To floats, 16-byte aligned: a thread takes four consecutive time steps per pass (one float4 of dy, one of x
         // and the two neighbours), two passes in flight - the one-element loop below ran at 1.3 TB/s (91 us at 16 x 136 x 6912)
         const int q4 = T >> 2, groups = B * q4;
@@ -501,7 +510,11 @@ extern "C" int otp_dwconv3_backward(const void* x, const void* w, const void* gr
     if (!x || !w || !grad_y || !grad_x || !grad_w || B <= 0 || C <= 0 || T <= 0 || stride <= 0) return OTP_ERR_BAD_ARG;
     const int To = (T + 2 - 3) / stride + 1;
     auto st = static_cast<hipStream_t>(stream);
-    if (stride == 1 && (T & 3) == 0 && ((reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(grad_x)) & 15) == 0) {
+    // one vector rule for both kernels: rows of T % 4 == 0 floats and every tensor they read or write as float4 16-byte aligned (a
+    // contiguous view at an odd storage offset is not); dW reads x and grad_y, dX reads grad_y and writes grad_x
+    const bool vec = stride == 1 && (T & 3) == 0 &&
+                     ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(grad_x)) & 15) == 0;
+    if (vec) {
         const size_t groups = (size_t)B * C * (T >> 2);
         const size_t blocks = (groups + 255) / 256;
         hipLaunchKernelGGL(dwconv3_bwd_x_s1_kernel, dim3((unsigned)(blocks > 16384 ? 16384 : blocks)), dim3(256), 0, st,
@@ -512,7 +525,7 @@ extern "C" int otp_dwconv3_backward(const void* x, const void* w, const void* gr
                            stride);
     }
     hipLaunchKernelGGL(dwconv3_bwd_w_kernel, dim3(C), dim3(DWW_THREADS), 0, st, static_cast<const float*>(x),
-                       static_cast<const float*>(grad_y), static_cast<float*>(grad_w), B, C, T, To, stride);
+                       static_cast<const float*>(grad_y), static_cast<float*>(grad_w), B, C, T, To, stride, (int)vec);
     return otp_launch_status();
 }
 

@@ -36,8 +36,8 @@ static inline int otp_launch_status() {
 
 static inline int otp_ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-// the vector types of every kernel file (16-bit element vectors: otp_x3x2 / otp_x3x8 below; csrc/h16.hip and csrc/nhwc.hip keep
-// their own element type, switched by OTP_H16_BF16)
+// the vector types of every kernel file (16-bit element vectors: otp_x3x2 / otp_x3x8 below; csrc/h16_kernels.h takes its element
+// type from a traits parameter, csrc/nhwc.hip is bfloat16 only)
 typedef float otp_f32x4 __attribute__((ext_vector_type(4)));
 typedef float otp_f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int otp_u32x4 __attribute__((ext_vector_type(4)));

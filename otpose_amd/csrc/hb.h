@@ -1,5 +1,5 @@
-// csrc/hb.hip (= csrc/h16.hip compiled for bfloat16, NHWC addressing): the training step's 3x3 convolutions on the window /
-// weight-stream kernel of the fp16 engine.  Internal interface between csrc/nhwc.hip (which owns the C ABI: otp_nhwc_conv_*)
+// csrc/hb.hip (csrc/h16_kernels.h instantiated for bfloat16, NHWC addressing): the training step's 3x3 convolutions on the window /
+// weight-stream kernel of the fp16 engine, its 1x1 convolutions on that engine's pointwise kernel.  Internal interface between csrc/nhwc.hip (which owns the C ABI: otp_nhwc_conv_*)
 // and that translation unit, plus the layout of the packed weights both sides must agree on.
 #pragma once
 #include "x3.h"
@@ -24,7 +24,7 @@ __host__ __device__ inline void otp_hb_unit(int u, int ntw, int* s, int* t, int*
     }
 }
 
-// ---- 1x1 convolutions (csrc/h16.hip: h16_pointwise_kernel) -------------------------------------------------------------------------
+// ---- 1x1 convolutions (csrc/h16_kernels.h: h16_pointwise_kernel) -------------------------------------------------------------------------
 // KS k-steps of 32 input channels (Cin padded with zero weights and masked loads); the packed operator is ceil(Cout / 32) blocks of
 // [tile of the pair (2)][k-step][lane] 16-byte A fragments - row r16 of tile m of block p = output channel 32 p + 8 (r16 >> 2) + 4 m +
 // (r16 & 3), lane = (r16 = lane & 15, kq = lane >> 4): input channels 32 ks + 8 kq .. + 7 - each block padded to whole 4 KB

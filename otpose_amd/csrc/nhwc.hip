@@ -1531,8 +1531,8 @@ namespace {
 // Which kernel runs a descriptor, and the sizes that follow from it.  Every otp_nhwc_conv_* entry point below reads ONE resolve() of
 // its descriptor, so the byte count, the statistics rows, the packer and the launch cannot disagree.
 //
-// hb 3x3: 3x3 / pad 1 / stride 1 or 2 convolutions with Cin % 16 == 0 run on csrc/hb.hip's window kernel (the fp16 engine's conv for
-// bfloat16 NHWC tensors: whole-Cin window by LDS-DMA, weights streamed through registers, three workgroups per CU) where that is
+// hb 3x3: 3x3 / pad 1 / stride 1 or 2 convolutions with Cin % 16 == 0 run on csrc/hb.hip's window kernel (csrc/h16_kernels.h, the fp16 engine's conv,
+// instantiated for bfloat16 NHWC tensors: whole-Cin window by LDS-DMA, weights streamed through registers, three workgroups per CU) where that is
 // faster than nhwc_conv_kernel (otp_hb_pays: 96 / 192-channel branches, the stride-2 fuse convs).
 //
 // hb pointwise: every 1x1 convolution the pointwise kernel of csrc/hb.hip covers - the two projections of a TransformerBlock's MLP on

@@ -49,6 +49,9 @@ CONV_CASES = [
     (256, 64, 1, 1, 0, 1, 1, 96, 72),
     (32, 153, 3, 1, 15, 15, 1, 96, 72),      # widely dilated offset conv on the full map: tap-mode wgrad, 8-channel chunks
     (64, 64, 3, 2, 1, 1, 1, 192, 144),       # second stem conv: strided wide map
+    (136, 64, 1, 1, 0, 1, 1, 16, 12),        # pointwise kernel with statistics at 5, 12 and 17 k-steps
+    (264, 64, 1, 1, 0, 1, 1, 16, 12),
+    (520, 64, 1, 1, 0, 1, 1, 16, 12),
 ]
 
 
@@ -92,7 +95,12 @@ def test_conv_forward_stats_dgrad_wgrad(case):
 
 
 @pytest.mark.parametrize("case", [(48, 48, 1, 5, 96, 72), (96, 96, 1, 3, 48, 36), (192, 192, 1, 3, 24, 18), (384, 384, 1, 5, 12, 9),
-                                  (64, 64, 2, 2, 192, 144), (48, 96, 2, 3, 96, 72), (96, 40, 1, 2, 20, 14), (32, 56, 2, 3, 16, 12)])
+                                  (64, 64, 2, 2, 192, 144), (48, 96, 2, 3, 96, 72), (96, 40, 1, 2, 20, 14), (32, 56, 2, 3, 16, 12),
+                                  # the (NTW, NPT, stride) instances of the statistics form the cases above do not reach (256- / 128-pixel
+                                  # tiles need launches of >= 768 workgroups: tests/test_gpu_h16.py CONV_SHAPES)
+                                  (16, 32, 1, 1, 8, 16), (16, 1024, 1, 1, 152, 40), (16, 1024, 1, 1, 32, 96), (16, 1024, 2, 1, 136, 88),
+                                  (16, 24608, 2, 1, 16, 32), (16, 1536, 1, 1, 152, 40), (16, 1536, 1, 1, 32, 96), (16, 1536, 2, 1, 136, 88),
+                                  (16, 36864, 2, 1, 16, 32)])
 def test_window_kernel_matches_the_chunked_kernel(case, monkeypatch):
     """3x3 / pad 1 convolutions with Cin % 16 == 0 run on csrc/hb.hip (the fp16 engine's window + weight-stream kernel compiled for
     bfloat16 NHWC tensors); OTPOSE_NHWC_HB=0 keeps nhwc_conv_kernel.  Same operands, same products, fp32 sums in another order:
@@ -131,7 +139,7 @@ def test_window_kernel_matches_the_chunked_kernel(case, monkeypatch):
 
 
 @pytest.mark.parametrize("case", [(136, 544, 2, 6912), (544, 136, 2, 6912), (136, 136, 3, 200), (40, 24, 1, 77), (204, 816, 1, 1000),
-                                  (816, 204, 1, 1000)])
+                                  (816, 204, 1, 1000), (104, 264, 1, 77)])      # (the last: 4 k-steps forward, 12 in the input gradient)
 def test_sequence_pointwise_convs_forward_and_input_gradient(case, monkeypatch):
     """The two projections of a TransformerBlock MLP (model/blocks.py:248-254) on the (B, 1, T, C) view of a sequence: csrc/hb.hip's
     pointwise kernel (register-resident input, streamed weights) behind otp_nhwc_conv_* - bf16 NHWC and fp32 NCHW results, bias,
@@ -292,7 +300,9 @@ def test_mlp_interior_matches_fp32_reference():
     close(b2d.grad, b2r.grad, 1e-4)
 
 
-@pytest.mark.parametrize("case", [(3, 48, 48, 24, 18), (2, 96, 96, 12, 9), (2, 20, 44, 10, 7)])
+@pytest.mark.parametrize("case", [(3, 48, 48, 24, 18), (2, 96, 96, 12, 9), (2, 20, 44, 10, 7),
+                                  # the window kernel's plain / residual forms at NTW 2 and at 128- / 256-pixel tiles (>= 768 workgroups)
+                                  (1, 32, 16, 8, 16), (7, 160, 16, 88, 32), (7, 160, 16, 88, 64), (4, 192, 16, 64, 96), (8, 192, 16, 64, 96)])
 def test_conv_dgrad_with_skip_gradient_is_the_separate_add(case):
     """otp_nhwc_conv_bf16_res: the input-gradient conv with the skip connection's gradient added in its epilogue equals
     the plain launch followed by a bf16 tensor add, bit for bit (the conv result is rounded to bf16 before the add in both)."""
@@ -344,7 +354,8 @@ def test_gelu_dropout_is_gelu_then_dropout_with_repeatable_draws():
     assert torch.equal(B.gelu_dropout(x, 0.0), B.gelu(x))
 
 
-@pytest.mark.parametrize("case", [(136, 544, 2, 6912, 0.1), (136, 544, 3, 200, 0.0), (40, 160, 1, 77, 0.25)])
+@pytest.mark.parametrize("case", [(136, 544, 2, 6912, 0.1), (136, 544, 3, 200, 0.0), (40, 160, 1, 77, 0.25),
+                                  (104, 416, 1, 77, 0.1), (168, 336, 1, 77, 0.1)])      # (the MLP epilogues at 4 and 8 k-steps)
 def test_mlp_interior_node_matches_the_three_node_chain(case):
     """MlpInteriorFunction (GELU / dropout and their derivatives inside the projections' launches, otp_nhwc_mlp_*) against
     conv_bias -> gelu_dropout -> conv_out with the SAME dropout seed: the same keep decisions, results and gradients within the bf16

@@ -56,6 +56,26 @@ CONV_SHAPES = [
     (2, 96, 192, 48, 36, 2, False, ACT_NONE),
     (2, 64, 64, 96, 144, 2, False, ACT_RELU),      # wide rows (the stem's conv2 at reduced height)
     (5, 256, 48, 24, 18, 1, False, ACT_RELU),      # transition1
+    # one case per dispatch instance (NTW x NPT x stride x residual) the cases above do not reach.  The plan takes 256- / 128-pixel tiles
+    # (NPT 4 / 2) only for launches of >= 768 workgroups: 32 cout blocks x >= 24 tiles - or, at stride 2, where a 256-pixel tile's
+    # window never fits 1024 records unless the whole map is smaller than the tile, 768 cout blocks x 1 tile
+    (1, 16, 16, 4, 16, 2, True, ACT_RELU),         # NTW 2, NPT 1, stride 2, residual
+    (1, 16, 1024, 152, 40, 1, False, ACT_RELU),    # NTW 2, NPT 4
+    (1, 16, 1024, 152, 40, 1, True, ACT_RELU),
+    (1, 16, 1024, 32, 96, 1, False, ACT_NONE),     # NTW 2, NPT 2
+    (1, 16, 1024, 32, 96, 1, True, ACT_RELU),
+    (1, 16, 1024, 136, 88, 2, False, ACT_RELU),    # NTW 2, NPT 2, stride 2
+    (1, 16, 1024, 136, 88, 2, True, ACT_RELU),
+    (1, 16, 24608, 16, 32, 2, False, ACT_RELU),    # NTW 2, NPT 4, stride 2
+    (1, 16, 24608, 16, 32, 2, True, ACT_RELU),
+    (1, 16, 1536, 152, 40, 1, False, ACT_RELU),    # NTW 3, NPT 4
+    (1, 16, 1536, 152, 40, 1, True, ACT_RELU),
+    (1, 16, 1536, 32, 96, 1, False, ACT_NONE),     # NTW 3, NPT 2
+    (1, 16, 1536, 32, 96, 1, True, ACT_RELU),
+    (1, 16, 1536, 136, 88, 2, False, ACT_RELU),    # NTW 3, NPT 2, stride 2
+    (1, 16, 1536, 136, 88, 2, True, ACT_RELU),
+    (1, 16, 36864, 16, 32, 2, False, ACT_RELU),    # NTW 3, NPT 4, stride 2
+    (1, 16, 36864, 16, 32, 2, True, ACT_RELU),
 ]
 
 

@@ -134,21 +134,40 @@ __device__ __forceinline__ float bload(otp_rsrc r, int voff_bytes, int soff_byte
 // 16x16x32 MFMA (csrc/convx.hip).  Rounds 2-3 used bfloat16 pieces: 8 significand bits each, a = hi + lo to 2^-17.  Round 4
 // switched to IEEE half: 11 bits each, a = hi + lo to max(2^-22 |a|, 2^-25) - the f16 MFMA of gfx950 has the same rate as the
 // bf16 one and takes SUBNORMAL f16 inputs exactly (tools/micro/mfma_f16_denorm.hip), which the small `lo` pieces need.  Range:
-// operands above 65504 become infinities (BatchNorm-folded weights and heat-map activations are orders of magnitude below);
-// -DOTP_X3_BF16 restores the bfloat16 pieces.
-#ifdef OTP_X3_BF16
-typedef __bf16 otp_x3_t;
-#define OTP_X3_MFMA __builtin_amdgcn_mfma_f32_16x16x32_bf16
-#else
-typedef _Float16 otp_x3_t;
-#define OTP_X3_MFMA __builtin_amdgcn_mfma_f32_16x16x32_f16
-#endif
-typedef otp_x3_t otp_x3x2 __attribute__((ext_vector_type(2)));
-typedef otp_x3_t otp_x3x8 __attribute__((ext_vector_type(8)));
-// the two pieces of a packed pair back as fp32
-__device__ __forceinline__ otp_f32x2 otp_x3_widen(uint32_t pair) {
-    return __builtin_convertvector(__builtin_bit_cast(otp_x3x2, pair), otp_f32x2);
-}
+// operands above 65504 become infinities (BatchNorm-folded weights and heat-map activations are orders of magnitude below).
+// The piece type is a traits parameter of the kernels that exist for both (csrc/densex.hip, the attention products of
+// csrc/transformer.hip: bfloat16 pieces for the GRADIENT operands of the training backward); every other file uses the half
+// aliases below.
+struct otp_half_pieces {
+    typedef _Float16 elem;
+    typedef _Float16 x2 __attribute__((ext_vector_type(2)));
+    typedef _Float16 x8 __attribute__((ext_vector_type(8)));
+    static constexpr float range_limit = 65504.f;
+    static __device__ __forceinline__ otp_f32x4 mfma(x8 a, x8 b, otp_f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    }
+    // the two pieces of a packed pair back as fp32
+    static __device__ __forceinline__ otp_f32x2 widen(uint32_t pair) {
+        return __builtin_convertvector(__builtin_bit_cast(x2, pair), otp_f32x2);
+    }
+};
+struct otp_bf16_pieces {
+    typedef __bf16 elem;
+    typedef __bf16 x2 __attribute__((ext_vector_type(2)));
+    typedef __bf16 x8 __attribute__((ext_vector_type(8)));
+    static constexpr float range_limit = 3.0e38f;                  // fp32's own range
+    static __device__ __forceinline__ otp_f32x4 mfma(x8 a, x8 b, otp_f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ otp_f32x2 widen(uint32_t pair) {
+        return __builtin_convertvector(__builtin_bit_cast(x2, pair), otp_f32x2);
+    }
+};
+typedef otp_half_pieces::elem otp_x3_t;
+typedef otp_half_pieces::x2 otp_x3x2;
+typedef otp_half_pieces::x8 otp_x3x8;
+#define OTP_X3_MFMA __builtin_amdgcn_mfma_f32_16x16x32_f16       /* what otp_half_pieces::mfma wraps, with its three modifiers */
+__device__ __forceinline__ otp_f32x2 otp_x3_widen(uint32_t pair) { return otp_half_pieces::widen(pair); }
 
 // ---- range guard of the 16-bit-operand kernels (csrc/range.hip) ----------------------------------------------------------------
 // A half piece overflows at 65504: hi = rne(a) = inf, lo = rne(a - hi) = -inf, every product with it NaN - and a ReLU (v_max_f32
@@ -157,21 +176,20 @@ __device__ __forceinline__ otp_f32x2 otp_x3_widen(uint32_t pair) {
 // the next consumer could not split - and stores a code word through `otp_range_word()` (one word of pinned host memory, visible
 // to every device of the process; written only on a violation, so the guard costs a compare per result and no memory traffic).
 // include/otpose_hip.h: otp_range_flag_read / otp_range_poison.
-#ifdef OTP_X3_BF16
-#define OTP_RANGE_LIMIT 3.0e38f                                    /* bfloat16 pieces (the gradient builds): fp32's own range */
-#else
-#define OTP_RANGE_LIMIT 65504.f
-#endif
 enum {
     OTP_RANGE_CONVX = 1, OTP_RANGE_CONVS = 2, OTP_RANGE_CONVS2 = 3, OTP_RANGE_POINTX = 4, OTP_RANGE_STEM = 5, OTP_RANGE_S8PASS = 6,
     OTP_RANGE_MLPX = 7, OTP_RANGE_DENSEX = 8, OTP_RANGE_ATTN = 9, OTP_RANGE_DCNF = 10, OTP_RANGE_H16 = 11
 };
 unsigned* otp_range_word();                                        // host side: the word's address (NULL without a GPU)
+template <typename P>                                              // P: the piece traits above, whose range_limit is the bound
+__device__ __forceinline__ bool otp_out_of_range(float v) {
 #ifdef OTP_NO_RANGE_GUARD                                          /* development A/B only (tools/lib_variant.sh): what the guard costs */
-__device__ __forceinline__ bool otp_out_of_range(float) { return false; }
+    return false;
 #else
-__device__ __forceinline__ bool otp_out_of_range(float v) { return !(__builtin_fabsf(v) < OTP_RANGE_LIMIT); }   // true for NaN too
+    return !(__builtin_fabsf(v) < P::range_limit);                 // true for NaN too
 #endif
+}
+__device__ __forceinline__ bool otp_out_of_range(float v) { return otp_out_of_range<otp_half_pieces>(v); }
 __device__ __forceinline__ void otp_range_report(unsigned* word, bool bad, unsigned code) {
     if (bad && word) __hip_atomic_store(word, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }

@@ -9,14 +9,11 @@
 // block at a time (LDS-DMA, double buffered, one barrier per block); a block's 16 x 32 result is scaled, shifted, added to
 // the residual and stored as soon as its 30 MFMAs are done.
 //
-// This file is compiled twice.  densex.o: IEEE-half pieces (csrc/common.h) for the forward's O(1) activations.  densex_grad.o
-// (densex_grad.hip: -DOTP_X3_BF16, entry points suffixed _bf16p): bfloat16 pieces for operands whose magnitude is not known -
-// the GRADIENTS the training backward sends through the same projection (dx = W^T dy, otpose_amd/train_ops.py): a half piece
-// flushes 1e-8 to zero and holds 1e-5 to 8 bits, a bfloat16 pair keeps 16-17 bits at any magnitude.
+// The packer and the projection are templates over the piece traits P (csrc/common.h).  otp_half_pieces: the forward's O(1)
+// activations.  otp_bf16_pieces (entry points suffixed _bf16p): operands whose magnitude is not known - the GRADIENTS the
+// training backward sends through the same projection (dx = W^T dy, otpose_amd/train_ops.py): a half piece flushes 1e-8 to
+// zero and holds 1e-5 to 8 bits, a bfloat16 pair keeps 16-17 bits at any magnitude.
 #include "x3.h"
-#ifndef OTP_ENTRY
-#define OTP_ENTRY(name) name
-#endif
 
 namespace {
 
@@ -24,6 +21,7 @@ constexpr int dx_ks(int C) { return (C + 31) / 32; }
 // bytes of one 16-row output block: A fragments [ks][hi, lo][1 KB], scale[16], shift[16]; whole 4 KB (256 x 16 B) passes
 constexpr int dx_block_bytes(int C) { return (dx_ks(C) * 2 * 1024 + 128 + 4095) / 4096 * 4096; }
 
+template <typename P>
 __global__ void densex_pack_kernel(const float* __restrict__ w, const float* __restrict__ scale, const float* __restrict__ shift,
                                    unsigned char* __restrict__ packed, int C) {
     const int KS = dx_ks(C), MT = (C + 15) / 16, BLKB = dx_block_bytes(C), units = BLKB / 16;
@@ -39,8 +37,8 @@ __global__ void densex_pack_kernel(const float* __restrict__ w, const float* __r
             const int c = 32 * ks + 8 * kq + j;
             v[j] = (row < C && c < C) ? w[(size_t)row * C + c] : 0.f;
         }
-        otp_x3x8 hi, lo;
-        otp_x3_split8(v, hi, lo);
+        typename P::x8 hi, lo;
+        otp_x3_split8<P>(v, hi, lo);
         o = __builtin_bit_cast(otp_u32x4, (frag & 1) ? lo : hi);
     } else if (u < KS * 2 * 64 + 8) {
         const int k = (u - KS * 2 * 64) * 4;                       // floats 0..15: scale, 16..31: shift
@@ -62,13 +60,13 @@ __global__ void densex_pack_kernel(const float* __restrict__ w, const float* __r
 // the DMA alone (`s_waitcnt vmcnt(4)`: all but the four stores, which stay in flight under the next block's MFMAs) instead of
 // the `vmcnt(0)` of __syncthreads(), which made every block pay a store round trip.
 // H1: the fp16 engine's arithmetic - the hi pieces only (operands rounded to half once), one MFMA per product
-template <int C, bool RES, bool H1 = false>
-__device__ __forceinline__ void dx_project(const otp_x3x8 (&Xh)[dx_ks(C)][2], const otp_x3x8 (&Xl)[dx_ks(C)][2],
+template <typename P, int C, bool RES, bool H1 = false>
+__device__ __forceinline__ void dx_project(const typename P::x8 (&Xh)[dx_ks(C)][2], const typename P::x8 (&Xl)[dx_ks(C)][2],
                                            const unsigned char* __restrict__ packed, unsigned char* lds,
                                            const float* __restrict__ res, float* __restrict__ out, size_t base, int T, int tok,
                                            bool valid, unsigned* rflag) {
     constexpr int KS = dx_ks(C), MT = (C + 15) / 16, BLKB = dx_block_bytes(C);
-    bool bad = false;                                 // range guard (common.h): a NaN sum = an operand beyond a half's range
+    bool bad = false;                                 // range guard (common.h): a NaN sum = an operand beyond the pieces' range
     const int lane = threadIdx.x & 63, kq = lane >> 4;
     const unsigned plane = (unsigned)((size_t)C * T * sizeof(float));
     const otp_rsrc ro = make_rsrc32(out + base, plane);
@@ -86,29 +84,29 @@ __device__ __forceinline__ void dx_project(const otp_x3x8 (&Xh)[dx_ks(C)][2], co
         asm volatile("" ::: "memory");
         if (mt + 1 < MT) otp_lds_stage<256, BLKB>(packed + (size_t)(mt + 1) * BLKB, lds + ((mt + 1) & 1) * BLKB);
         asm volatile("" ::: "memory");
-        const unsigned char* P = lds + (mt & 1) * BLKB;
+        const unsigned char* blk = lds + (mt & 1) * BLKB;
         otp_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            const otp_x3x8 ah = *reinterpret_cast<const otp_x3x8*>(P + (ks * 2) * 1024 + lane * 16);
+            const typename P::x8 ah = *reinterpret_cast<const typename P::x8*>(blk + (ks * 2) * 1024 + lane * 16);
             if constexpr (!H1) {
-                const otp_x3x8 al = *reinterpret_cast<const otp_x3x8*>(P + (ks * 2 + 1) * 1024 + lane * 16);
-                acc0 = OTP_X3_MFMA(al, Xh[ks][0], acc0, 0, 0, 0);
-                acc1 = OTP_X3_MFMA(al, Xh[ks][1], acc1, 0, 0, 0);
-                acc0 = OTP_X3_MFMA(ah, Xl[ks][0], acc0, 0, 0, 0);
-                acc1 = OTP_X3_MFMA(ah, Xl[ks][1], acc1, 0, 0, 0);
+                const typename P::x8 al = *reinterpret_cast<const typename P::x8*>(blk + (ks * 2 + 1) * 1024 + lane * 16);
+                acc0 = P::mfma(al, Xh[ks][0], acc0);
+                acc1 = P::mfma(al, Xh[ks][1], acc1);
+                acc0 = P::mfma(ah, Xl[ks][0], acc0);
+                acc1 = P::mfma(ah, Xl[ks][1], acc1);
             }
-            acc0 = OTP_X3_MFMA(ah, Xh[ks][0], acc0, 0, 0, 0);
-            acc1 = OTP_X3_MFMA(ah, Xh[ks][1], acc1, 0, 0, 0);
+            acc0 = P::mfma(ah, Xh[ks][0], acc0);
+            acc1 = P::mfma(ah, Xh[ks][1], acc1);
         }
-        const otp_f32x4 sc = *reinterpret_cast<const otp_f32x4*>(P + KS * 2048 + 16 * kq);
-        const otp_f32x4 sh = *reinterpret_cast<const otp_f32x4*>(P + KS * 2048 + 64 + 16 * kq);
+        const otp_f32x4 sc = *reinterpret_cast<const otp_f32x4*>(blk + KS * 2048 + 16 * kq);
+        const otp_f32x4 sh = *reinterpret_cast<const otp_f32x4*>(blk + KS * 2048 + 64 + 16 * kq);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             otp_f32x2 v = {acc0[i] * sc[i] + sh[i], acc1[i] * sc[i] + sh[i]};
             if (RES) v += r[i];
-            bad |= otp_out_of_range(v.x);
-                bad |= otp_out_of_range(v.y);
+            bad |= otp_out_of_range<P>(v.x);
+            bad |= otp_out_of_range<P>(v.y);
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(otp_u32x2, v), ro, voff[i], 0, 0);
         }
         if (mt + 1 < MT) {
@@ -127,7 +125,7 @@ struct DxArgs {
     float* out[3];
 };
 
-template <int C, bool H1 = false>
+template <typename P, int C, bool H1>
 __global__ __launch_bounds__(256, 2) void densex_cc_kernel(DxArgs A, int T, int tiles_per_b, unsigned* rflag) {
     constexpr int KS = dx_ks(C), BLKB = dx_block_bytes(C);
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BLKB];
@@ -138,7 +136,7 @@ __global__ __launch_bounds__(256, 2) void densex_cc_kernel(DxArgs A, int T, int 
     const size_t base = (size_t)b * C * T;
     const float* __restrict__ x = A.x[blockIdx.y];
     otp_lds_stage<256, BLKB>(A.packed[blockIdx.y], lds);
-    otp_x3x8 Xh[KS][2], Xl[KS][2];
+    typename P::x8 Xh[KS][2], Xl[KS][2];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         float v0[8], v1[8];
@@ -150,11 +148,11 @@ __global__ __launch_bounds__(256, 2) void densex_cc_kernel(DxArgs A, int T, int 
             v0[j] = live ? v.x : 0.f;
             v1[j] = live ? v.y : 0.f;
         }
-        otp_x3_split8(v0, Xh[ks][0], Xl[ks][0]);
-        otp_x3_split8(v1, Xh[ks][1], Xl[ks][1]);
+        otp_x3_split8<P>(v0, Xh[ks][0], Xl[ks][0]);
+        otp_x3_split8<P>(v1, Xh[ks][1], Xl[ks][1]);
     }
     __syncthreads();
-    dx_project<C, true, H1>(Xh, Xl, A.packed[blockIdx.y], lds, A.res[blockIdx.y], A.out[blockIdx.y], base, T, tok, valid, rflag);
+    dx_project<P, C, true, H1>(Xh, Xl, A.packed[blockIdx.y], lds, A.res[blockIdx.y], A.out[blockIdx.y], base, T, tok, valid, rflag);
 }
 
 struct QxArgs {
@@ -238,36 +236,36 @@ __global__ __launch_bounds__(256, C <= 136 ? 3 : 1) void qkvx_front_kernel(const
             otp_x3_split8(X1[ks], Xh[ks][1], Xl[ks][1]);
         }
         __syncthreads();                              // weight block 0 of this problem landed
-        dx_project<C, false, H1>(Xh, Xl, A.packed[p], lds, nullptr, A.out[p], base, T, tok, valid, rflag);
+        dx_project<otp_half_pieces, C, false, H1>(Xh, Xl, A.packed[p], lds, nullptr, A.out[p], base, T, tok, valid, rflag);
     }
 }
 
 }  // namespace
 
 // C = 136: 8 stacked maps x 17 joints (5-frame window); C = 204: 12 x 17 (the 7-frame window of BASELINE configs[4])
-#ifndef OTP_X3_GRAD_COPY
 extern "C" int otp_dense_x3_supported(int C, int T) { return ((C == 136 || C == 204) && T > 0 && T % 2 == 0) ? 1 : 0; }
 
 extern "C" size_t otp_dense_x3_weight_bytes(int C) {
     if (C <= 0 || C % 4) return 0;
     return (size_t)((C + 15) / 16) * dx_block_bytes(C);
 }
-#endif
 
-extern "C" int OTP_ENTRY(otp_dense_x3_pack)(const void* w, const void* scale, const void* shift, void* packed, int C, void* stream) {
+namespace {
+template <typename P>
+int dx_pack_launch(const void* w, const void* scale, const void* shift, void* packed, int C, void* stream) {
     if (!w || !packed) return OTP_ERR_BAD_ARG;
     const size_t bytes = otp_dense_x3_weight_bytes(C);
     if (!bytes) return OTP_ERR_UNSUPPORTED;
     const int total = (int)(bytes / 16);
-    hipLaunchKernelGGL(densex_pack_kernel, dim3(otp_ceil_div(total, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(densex_pack_kernel<P>, dim3(otp_ceil_div(total, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const float*>(w), static_cast<const float*>(scale), static_cast<const float*>(shift),
                        static_cast<unsigned char*>(packed), C);
     return otp_launch_status();
 }
 
-namespace {
+template <typename P, bool H1>
 int dx_dense_launch(const void* const* x, const void* const* packed, const void* const* res, void* const* out, int nprob, int B, int C,
-                    int T, void* stream, bool h1) {
+                    int T, void* stream) {
     if (!x || !packed || !out || nprob < 1 || nprob > 3 || B <= 0) return OTP_ERR_BAD_ARG;
     if (!otp_dense_x3_supported(C, T)) return OTP_ERR_UNSUPPORTED;
     DxArgs a = {};
@@ -284,32 +282,37 @@ int dx_dense_launch(const void* const* x, const void* const* packed, const void*
     const int tiles = otp_ceil_div(T, 128);
     const dim3 grid((unsigned)(B * tiles), (unsigned)nprob);
     auto st = static_cast<hipStream_t>(stream);
-    if (C == 204) {
-        if (h1) hipLaunchKernelGGL((densex_cc_kernel<204, true>), grid, dim3(256), 0, st, a, T, tiles, otp_range_word());
-        else hipLaunchKernelGGL((densex_cc_kernel<204, false>), grid, dim3(256), 0, st, a, T, tiles, otp_range_word());
-    } else {
-        if (h1) hipLaunchKernelGGL((densex_cc_kernel<136, true>), grid, dim3(256), 0, st, a, T, tiles, otp_range_word());
-        else hipLaunchKernelGGL((densex_cc_kernel<136, false>), grid, dim3(256), 0, st, a, T, tiles, otp_range_word());
-    }
+    if (C == 204) hipLaunchKernelGGL((densex_cc_kernel<P, 204, H1>), grid, dim3(256), 0, st, a, T, tiles, otp_range_word());
+    else hipLaunchKernelGGL((densex_cc_kernel<P, 136, H1>), grid, dim3(256), 0, st, a, T, tiles, otp_range_word());
     return otp_launch_status();
 }
 }  // namespace
 
-extern "C" int OTP_ENTRY(otp_dense_x3)(const void* const* x, const void* const* packed, const void* const* res, void* const* out,
-                            int nprob, int B, int C, int T, void* stream) {
-    return dx_dense_launch(x, packed, res, out, nprob, B, C, T, stream, false);
+extern "C" int otp_dense_x3_pack(const void* w, const void* scale, const void* shift, void* packed, int C, void* stream) {
+    return dx_pack_launch<otp_half_pieces>(w, scale, shift, packed, C, stream);
 }
 
-#ifndef OTP_X3_GRAD_COPY
+extern "C" int otp_dense_x3_pack_bf16p(const void* w, const void* scale, const void* shift, void* packed, int C, void* stream) {
+    return dx_pack_launch<otp_bf16_pieces>(w, scale, shift, packed, C, stream);
+}
+
+extern "C" int otp_dense_x3(const void* const* x, const void* const* packed, const void* const* res, void* const* out,
+                            int nprob, int B, int C, int T, void* stream) {
+    return dx_dense_launch<otp_half_pieces, false>(x, packed, res, out, nprob, B, C, T, stream);
+}
+
+extern "C" int otp_dense_x3_bf16p(const void* const* x, const void* const* packed, const void* const* res, void* const* out,
+                                  int nprob, int B, int C, int T, void* stream) {
+    return dx_dense_launch<otp_bf16_pieces, false>(x, packed, res, out, nprob, B, C, T, stream);
+}
+
 /* otp_dense_x3 with the fp16 engine's arithmetic: operands rounded to half once (the hi pieces of the same packed image), one MFMA
  * per product; fp32 tensors and accumulation */
 extern "C" int otp_dense_h1(const void* const* x, const void* const* packed, const void* const* res, void* const* out, int nprob, int B,
                             int C, int T, void* stream) {
-    return dx_dense_launch(x, packed, res, out, nprob, B, C, T, stream, true);
+    return dx_dense_launch<otp_half_pieces, true>(x, packed, res, out, nprob, B, C, T, stream);
 }
-#endif
 
-#ifndef OTP_X3_GRAD_COPY
 namespace {
 int dx_qkv_launch(const void* x, const void* table, const void* packed_q, const void* packed_k, const void* packed_v, void* q, void* k,
                   void* v, int B, int C, int T, float eps, void* stream, bool h1) {
@@ -350,4 +353,3 @@ extern "C" int otp_qkv_front_h1(const void* x, const void* table, const void* pa
                                 const void* packed_v, void* q, void* k, void* v, int B, int C, int T, float eps, void* stream) {
     return dx_qkv_launch(x, table, packed_q, packed_k, packed_v, q, k, v, B, C, T, eps, stream, true);
 }
-#endif  // OTP_X3_GRAD_COPY

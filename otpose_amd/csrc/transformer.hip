@@ -6,15 +6,13 @@
 // All tensors are (B, C, T) with T contiguous, so a thread owns one time step t and walks the C
 // channels: every global access of a wave is a coalesced 256-byte run along T.
 //
-// This file is compiled twice.  transformer.o: everything, split products on IEEE-half pieces (csrc/common.h).
-// transformer_grad.o (transformer_grad.hip: -DOTP_X3_BF16 -DOTP_X3_GRAD_COPY): only otp_chan_attn_scores_bf16p /
-// otp_chan_attn_apply_bf16p, the two attention products with bfloat16 pieces, for the training backward, whose operands are
-// GRADIENTS of unknown magnitude (a half piece flushes 1e-8 to zero; a bfloat16 pair keeps 16-17 bits at any magnitude).
-#include "common.h"
+// The two split-product kernels of the attention are templates over the piece traits P (csrc/common.h): otp_half_pieces for
+// the forward, otp_bf16_pieces for otp_chan_attn_scores_bf16p / otp_chan_attn_apply_bf16p, the two attention products of the
+// training backward, whose operands are GRADIENTS of unknown magnitude (a half piece flushes 1e-8 to zero; a bfloat16 pair
+// keeps 16-17 bits at any magnitude).
+#include "x3.h"
 #include <cstdlib>
-#ifndef OTP_ENTRY
-#define OTP_ENTRY(name) name
-#endif
+#include <type_traits>
 
 namespace {
 
@@ -335,7 +333,7 @@ __global__ __launch_bounds__(256) void attn_scores_kernel(const float* __restric
 // 16 x 16 score tile takes 3 MFMAs per 32 tokens instead of 8 f32 ones at twice the cycles.
 constexpr int SX_PITCH = ATT_TC * 2 + 16;          // bytes per LDS row
 
-template <int NB>
+template <typename P, int NB>
 __global__ __launch_bounds__(256) void attn_scores_x3_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                               float* __restrict__ slabs, int hs, int T, int chunk) {
     constexpr int HSP = NB * 16, NT = NB * NB, TPW = (NT + 3) / 4;
@@ -376,19 +374,6 @@ __global__ __launch_bounds__(256) void attn_scores_x3_kernel(const float* __rest
             pk[j] = b;
         }
     };
-    auto split4 = [](otp_f32x4 v, unsigned long long& hi, unsigned long long& lo) __attribute__((always_inline)) {
-        uint32_t h[2], l[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const otp_f32x2 a = {v[2 * i], v[2 * i + 1]};
-            const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, otp_x3x2));
-            const otp_f32x2 af = otp_x3_widen(hb);
-            h[i] = hb;
-            l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a - af, otp_x3x2));
-        }
-        hi = (unsigned long long)h[0] | ((unsigned long long)h[1] << 32);
-        lo = (unsigned long long)l[0] | ((unsigned long long)l[1] << 32);
-    };
     auto store_tile = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
@@ -396,10 +381,10 @@ __global__ __launch_bounds__(256) void attn_scores_x3_kernel(const float* __rest
             if (idx < HSP * (ATT_TC / 4)) {
                 const int row = idx / (ATT_TC / 4), tt = 4 * (idx - row * (ATT_TC / 4));
                 unsigned long long h, l;
-                split4(pq[j], h, l);
+                otp_x3_split4<P>(pq[j], h, l);
                 *reinterpret_cast<unsigned long long*>(qh + row * SX_PITCH + tt * 2) = h;
                 *reinterpret_cast<unsigned long long*>(ql + row * SX_PITCH + tt * 2) = l;
-                split4(pk[j], h, l);
+                otp_x3_split4<P>(pk[j], h, l);
                 *reinterpret_cast<unsigned long long*>(kh + row * SX_PITCH + tt * 2) = h;
                 *reinterpret_cast<unsigned long long*>(kl_ + row * SX_PITCH + tt * 2) = l;
             }
@@ -419,13 +404,13 @@ __global__ __launch_bounds__(256) void attn_scores_x3_kernel(const float* __rest
                 const int qo = (ib * 16 + r16) * SX_PITCH + kk * 16, ko = (jb * 16 + r16) * SX_PITCH + kk * 16;
 #pragma unroll
                 for (int ks = 0; ks < ATT_TC / 32; ++ks) {
-                    const otp_x3x8 a_h = *reinterpret_cast<const otp_x3x8*>(qh + qo + ks * 64);
-                    const otp_x3x8 a_l = *reinterpret_cast<const otp_x3x8*>(ql + qo + ks * 64);
-                    const otp_x3x8 b_h = *reinterpret_cast<const otp_x3x8*>(kh + ko + ks * 64);
-                    const otp_x3x8 b_l = *reinterpret_cast<const otp_x3x8*>(kl_ + ko + ks * 64);
-                    acc[i] = OTP_X3_MFMA(a_l, b_h, acc[i], 0, 0, 0);
-                    acc[i] = OTP_X3_MFMA(a_h, b_l, acc[i], 0, 0, 0);
-                    acc[i] = OTP_X3_MFMA(a_h, b_h, acc[i], 0, 0, 0);
+                    const typename P::x8 a_h = *reinterpret_cast<const typename P::x8*>(qh + qo + ks * 64);
+                    const typename P::x8 a_l = *reinterpret_cast<const typename P::x8*>(ql + qo + ks * 64);
+                    const typename P::x8 b_h = *reinterpret_cast<const typename P::x8*>(kh + ko + ks * 64);
+                    const typename P::x8 b_l = *reinterpret_cast<const typename P::x8*>(kl_ + ko + ks * 64);
+                    acc[i] = P::mfma(a_l, b_h, acc[i]);
+                    acc[i] = P::mfma(a_h, b_l, acc[i]);
+                    acc[i] = P::mfma(a_h, b_h, acc[i]);
                 }
             }
         }
@@ -595,8 +580,8 @@ constexpr int pvx_waves(int NB) { return NB <= 5 ? 8 : 4; }
 constexpr size_t pvx_lds(int NB) {
     return NB <= 5 ? PVX_LDS : (size_t)(32 * pvx_waves(NB) + NB * 16) * (NB * 16 * 4 + 16) + 16;
 }
-template <int NB>
-__global__ __launch_bounds__(64 * pvx_waves(NB), 2) void attn_pv_x3_kernel(const float* __restrict__ v, const float* __restrict__ P,
+template <typename P, int NB>
+__global__ __launch_bounds__(64 * pvx_waves(NB), 2) void attn_pv_x3_kernel(const float* __restrict__ v, const float* __restrict__ M,
                                                                       float* __restrict__ out, int hs, int T, unsigned* rflag) {
     constexpr int PVX_WAVES = pvx_waves(NB), PVX_TH = 64 * PVX_WAVES, PVX_TT = 32 * PVX_WAVES;
     constexpr int HSP = NB * 16, KS = (HSP + 31) / 32, G = HSP / 8;
@@ -610,22 +595,9 @@ __global__ __launch_bounds__(64 * pvx_waves(NB), 2) void attn_pv_x3_kernel(const
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int bh = blockIdx.x, t0 = blockIdx.y * PVX_TT;
     const float* vb = v + (size_t)bh * hs * T;
-    const float* pb = P + (size_t)bh * HSP * HSP;
-    auto split4 = [](otp_f32x4 x, unsigned long long& hi, unsigned long long& lo) __attribute__((always_inline)) {
-        uint32_t h[2], l[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const otp_f32x2 a = {x[2 * i], x[2 * i + 1]};
-            const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, otp_x3x2));
-            const otp_f32x2 af = otp_x3_widen(hb);
-            h[i] = hb;
-            l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a - af, otp_x3x2));
-        }
-        hi = (unsigned long long)h[0] | ((unsigned long long)h[1] << 32);
-        lo = (unsigned long long)l[0] | ((unsigned long long)l[1] << 32);
-    };
+    const float* pb = M + (size_t)bh * HSP * HSP;
     if (tid < 4) reinterpret_cast<uint32_t*>(zrec)[tid] = 0u;
-    // P (HSP x HSP fp32, zero padded) -> rows of bf16 hi / lo
+    // M (HSP x HSP fp32, zero padded) -> rows of hi / lo pieces
     {
         otp_f32x4 rp[NP4];
 #pragma unroll
@@ -639,7 +611,7 @@ __global__ __launch_bounds__(64 * pvx_waves(NB), 2) void attn_pv_x3_kernel(const
             if (idx < HSP * HSP / 4) {
                 const int i = (4 * idx) / HSP, jj = 4 * idx - i * HSP;
                 unsigned long long h, l;
-                split4(rp[j], h, l);
+                otp_x3_split4<P>(rp[j], h, l);
                 *reinterpret_cast<unsigned long long*>(prec + i * REC + jj * 2) = h;
                 *reinterpret_cast<unsigned long long*>(prec + i * REC + HSP * 2 + jj * 2) = l;
             }
@@ -673,8 +645,8 @@ __global__ __launch_bounds__(64 * pvx_waves(NB), 2) void attn_pv_x3_kernel(const
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 unsigned long long h0, l0, h1, l1;
-                split4((otp_f32x4){x[0][c], x[1][c], x[2][c], x[3][c]}, h0, l0);
-                split4((otp_f32x4){x[4][c], x[5][c], x[6][c], x[7][c]}, h1, l1);
+                otp_x3_split4<P>((otp_f32x4){x[0][c], x[1][c], x[2][c], x[3][c]}, h0, l0);
+                otp_x3_split4<P>((otp_f32x4){x[4][c], x[5][c], x[6][c], x[7][c]}, h1, l1);
                 unsigned char* r = vrec + (4 * f4 + c) * REC + g * 16;
                 *reinterpret_cast<unsigned long long*>(r) = h0;
                 *reinterpret_cast<unsigned long long*>(r + 8) = h1;
@@ -694,34 +666,34 @@ __global__ __launch_bounds__(64 * pvx_waves(NB), 2) void attn_pv_x3_kernel(const
     for (int ks = 0; ks < KS; ++ks) {
         const int kg = 4 * ks + kk;                                // 8-wide j group of this lane
         const bool kv = kg < G;
-        otp_x3x8 ah[2], al[2];
+        typename P::x8 ah[2], al[2];
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             const unsigned char* a = kv ? vrec + ((wave * 2 + mt) * 16 + r16) * REC + kg * 16 : zrec;
-            ah[mt] = *reinterpret_cast<const otp_x3x8*>(a);
-            al[mt] = *reinterpret_cast<const otp_x3x8*>(kv ? a + HSP * 2 : zrec);
+            ah[mt] = *reinterpret_cast<const typename P::x8*>(a);
+            al[mt] = *reinterpret_cast<const typename P::x8*>(kv ? a + HSP * 2 : zrec);
         }
 #pragma unroll
         for (int nt = 0; nt < NB; ++nt) {
             const unsigned char* b = kv ? prec + (nt * 16 + r16) * REC + kg * 16 : zrec;
-            const otp_x3x8 b_h = *reinterpret_cast<const otp_x3x8*>(b);
-            const otp_x3x8 b_l = *reinterpret_cast<const otp_x3x8*>(kv ? b + HSP * 2 : zrec);
+            const typename P::x8 b_h = *reinterpret_cast<const typename P::x8*>(b);
+            const typename P::x8 b_l = *reinterpret_cast<const typename P::x8*>(kv ? b + HSP * 2 : zrec);
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
-                acc[mt][nt] = OTP_X3_MFMA(al[mt], b_h, acc[mt][nt], 0, 0, 0);
-                acc[mt][nt] = OTP_X3_MFMA(ah[mt], b_l, acc[mt][nt], 0, 0, 0);
-                acc[mt][nt] = OTP_X3_MFMA(ah[mt], b_h, acc[mt][nt], 0, 0, 0);
+                acc[mt][nt] = P::mfma(al[mt], b_h, acc[mt][nt]);
+                acc[mt][nt] = P::mfma(ah[mt], b_l, acc[mt][nt]);
+                acc[mt][nt] = P::mfma(ah[mt], b_h, acc[mt][nt]);
             }
         }
     }
-    {   // range guard (common.h): q, k or v beyond a half's range has made these sums NaN (through the scores and the softmax)
+    {   // range guard (common.h): q, k or v beyond the pieces' range has made these sums NaN (through the scores and the softmax)
         bool bad = false;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int nt = 0; nt < NB; ++nt)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) bad |= otp_out_of_range(acc[mt][nt][r]);
+                for (int r = 0; r < 4; ++r) bad |= otp_out_of_range<P>(acc[mt][nt][r]);
         otp_range_report(rflag, bad, OTP_RANGE_ATTN);
     }
     float* ob = out + (size_t)bh * T * hs;
@@ -791,7 +763,6 @@ __global__ void upsample_linear4_kernel(const float* __restrict__ x, float* __re
 
 }  // namespace
 
-#ifndef OTP_X3_GRAD_COPY
 extern "C" int otp_ln_channel(const void* x, const void* gamma, const void* beta, void* y, void* pool, int B,
                               int C, int T, float eps, void* stream) {
     if (!x || !gamma || !beta || !y || B <= 0 || C <= 0 || T <= 0) return OTP_ERR_BAD_ARG;
@@ -836,25 +807,97 @@ extern "C" int otp_dwconv_ln3(const void* x, const void* dwq, const void* dwk, c
 #undef OTP_DW_ARGS
     return otp_launch_status();
 }
-#endif  // OTP_X3_GRAD_COPY
-
-// 1: score products as split products (default), 0: f32 MFMA (otp_chan_attn_set_split); one flag for both copies of this file
-#ifndef OTP_X3_GRAD_COPY
-std::atomic<int> otp_g_attn_split{1};
-#else
-extern std::atomic<int> otp_g_attn_split;
-#endif
-#define g_attn_split otp_g_attn_split
-
 namespace {
+// 1: the attention products as split products (default), 0: f32 MFMA (otp_chan_attn_set_split)
+std::atomic<int> g_attn_split{1};
+
 int attn_splits(int BH, int T) {
     int ns = 1;
     while (BH * ns < 768 && T / (ns * 2) >= 2 * ATT_TC) ns *= 2;
     return ns;
 }
+
+// f(std::integral_constant<int, NB>) for the NB = ceil(hs / 16) <= 7 of a head; the callers have checked the bound
+template <typename F>
+void with_nb(int hs, F f) {
+    switch ((hs + 15) / 16) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 5: f(std::integral_constant<int, 5>{}); break;
+        case 6: f(std::integral_constant<int, 6>{}); break;
+        default: f(std::integral_constant<int, 7>{}); break;
+    }
+}
+
+// slabs[bh][s] = partial a . b^T over the s-th of NS slices of T (chunk steps each): split products on pieces P, or the f32 kernel.
+// (OTP_ALLOW_BIG_LDS in a body instantiated per P and NB: one flag per kernel instantiation)
+template <typename P>
+void launch_scores(const float* a, const float* b, float* slabs, int BH, int hs, int T, int NS, int chunk, hipStream_t st) {
+    const bool split = g_attn_split.load(std::memory_order_relaxed);
+    with_nb(hs, [&](auto nb) {
+        constexpr int NB = decltype(nb)::value;
+        if (split) {
+            auto kern = attn_scores_x3_kernel<P, NB>;
+            const size_t lds = (size_t)4 * NB * 16 * SX_PITCH;
+            OTP_ALLOW_BIG_LDS(kern, lds);
+            hipLaunchKernelGGL(kern, dim3(BH, NS), dim3(256), lds, st, a, b, slabs, hs, T, chunk);
+        } else {
+            hipLaunchKernelGGL(attn_scores_kernel<NB>, dim3(BH, NS), dim3(256), 0, st, a, b, slabs, hs, T, chunk);
+        }
+    });
+}
+
+// the f32 kernel of launch_apply: independent of the piece type, so its LDS flag is one per NB
+template <int NB>
+void launch_pv_f32(const float* v, const float* M, float* out, int BH, int hs, int T, hipStream_t st) {
+    constexpr int HSP = NB * 16, TT = pv_tt(NB);
+    const size_t lds = ((size_t)HSP * (HSP + 2) + (size_t)HSP * (TT + 16)) * sizeof(float);
+    auto kern = attn_pv_kernel<NB>;
+    OTP_ALLOW_BIG_LDS(kern, lds);
+    hipLaunchKernelGGL(kern, dim3(BH, otp_ceil_div(T, TT)), dim3(256), lds, st, v, M, out, hs, T);
+}
+
+// out[bh][t][i] = sum_j M[bh][i][j] * v[bh][j][t]: split products on pieces P, or the f32 kernel
+template <typename P>
+void launch_apply(const float* v, const float* M, float* out, int BH, int hs, int T, hipStream_t st) {
+    const bool split = g_attn_split.load(std::memory_order_relaxed);
+    with_nb(hs, [&](auto nb) {
+        constexpr int NB = decltype(nb)::value;
+        if (split) {
+            auto kern = attn_pv_x3_kernel<P, NB>;
+            const size_t lds = pvx_lds(NB);                        // >= (tokens + HSP) * (HSP * 4 + 16) + 16
+            OTP_ALLOW_BIG_LDS(kern, lds);
+            hipLaunchKernelGGL(kern, dim3(BH, otp_ceil_div(T, 32 * pvx_waves(NB))), dim3(64 * pvx_waves(NB)), lds, st, v, M, out, hs,
+                               T, otp_range_word());
+        } else {
+            launch_pv_f32<NB>(v, M, out, BH, hs, T, st);
+        }
+    });
+}
+
+template <typename P>
+int scores_entry(const void* a, const void* b, void* slabs, int BH, int hs, int T, void* stream) {
+    if (!a || !b || !slabs || BH <= 0 || hs <= 0 || T <= 0) return OTP_ERR_BAD_ARG;
+    if (hs > 7 * 16) return OTP_ERR_UNSUPPORTED;
+    const int NS = attn_splits(BH, T);
+    const int chunk = otp_ceil_div(otp_ceil_div(T, NS), ATT_TC) * ATT_TC;
+    launch_scores<P>(static_cast<const float*>(a), static_cast<const float*>(b), static_cast<float*>(slabs), BH, hs, T, NS, chunk,
+                     static_cast<hipStream_t>(stream));
+    return otp_launch_status();
+}
+
+template <typename P>
+int apply_entry(const void* v, const void* M, void* out, int BH, int hs, int T, void* stream) {
+    if (!v || !M || !out || BH <= 0 || hs <= 0 || T <= 0) return OTP_ERR_BAD_ARG;
+    if (hs > 7 * 16) return OTP_ERR_UNSUPPORTED;
+    launch_apply<P>(static_cast<const float*>(v), static_cast<const float*>(M), static_cast<float*>(out), BH, hs, T,
+                    static_cast<hipStream_t>(stream));
+    return otp_launch_status();
+}
 }  // namespace
 
-#ifndef OTP_X3_GRAD_COPY
 extern "C" size_t otp_chan_attn_workspace(int B, int C, int T, int n_head) {
     if (B <= 0 || C <= 0 || T <= 0 || n_head <= 0 || C % n_head) return 0;
     const int hs = C / n_head, HSP = (hs + 15) & ~15;
@@ -866,147 +909,46 @@ extern "C" int otp_chan_attn(const void* q, const void* k, const void* v, void* 
                              size_t workspace_bytes, int B, int C, int T, int n_head, float scale, void* stream) {
     if (!q || !k || !v || !out || !workspace || B <= 0 || C <= 0 || T <= 0 || n_head <= 0) return OTP_ERR_BAD_ARG;
     if (C % n_head) return OTP_ERR_BAD_ARG;
-    const int hs = C / n_head, HSP = (hs + 15) & ~15, NB = HSP / 16;
-    if (NB > 7) return OTP_ERR_UNSUPPORTED;                              // hs <= 112
+    const int hs = C / n_head, HSP = (hs + 15) & ~15;
+    if (HSP > 7 * 16) return OTP_ERR_UNSUPPORTED;                        // hs <= 112
     if (workspace_bytes < otp_chan_attn_workspace(B, C, T, n_head)) return OTP_ERR_WORKSPACE;
     const int BH = B * n_head, NS = attn_splits(BH, T);
     const int chunk = otp_ceil_div(otp_ceil_div(T, NS), ATT_TC) * ATT_TC;
     auto st = static_cast<hipStream_t>(stream);
     float* slabs = static_cast<float*>(workspace);
     float* P = slabs + (size_t)BH * NS * HSP * HSP;
-    auto qf = static_cast<const float*>(q);
-    auto kf = static_cast<const float*>(k);
-    auto vf = static_cast<const float*>(v);
-    auto of = static_cast<float*>(out);
-    const int TT = pv_tt(NB);
-    const size_t pv_lds = ((size_t)HSP * (HSP + 2) + (size_t)HSP * (TT + 16)) * sizeof(float);
-    dim3 g1(BH, NS), g3(BH, otp_ceil_div(T, TT));
-#define OTP_ATT(NB_)                                                                                           \
-    {                                                                                                          \
-        bool split_ = false;                                                                                   \
-        if (g_attn_split.load(std::memory_order_relaxed)) {                                                    \
-            split_ = true;                                                                                     \
-            auto ks_ = attn_scores_x3_kernel<NB_>;                                                             \
-            const size_t ls_ = (size_t)4 * NB_ * 16 * SX_PITCH;                                                \
-            OTP_ALLOW_BIG_LDS(ks_, ls_);                                                                       \
-            hipLaunchKernelGGL(ks_, g1, dim3(256), ls_, st, qf, kf, slabs, hs, T, chunk);                      \
-        }                                                                                                      \
-        if (!split_) hipLaunchKernelGGL(attn_scores_kernel<NB_>, g1, dim3(256), 0, st, qf, kf, slabs, hs, T, chunk); \
-        hipLaunchKernelGGL(attn_softmax_kernel, dim3(BH, otp_ceil_div(HSP, 4)), dim3(256), 0, st, slabs, P, hs, HSP, NS, scale);      \
-        if (split_) {                                                                                          \
-            auto kx = attn_pv_x3_kernel<NB_>;                                                                  \
-            const size_t lx = pvx_lds(NB_);                 /* >= (tokens + HSP) * (HSP * 4 + 16) + 16 */                                                   \
-            OTP_ALLOW_BIG_LDS(kx, lx);                                                                         \
-            hipLaunchKernelGGL(kx, dim3(BH, otp_ceil_div(T, 32 * pvx_waves(NB_))), dim3(64 * pvx_waves(NB_)), lx, st, vf, P, of, hs, T, otp_range_word()); \
-        } else {                                                                                               \
-            auto kern = attn_pv_kernel<NB_>;                                                                   \
-            OTP_ALLOW_BIG_LDS(kern, pv_lds);                                                                   \
-            hipLaunchKernelGGL(kern, g3, dim3(256), pv_lds, st, vf, P, of, hs, T);                             \
-        }                                                                                                      \
-    }
-    switch (NB) {
-        case 1: OTP_ATT(1) break;
-        case 2: OTP_ATT(2) break;
-        case 3: OTP_ATT(3) break;
-        case 4: OTP_ATT(4) break;
-        case 5: OTP_ATT(5) break;
-        case 6: OTP_ATT(6) break;
-        default: OTP_ATT(7) break;
-    }
-#undef OTP_ATT
+    launch_scores<otp_half_pieces>(static_cast<const float*>(q), static_cast<const float*>(k), slabs, BH, hs, T, NS, chunk, st);
+    hipLaunchKernelGGL(attn_softmax_kernel, dim3(BH, otp_ceil_div(HSP, 4)), dim3(256), 0, st, slabs, P, hs, HSP, NS, scale);
+    launch_apply<otp_half_pieces>(static_cast<const float*>(v), P, static_cast<float*>(out), BH, hs, T, st);
     return otp_launch_status();
 }
 
 // ---- pieces of the channel attention exposed for its backward (otpose_amd/train_ops.py) -------------------------
-// number of T-splits / score slabs the kernels use for (BH, T), and where otp_chan_attn leaves P inside its workspace
-// 1 (default): q.k^T products as split bf16 on the bf16 matrix cores; 0: the f32 MFMA kernel.  Process-wide.
+// 1 (default): the attention products as split products on the 16-bit matrix cores; 0: the f32 MFMA kernels.  Process-wide.
 extern "C" int otp_chan_attn_set_split(int on) {
     g_attn_split.store(on ? 1 : 0, std::memory_order_relaxed);
     return OTP_OK;
 }
 
+// number of T-splits / score slabs the kernels use for (BH, T)
 extern "C" int otp_chan_attn_splits(int BH, int T) { return (BH > 0 && T > 0) ? attn_splits(BH, T) : 0; }
-#endif  // OTP_X3_GRAD_COPY
 
 // slabs[bh][s] (HSP x HSP, zero padded) = partial a . b^T over the s-th slice of T, no scale: sum the slabs for a . b^T
-extern "C" int OTP_ENTRY(otp_chan_attn_scores)(const void* a, const void* b, void* slabs, int BH, int hs, int T, void* stream) {
-    if (!a || !b || !slabs || BH <= 0 || hs <= 0 || T <= 0) return OTP_ERR_BAD_ARG;
-    const int HSP = (hs + 15) & ~15, NB = HSP / 16;
-    if (NB > 7) return OTP_ERR_UNSUPPORTED;
-    const int NS = attn_splits(BH, T);
-    const int chunk = otp_ceil_div(otp_ceil_div(T, NS), ATT_TC) * ATT_TC;
-    auto st = static_cast<hipStream_t>(stream);
-    dim3 g1(BH, NS);
-    auto af = static_cast<const float*>(a);
-    auto bf = static_cast<const float*>(b);
-    auto sf = static_cast<float*>(slabs);
-#define OTP_SC(NB_)                                                                                       \
-    {                                                                                                     \
-        bool split_ = false;                                                                              \
-        if (g_attn_split.load(std::memory_order_relaxed)) {                                               \
-            split_ = true;                                                                                \
-            auto ks_ = attn_scores_x3_kernel<NB_>;                                                        \
-            const size_t ls_ = (size_t)4 * NB_ * 16 * SX_PITCH;                                           \
-            OTP_ALLOW_BIG_LDS(ks_, ls_);                                                                  \
-            hipLaunchKernelGGL(ks_, g1, dim3(256), ls_, st, af, bf, sf, hs, T, chunk);                    \
-        }                                                                                                 \
-        if (!split_) hipLaunchKernelGGL(attn_scores_kernel<NB_>, g1, dim3(256), 0, st, af, bf, sf, hs, T, chunk); \
-    }
-    switch (NB) {
-        case 1: OTP_SC(1) break;
-        case 2: OTP_SC(2) break;
-        case 3: OTP_SC(3) break;
-        case 4: OTP_SC(4) break;
-        case 5: OTP_SC(5) break;
-        case 6: OTP_SC(6) break;
-        default: OTP_SC(7) break;
-    }
-#undef OTP_SC
-    return otp_launch_status();
+extern "C" int otp_chan_attn_scores(const void* a, const void* b, void* slabs, int BH, int hs, int T, void* stream) {
+    return scores_entry<otp_half_pieces>(a, b, slabs, BH, hs, T, stream);
+}
+extern "C" int otp_chan_attn_scores_bf16p(const void* a, const void* b, void* slabs, int BH, int hs, int T, void* stream) {
+    return scores_entry<otp_bf16_pieces>(a, b, slabs, BH, hs, T, stream);
 }
 
 // out[bh][t][i] = sum_j M[bh][i][j] * v[bh][j][t]   (M: HSP x HSP zero padded; the transposed-contiguous output image)
-extern "C" int OTP_ENTRY(otp_chan_attn_apply)(const void* v, const void* M, void* out, int BH, int hs, int T, void* stream) {
-    if (!v || !M || !out || BH <= 0 || hs <= 0 || T <= 0) return OTP_ERR_BAD_ARG;
-    const int HSP = (hs + 15) & ~15, NB = HSP / 16;
-    if (NB > 7) return OTP_ERR_UNSUPPORTED;
-    auto st = static_cast<hipStream_t>(stream);
-    const int TT = pv_tt(NB);
-    const size_t pv_lds = ((size_t)HSP * (HSP + 2) + (size_t)HSP * (TT + 16)) * sizeof(float);
-    dim3 g3(BH, otp_ceil_div(T, TT));
-    auto vf = static_cast<const float*>(v);
-    auto mf = static_cast<const float*>(M);
-    auto of = static_cast<float*>(out);
-#define OTP_APPLY(NB_)                                                                                      \
-    {                                                                                                       \
-        bool split_ = false;                                                                                \
-        if (g_attn_split.load(std::memory_order_relaxed)) {                                                 \
-            split_ = true;                                                                                  \
-            auto kx = attn_pv_x3_kernel<NB_>;                                                               \
-            const size_t lx = pvx_lds(NB_);                                                                 \
-            OTP_ALLOW_BIG_LDS(kx, lx);                                                                      \
-            hipLaunchKernelGGL(kx, dim3(BH, otp_ceil_div(T, 32 * pvx_waves(NB_))), dim3(64 * pvx_waves(NB_)), lx, st, vf, mf, of, hs, T, otp_range_word()); \
-        }                                                                                                   \
-        if (!split_) {                                                                                      \
-            auto kern = attn_pv_kernel<NB_>;                                                                \
-            OTP_ALLOW_BIG_LDS(kern, pv_lds);                                                                \
-            hipLaunchKernelGGL(kern, g3, dim3(256), pv_lds, st, vf, mf, of, hs, T);                         \
-        }                                                                                                   \
-    }
-    switch (NB) {
-        case 1: OTP_APPLY(1) break;
-        case 2: OTP_APPLY(2) break;
-        case 3: OTP_APPLY(3) break;
-        case 4: OTP_APPLY(4) break;
-        case 5: OTP_APPLY(5) break;
-        case 6: OTP_APPLY(6) break;
-        default: OTP_APPLY(7) break;
-    }
-#undef OTP_APPLY
-    return otp_launch_status();
+extern "C" int otp_chan_attn_apply(const void* v, const void* M, void* out, int BH, int hs, int T, void* stream) {
+    return apply_entry<otp_half_pieces>(v, M, out, BH, hs, T, stream);
+}
+extern "C" int otp_chan_attn_apply_bf16p(const void* v, const void* M, void* out, int BH, int hs, int T, void* stream) {
+    return apply_entry<otp_bf16_pieces>(v, M, out, BH, hs, T, stream);
 }
 
-#ifndef OTP_X3_GRAD_COPY
 extern "C" int otp_maxpool3s2_forward(const void* x, void* y, int rows, int T, void* stream) {
     if (!x || !y || rows <= 0 || T <= 0) return OTP_ERR_BAD_ARG;
     const int To = (T + 2 - 3) / 2 + 1;
@@ -1030,4 +972,3 @@ extern "C" int otp_upsample_linear(const void* x, void* out, int B, int C, int T
                            f, out_ctot, out_coff);
     return otp_launch_status();
 }
-#endif  // OTP_X3_GRAD_COPY

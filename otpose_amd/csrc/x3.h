@@ -5,26 +5,43 @@
 #pragma once
 #include "common.h"
 
-// 8 floats -> hi / lo records of 8 pieces each: hi = rne(a), lo = rne(a - hi) (common.h: otp_x3_t)
+// 8 floats -> hi / lo records of 8 pieces each: hi = rne(a), lo = rne(a - hi); P: the piece traits of common.h
+template <typename P = otp_half_pieces>
 __device__ __forceinline__ void otp_x3_split8(const float (&v)[8], otp_u32x4& hi, otp_u32x4& lo) {
     uint32_t h[4], l[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const otp_f32x2 a = {v[2 * i], v[2 * i + 1]};
-        const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, otp_x3x2));
-        const otp_f32x2 af = otp_x3_widen(hb);
+        const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, typename P::x2));
+        const otp_f32x2 af = P::widen(hb);
         h[i] = hb;
-        l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a - af, otp_x3x2));
+        l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a - af, typename P::x2));
     }
     hi = (otp_u32x4){h[0], h[1], h[2], h[3]};
     lo = (otp_u32x4){l[0], l[1], l[2], l[3]};
 }
 // the same as MFMA operand vectors
-__device__ __forceinline__ void otp_x3_split8(const float (&v)[8], otp_x3x8& hi, otp_x3x8& lo) {
+template <typename P = otp_half_pieces>
+__device__ __forceinline__ void otp_x3_split8(const float (&v)[8], typename P::x8& hi, typename P::x8& lo) {
     otp_u32x4 h, l;
-    otp_x3_split8(v, h, l);
-    hi = __builtin_bit_cast(otp_x3x8, h);
-    lo = __builtin_bit_cast(otp_x3x8, l);
+    otp_x3_split8<P>(v, h, l);
+    hi = __builtin_bit_cast(typename P::x8, h);
+    lo = __builtin_bit_cast(typename P::x8, l);
+}
+// 4 floats -> the hi and the lo pieces as one 64-bit word each
+template <typename P>
+__device__ __forceinline__ void otp_x3_split4(otp_f32x4 v, unsigned long long& hi, unsigned long long& lo) {
+    uint32_t h[2], l[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const otp_f32x2 a = {v[2 * i], v[2 * i + 1]};
+        const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, typename P::x2));
+        const otp_f32x2 af = P::widen(hb);
+        h[i] = hb;
+        l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a - af, typename P::x2));
+    }
+    hi = (unsigned long long)h[0] | ((unsigned long long)h[1] << 32);
+    lo = (unsigned long long)l[0] | ((unsigned long long)l[1] << 32);
 }
 
 // ---- weight image and row order of the S8 / H8 3x3 convolutions --------------------------------------------------------------------

@@ -755,7 +755,7 @@ def pack_dense_cc(weight, scale=None, shift=None, x3=False, grad=False):
     """(C, C[, 1]) pointwise weight (+ per-output-channel scale / shift) -> the per-16-row fragment image of
     :func:`dense_cc` (MaskedMHCA query / key / value / proj, model/blocks.py:383-386).  ``x3``: the split-half image of
     csrc/densex.hip (pass the same flag to :func:`dense_cc` / :func:`qkv_front`); ``grad`` (with ``x3``): the image with
-    bfloat16 pieces for :func:`dense_cc` on operands of unknown magnitude - gradients (csrc/densex_grad.hip)."""
+    bfloat16 pieces for :func:`dense_cc` on operands of unknown magnitude - gradients (otp_bf16_pieces in csrc/densex.hip)."""
     _require_gpu(weight)
     c = weight.shape[0]
     L = hip.lib()

@@ -116,7 +116,7 @@ def conv2d_forward(x, weight, bias, stride, pad, dil, routes=None):
 def _dense_cc_launch(routes, x4, w2, bias, out4, grad=False):
     n, c = x4.shape[:2]
     # split products (csrc/densex.hip) unless the exact-fp32 kernels are asked for, as in the inference engine; ``grad``: x4 is a
-    # gradient - bfloat16 pieces (csrc/densex_grad.hip), an IEEE-half piece would flush the small ones to zero
+    # gradient - bfloat16 pieces (otp_bf16_pieces in csrc/densex.hip), an IEEE-half piece would flush the small ones to zero
     x3 = routes.use_x3 and ops.dense_x3_supported(c, x4.shape[2] * x4.shape[3])
     pk = ops.pack_dense_cc(w2, None, bias, x3=x3, grad=grad)
     ops.dense_cc([x4.view(n, c, -1)], [pk], None, [out4.view(n, c, -1)], x3=x3, grad=grad)
@@ -566,7 +566,7 @@ class ChanAttnFunction(Function):
         hip.check(L.otp_transpose_scale(hip.ptr(gout), hip.ptr(d_o), bh, t, hs, 1.0, st), "otp_transpose_scale")
         ns = L.otp_chan_attn_splits(bh, t)
         slabs = new(bh * ns * hsp * hsp)
-        # (every product of the backward has a gradient operand: bfloat16 pieces - csrc/transformer_grad.hip)
+        # (every product of the backward has a gradient operand: bfloat16 pieces - otp_bf16_pieces in csrc/transformer.hip)
         hip.check(L.otp_chan_attn_scores_bf16p(hip.ptr(d_o), hip.ptr(v), hip.ptr(slabs), bh, hs, t, st), "otp_chan_attn_scores_bf16p")
         d_s, d_st, p_t = new(bh, hsp, hsp), new(bh, hsp, hsp), new(bh, hsp, hsp)
         hip.check(L.otp_softmax_backward(hip.ptr(slabs), hip.ptr(p), hip.ptr(d_s), hip.ptr(d_st), hip.ptr(p_t), bh, hs, ns,

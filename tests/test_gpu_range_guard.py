@@ -157,3 +157,44 @@ def test_mlp_and_projection_kernels_flag_an_operand_beyond_65504():
     out = ops.mlp_x3(x, packed, one, zero, x)
     assert _flag() == 7
     assert not bool(torch.isfinite(out).all())
+
+
+def test_the_range_limit_travels_with_the_piece_type_projection():
+    """csrc/densex.hip on both piece types: a 1e5 operand is beyond a half piece (flag OTP_RANGE_DENSEX) and an ordinary number
+    for a bfloat16 pair, whose limit is fp32's own range."""
+    B, C, T = 1, 136, 128
+    g = torch.Generator().manual_seed(8)
+    x = torch.randn(B, C, T, generator=g).cuda()
+    w = (torch.randn(C, C, generator=g) / C ** 0.5).cuda()
+    x[0, 5, 17] = 1.0e5
+    pk_half, pk_bf16 = ops.pack_dense_cc(w, x3=True), ops.pack_dense_cc(w, x3=True, grad=True)
+    _flag()
+    ops.dense_cc([x], [pk_half], x3=True)
+    assert _flag() == 8
+    out = ops.dense_cc([x], [pk_bf16], x3=True, grad=True)[0]
+    assert _flag() == 0
+    assert bool(torch.isfinite(out).all())
+    ref = torch.einsum("oi,bit->bot", w.cpu().double(), x.cpu().double())
+    err = float((out.cpu().double() - ref).abs().max()) / float(ref.abs().max())
+    assert err <= 3e-5, err                                      # the bound of tests/test_gpu_train_ops.py's gradient operands
+
+
+def test_the_range_limit_travels_with_the_piece_type_attention():
+    """csrc/transformer.hip on both piece types: one 1e5 element of v flags the forward's apply (OTP_RANGE_ATTN); the same v
+    through the bfloat16-piece apply of the training backward does not."""
+    B, C, NH, T = 1, 34, 2, 70
+    hs, hsp = C // NH, 32
+    g = torch.Generator().manual_seed(9)
+    q, k, v = (torch.randn(B, C, T, generator=g).cuda() * s for s in (0.3, 0.3, 1.0))
+    v[0, 20, 33] = 1.0e5
+    m = torch.zeros(B * NH, hsp, hsp)
+    m[:, :hs, :hs] = torch.softmax(torch.randn(B * NH, hs, hs, generator=g), dim=-1)
+    m = m.cuda()
+    _flag()
+    ops.chan_attn(q, k, v, NH, hs ** -0.5)
+    assert _flag() == 9
+    out = torch.empty(B * NH, T, hs, device="cuda")
+    hip.check(hip.lib().otp_chan_attn_apply_bf16p(hip.ptr(v), hip.ptr(m), hip.ptr(out), B * NH, hs, T, hip.stream_of(v)),
+              "otp_chan_attn_apply_bf16p")
+    assert _flag() == 0
+    assert bool(torch.isfinite(out).all())

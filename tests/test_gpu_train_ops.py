@@ -2,6 +2,7 @@
 every conv flavour of the path, BatchNorm2d in training mode fused with residual + ReLU, and a BasicBlock composed of
 them (reference model/HRNet.py:514-530 under model.train())."""
 import math
+import os
 
 import pytest
 import torch
@@ -296,7 +297,7 @@ def test_scale_residual_matches_autograd(b, c, t, masked):
 @pytest.mark.parametrize("mag", [1.0, 1e-5, 1e-8])
 def test_gradient_operands_of_any_magnitude_keep_their_precision(mag):
     """The backward sends GRADIENTS through the projection and the attention products.  Their magnitude is whatever the loss
-    makes it; the split products of those calls therefore use bfloat16 pieces (csrc/densex_grad.hip, transformer_grad.hip:
+    makes it; the split products of those calls therefore use bfloat16 pieces (otp_bf16_pieces in csrc/densex.hip, transformer.hip:
     16-17 bits at any magnitude), not the IEEE-half pieces of the forward, which flush 1e-8 to zero and hold 1e-5 to 8 bits."""
     from otpose_amd import ops
     from otpose_amd import train_ops as T
@@ -307,7 +308,7 @@ def test_gradient_operands_of_any_magnitude_keep_their_precision(mag):
     ref = torch.einsum("oi,nohw->nihw", w.view(c, c).double(), gy.cpu().double())
     err = float((gx.cpu().double() - ref).abs().max()) / float(ref.abs().max())
     assert err <= 3e-5, err
-    # what the forward's half pieces would make of the same operand (why the second copy of the kernels exists)
+    # what the forward's half pieces would make of the same operand (why the bfloat16 instances of the kernels exist)
     pk = ops.pack_dense_cc(w.view(c, c).t().contiguous().cuda(), x3=True)
     half = ops.dense_cc([gy.view(2, c, t)], [pk], x3=True)[0]
     err_half = float((half.cpu().double().view_as(ref) - ref).abs().max()) / float(ref.abs().max())
@@ -325,3 +326,32 @@ def test_gradient_operands_of_any_magnitude_keep_their_precision(mag):
     for a, b in zip(leaves, refs):
         e = float((a.grad.cpu().double() - b.grad).abs().max()) / float(b.grad.abs().max())
         assert e <= 2e-4, e
+
+
+@pytest.mark.parametrize("mag", [1.0, 1e-8])
+def test_gradient_projection_at_204_channels(mag):
+    """The bfloat16-piece projection at C = 204 (the 7-frame window): densex_cc_kernel<otp_bf16_pieces, 204, false>, which the
+    training tests above (C = 136) do not launch.  Two token tiles, the second with two live tokens; same bound as at 136
+    channels (the library before the kernels became templates measured 3.9e-6 and 5.9e-6, profiles/r13_x3_pieces.txt)."""
+    from otpose_amd import ops
+    c, t = 204, 130
+    w = seeded((c, c), 5) / math.sqrt(c)
+    x = (seeded((2, c, t), 6) * mag).cuda()
+    pk = ops.pack_dense_cc(w.cuda(), x3=True, grad=True)
+    out = ops.dense_cc([x], [pk], x3=True, grad=True)[0]
+    ref = torch.einsum("oi,bit->bot", w.double(), x.cpu().double())
+    err = float((out.cpu().double() - ref).abs().max()) / float(ref.abs().max())
+    print("C = 204 bf16-piece projection, magnitude %g: error %.3e of the largest reference value" % (mag, err))
+    assert err <= 3e-5, err
+
+
+def test_chan_attn_backward_with_split_products_off():
+    """otp_chan_attn_set_split(0): the _bf16p entries of the backward launch the fp32 kernels, the one copy that also serves
+    the forward's entries."""
+    from otpose_amd import hip
+    previous = 0 if os.environ.get("OTPOSE_CONV_MATH", "x3") == "f32" else 1      # what otpose_amd/hip.py set at load
+    hip.lib().otp_chan_attn_set_split(0)
+    try:
+        test_chan_attn_backward(34, 2, 70)
+    finally:
+        hip.lib().otp_chan_attn_set_split(previous)

@@ -413,6 +413,21 @@ int otp_dwconv_ln3(const void* x, const void* dwq, const void* dwk, const void* 
 size_t otp_chan_attn_workspace(int B, int C, int T, int n_head);
 int otp_chan_attn(const void* q, const void* k, const void* v, void* out, void* workspace, size_t workspace_bytes,
                   int B, int C, int T, int n_head, float scale, void* stream);
+/* local-window attention of LocalMaskedMHCA (blocks.py:479-833; csrc/localattn.hip): w = window / 2, per (b, head) and token t
+ *   S[t][j] = scale * sum_c q[c][t] k[c][t+j-w] (+ rel_pe[head][j]),  j = 0 .. 2w, positions outside [0, T) take no part,
+ *   P = softmax_j(S),  out[c][t] = sum_j P[t][j] v[c][t+j-w]           (out in the natural (B, C, T) layout)
+ * as one launch in exact fp32.  rel_pe (n_head x window) may be NULL; a non-NULL probs (B*n_head, T, window) also receives P
+ * (zero at the positions outside the sequence) for the backward.  Supported (otp_local_attn_supported: 1 / 0): odd window
+ * 5 .. 33, T % (window - 1) == 0 (the reference's own assertion), any head size; anything else is OTP_ERR_BAD_ARG.
+ * The backward is deterministic and atomic-free: gq, gk, gv (B, C, T), grel (n_head x window, may be NULL) = sum of dS over
+ * b and t in a fixed order; ws holds dS and the per-workgroup partial sums for grel. */
+int otp_local_attn_supported(int hs, int t, int window);
+int otp_local_attn(const void* q, const void* k, const void* v, const void* rel_pe, void* out, void* probs, int B, int C, int T,
+                   int n_head, int window, float scale, void* stream);
+size_t otp_local_attn_backward_workspace(int B, int C, int T, int n_head, int window);
+int otp_local_attn_backward(const void* q, const void* k, const void* v, const void* probs, const void* gout, void* gq, void* gk,
+                            void* gv, void* grel, void* ws, size_t ws_bytes, int B, int C, int T, int n_head, int window,
+                            float scale, void* stream);
 /* nn.Upsample(scale_factor=f, mode='linear', align_corners=False) on (B,C,T) -> out (B, out_ctot, T*f) at
  * channel offset out_coff (f = 1 copies) (ConvVideoTransformer.py:108,179; OTPose.py:362-369) */
 int otp_upsample_linear(const void* x, void* out, int B, int C, int T, int f, int out_ctot, int out_coff, void* stream);

@@ -10,6 +10,10 @@ Only the keys the hot path reads are given defaults ("Confi
 ``MODEL.{NUM_JOINTS,HEATMAP_SIZE,IMAGE_SIZE,PRETRAINED,FREEZE_HRNET_WEIGHTS,DEFORMABLE_CONV.*,
 DEFORMABLE_CONV_CH,OFFSET_MASK_COMBINE_CONV,EXTRA.*}`` and ``LOSS.{NAME,USE_TARGET_WEIGHT}``.
 Values follow reference configs/Base_PoseTrack17.yaml:36-88 and configs/17/model_RSN.yaml:28-40.
+
+Extension keys read with a default when absent (``otpose_amd.model.OTPose``): ``MODEL.WINDOW_FRAMES``, ``MODEL.DTYPE`` and the
+local attention windows ``MODEL.MHA_WIN_SIZE`` (int or per-level list, -1 = off), ``MODEL.USE_REL_PE`` (False) for the two temporal
+encoders and ``MODEL.FLOW_MHA_WIN_SIZE`` (-1) for the flow encoder.
 """
 from __future__ import annotations
 

@@ -929,7 +929,7 @@ class InferenceEngine:
             self._keep += [fp, bp]
             q, k, v, att, out = (self.new(B, C, T) for _ in range(5))
             self.call(L.otp_flow_front, "otp_flow_front", *ops.flow_front_args(x, fp, q, k, v, blk.ln1.eps))
-            self.chan_attn(q, k, v, att, a)
+            self.attention(q, k, v, att, a)
             self.call(L.otp_flow_back, "otp_flow_back", *ops.flow_back_args(x, att, bp, out, blk.mlp[0].out_channels, blk.ln2.eps))
             return out
         ln1 = self.new(B, C, T)
@@ -970,7 +970,7 @@ class InferenceEngine:
                 self.conv(self.v3(kn), a.key.weight, self.v3(k), bias=a.key.bias)
                 self.conv(self.v3(vn), a.value.weight, self.v3(v), bias=a.value.bias)
         att = self.new(B, C, To)
-        self.chan_attn(q, k, v, att, a)
+        self.attention(q, k, v, att, a)
         # y = pool_skip(x) + scale_attn * (proj(att) + b)   (eval: dropout / drop-path are identities)
         sa = blk.drop_path_attn.scale.detach().reshape(-1)
         y = self.new(B, C, To)
@@ -1007,6 +1007,20 @@ class InferenceEngine:
         self.conv(self.v3(hdn), blk.mlp[3].weight, self.v3(out), scale=sm,
                   shift=blk.mlp[3].bias.detach() * sm.to(blk.mlp[3].bias.device), res=self.v3(y))
         return out
+
+    def attention(self, q, k, v, att, a):
+        """The attention product of attention module ``a`` as one launch: the local window of a LocalMaskedMHCA
+        (csrc/localattn.hip; ``att`` in the natural layout), else the channel attention.  q, k, v are fp32 in both engines."""
+        if getattr(a, "window_size", 0) > 1:
+            B, C, T = q.shape
+            ops.check_local_attn(C, T, a.n_head, a.window_size)
+            rel = ops._rel_pe_table(getattr(a, "rel_pe", None), a.n_head, a.window_size, q)
+            if rel is not None:
+                self._keep.append(rel)
+            self.call(self.lib.otp_local_attn, "otp_local_attn",
+                      *ops.local_attn_args(q, k, v, rel, att, None, a.n_head, a.window_size, a.scale))
+        else:
+            self.chan_attn(q, k, v, att, a)
 
     def chan_attn(self, q, k, v, att, a):
         """Channel attention of a MaskedMHCA ``a`` (csrc/attn.hip) with its workspace."""

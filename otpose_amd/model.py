@@ -131,10 +131,16 @@ class OTPose(nn.Module):
         self.scale_arch, self.flow_scale_arch = (0, 6, 2), (0, 6, 0)
         tkw = dict(n_embd_ks=3, max_len=self.num_patches, h=self.pe_h, proj_pdrop=0.1, path_pdrop=0.1)
         d = self.temporal_encoding_dim
-        self.temporal_encoder1 = ConvTransformer(d, d, n_head=2, arch=self.scale_arch, **tkw)
-        self.temporal_encoder2 = ConvTransformer(d, d, n_head=2, arch=self.scale_arch, **tkw)
+        # extension keys (the reference's OTPose.py:209-216 builds its encoders without a window): MODEL.MHA_WIN_SIZE / MODEL.USE_REL_PE
+        # for the two temporal encoders, MODEL.FLOW_MHA_WIN_SIZE for the flow encoder; absent or <= 1 = channel attention
+        get = m.get if hasattr(m, "get") else (lambda k, dflt: getattr(m, k, dflt))
+        rel = bool(get("USE_REL_PE", False))
+        win = self._local_windows(get("MHA_WIN_SIZE", -1), self.scale_arch, "MODEL.MHA_WIN_SIZE")
+        fwin = self._local_windows(get("FLOW_MHA_WIN_SIZE", -1), self.flow_scale_arch, "MODEL.FLOW_MHA_WIN_SIZE")
+        self.temporal_encoder1 = ConvTransformer(d, d, n_head=2, arch=self.scale_arch, **tkw, **self._local_kw(win, rel))
+        self.temporal_encoder2 = ConvTransformer(d, d, n_head=2, arch=self.scale_arch, **tkw, **self._local_kw(win, rel))
         self.flow_encoder = ConvTransformer(self.patch_dim, self.patch_dim, n_head=1,
-                                            arch=self.flow_scale_arch, **tkw)
+                                            arch=self.flow_scale_arch, **tkw, **self._local_kw(fwin, False))
 
         self.deformable_conv_dilations = list(m.DEFORMABLE_CONV.DILATION)
         self.deformable_aggregation_type = m.DEFORMABLE_CONV.AGGREGATION_TYPE
@@ -160,6 +166,31 @@ class OTPose(nn.Module):
         # the next forward (bench.py's timed loop)
         self.alias_outputs = False
         self.init_weights()
+
+    def _local_windows(self, value, arch, key):
+        """The per-level local attention windows of an encoder of ``arch`` from cfg value ``value`` (an int for every level, or a
+        sequence: [0] the stem, [1 + i] branch i), validated against the token count of every level - T, T/2, T/4 of the
+        configured heat-map.  None when every level keeps the channel attention."""
+        from .modules import check_local_length, check_local_window
+        levels = arch[2] + 1
+        sizes = list(value) if isinstance(value, (list, tuple)) else [value] * levels
+        if len(sizes) < levels:
+            raise ValueError(f"{key} needs {levels} entries (stem + {arch[2]} branch levels), got {sizes}")
+        sizes = sizes[:levels]
+        if all(s <= 1 for s in sizes):
+            return None
+        for i, s in enumerate(sizes):
+            if s > 1:
+                t = self.num_patches // 2 ** i
+                check_local_window(s, f"{key}[{i}]")
+                check_local_length(t if self.num_patches % 2 ** i == 0 else 0, s,
+                                   f"{key}[{i}]: level {i} of the {self.pe_w}x{self.pe_h} heat-map: sequence length")
+        return sizes
+
+    @staticmethod
+    def _local_kw(windows, use_rel_pe):
+        """ConvTransformer keyword arguments of :meth:`_local_windows`' result (none at the defaults)."""
+        return {} if windows is None else {"mha_win_size": windows, "use_rel_pe": use_rel_pe}
 
     # ---- initialisation (reference model/OTPose.py:431-503) ---------------------------------
     def init_weights(self):

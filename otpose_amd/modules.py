@@ -253,19 +253,62 @@ class MaskedMHCA(_Container):
         self.proj = nn.Conv1d(n_embd, n_embd, 1)
 
 
+LOCAL_WINDOW_MIN, LOCAL_WINDOW_MAX = 5, 33          # the windows csrc/localattn.hip is built for (w = window // 2 = 2 .. 16)
+
+
+def check_local_window(window_size, what="window_size"):
+    """Raise ``ValueError`` unless ``window_size`` is one the local attention supports: odd, 5 .. 33.  (The reference's own
+    chunking fails at 3 - blocks.py:710 slices an empty range - and with an even size its ``rel_pe`` no longer matches the
+    band.)"""
+    if not isinstance(window_size, (int, np.integer)) or isinstance(window_size, bool):
+        raise ValueError(f"{what} must be an int, got {window_size!r}")
+    if window_size % 2 == 0 or not LOCAL_WINDOW_MIN <= window_size <= LOCAL_WINDOW_MAX:
+        raise ValueError(f"{what} must be odd and in [{LOCAL_WINDOW_MIN}, {LOCAL_WINDOW_MAX}], got {window_size}")
+
+
+def check_local_length(t, window_size, what="sequence length"):
+    """Raise ``ValueError`` unless ``t`` tokens divide into the reference's chunks of ``2 * (window_size // 2)``
+    (blocks.py:667)."""
+    if t <= 0 or t % (window_size - 1):
+        raise ValueError(f"{what} {t} is not a multiple of {window_size - 1} (local attention window {window_size})")
+
+
+class LocalMaskedMHCA(MaskedMHCA):
+    """Depthwise-conv + local-window attention parameters (reference model/blocks.py:479-583): the front end and the
+    projection of :class:`MaskedMHCA` under the same names, plus ``rel_pe`` (1, 1, n_head, window_size) when ``use_rel_pe``.
+    Every token attends to the ``window_size`` positions centred on it (csrc/localattn.hip)."""
+
+    def __init__(self, n_embd, n_head, window_size, n_qx_stride=1, n_kv_stride=1, attn_pdrop=0.0, proj_pdrop=0.0,
+                 use_rel_pe=False):
+        check_local_window(window_size)
+        super().__init__(n_embd, n_head, n_qx_stride, n_kv_stride, attn_pdrop, proj_pdrop)
+        self.window_size = int(window_size)
+        self.window_overlap = self.window_size // 2
+        self.use_rel_pe = bool(use_rel_pe)
+        if self.use_rel_pe:
+            self.rel_pe = nn.Parameter(torch.zeros(1, 1, n_head, self.window_size))
+            std = (2.0 / n_embd) ** 0.5
+            nn.init.trunc_normal_(self.rel_pe, std=std, a=-2 * std, b=2 * std)
+
+
 class _Marker(_Container):
     """Parameter-free slot (GELU / Dropout positions inside the reference's mlp Sequential)."""
 
 
 class TransformerBlock(_Container):
-    """reference model/blocks.py:191-262"""
+    """reference model/blocks.py:191-262; ``mha_win_size > 1`` selects :class:`LocalMaskedMHCA` (blocks.py:212-231)."""
 
-    def __init__(self, n_embd, n_head, n_ds_strides=(1, 1), attn_pdrop=0.0, proj_pdrop=0.0, path_pdrop=0.0):
+    def __init__(self, n_embd, n_head, n_ds_strides=(1, 1), attn_pdrop=0.0, proj_pdrop=0.0, path_pdrop=0.0,
+                 mha_win_size=-1, use_rel_pe=False):
         super().__init__()
         self.stride = n_ds_strides[0]
         self.ln1 = LayerNorm(n_embd)
         self.ln2 = LayerNorm(n_embd)
-        self.attn = MaskedMHCA(n_embd, n_head, n_ds_strides[0], n_ds_strides[1], attn_pdrop, proj_pdrop)
+        if mha_win_size > 1:
+            self.attn = LocalMaskedMHCA(n_embd, n_head, mha_win_size, n_ds_strides[0], n_ds_strides[1], attn_pdrop, proj_pdrop,
+                                        use_rel_pe)
+        else:
+            self.attn = MaskedMHCA(n_embd, n_head, n_ds_strides[0], n_ds_strides[1], attn_pdrop, proj_pdrop)
         self.pool_skip = _Marker()
         self.mlp = nn.Sequential(nn.Conv1d(n_embd, 4 * n_embd, 1), _Marker(), _Marker(),
                                  nn.Conv1d(4 * n_embd, n_embd, 1), _Marker())
@@ -291,18 +334,28 @@ class ConvTransformer(_Container):
     """reference model/ConvVideoTransformer.py:21-111 (arch[0] == 0: no conv embedding is built)."""
 
     def __init__(self, n_in, n_embd, n_head, n_embd_ks, max_len, arch, h=72, scale_factor=2,
-                 attn_pdrop=0.0, proj_pdrop=0.0, path_pdrop=0.0):
+                 attn_pdrop=0.0, proj_pdrop=0.0, path_pdrop=0.0, mha_win_size=-1, use_rel_pe=False):
         super().__init__()
         assert len(arch) == 3 and arch[0] == 0, "conv embedding (arch[0] > 0) is unused by OTPose"
         self.arch, self.max_len, self.n_embd, self.n_head = tuple(arch), max_len, n_embd, n_head
         self.scale_factor = scale_factor
+        # local attention window per pyramid level: [0] the stem, [1 + i] branch i (ConvVideoTransformer.py:29,48-49,89,104);
+        # entries <= 1 mean channel attention
+        if isinstance(mha_win_size, (int, np.integer)):
+            mha_win_size = [int(mha_win_size)] * (arch[2] + 1)
+        self.mha_win_size = [int(s) for s in mha_win_size]
+        if len(self.mha_win_size) < arch[2] + 1:
+            raise ValueError(f"mha_win_size needs {arch[2] + 1} entries (stem + {arch[2]} branch levels), got {self.mha_win_size}")
+        self.use_rel_pe = bool(use_rel_pe)
         self.register_buffer("pos_embd", sinusoid_table(max_len, n_embd) / (n_embd ** 0.5))
         self.embd = nn.ModuleList()
         self.embd_norm = nn.ModuleList()
-        kw = dict(attn_pdrop=attn_pdrop, proj_pdrop=proj_pdrop, path_pdrop=path_pdrop)
-        self.stem = nn.ModuleList([TransformerBlock(n_embd, n_head, (1, 1), **kw) for _ in range(arch[1])])
+        kw = dict(attn_pdrop=attn_pdrop, proj_pdrop=proj_pdrop, path_pdrop=path_pdrop, use_rel_pe=use_rel_pe)
+        self.stem = nn.ModuleList([TransformerBlock(n_embd, n_head, (1, 1), mha_win_size=self.mha_win_size[0], **kw)
+                                   for _ in range(arch[1])])
         self.branch = nn.ModuleList(
-            [TransformerBlock(n_embd, n_head, (scale_factor, scale_factor), **kw) for _ in range(arch[2])])
+            [TransformerBlock(n_embd, n_head, (scale_factor, scale_factor), mha_win_size=self.mha_win_size[1 + i], **kw)
+             for i in range(arch[2])])
         self.upsample = nn.ModuleList([_Marker() for _ in range(arch[2])])
 
 

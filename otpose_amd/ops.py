@@ -1185,6 +1185,46 @@ def chan_attn(q, k, v, n_head, scale):
     return out
 
 
+def check_local_attn(c, t, n_head, window_size):
+    """Raise ``ValueError`` for a shape the local attention does not take (odd window 5 .. 33, ``t % (window_size - 1) == 0``:
+    ``otp_local_attn_supported``)."""
+    if n_head <= 0 or c % n_head:
+        raise ValueError(f"local_attn: {c} channels do not split into {n_head} heads")
+    if not hip.lib().otp_local_attn_supported(c // n_head, t, int(window_size)):
+        raise ValueError(f"local_attn: window_size must be odd and in [5, 33] and the {t} tokens a multiple of window_size - 1, "
+                         f"got window_size {window_size}")
+
+
+def local_attn_args(q, k, v, rel_pe, out, probs, n_head, window_size, scale):
+    b, c, t = q.shape
+    return (hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(rel_pe), hip.ptr(out), hip.ptr(probs), b, c, t, n_head, int(window_size),
+            scale)
+
+
+def _rel_pe_table(rel_pe, n_head, window_size, like):
+    """``rel_pe`` ((1, 1, n_head, window_size) parameter or None) as the contiguous fp32 (n_head, window_size) table."""
+    if rel_pe is None:
+        return None
+    if rel_pe.numel() != n_head * window_size:
+        raise ValueError(f"local_attn: rel_pe has {rel_pe.numel()} entries, n_head * window_size is {n_head * window_size}")
+    return rel_pe.detach().to(like.device, torch.float32).reshape(n_head, window_size).contiguous()
+
+
+def local_attn(q, k, v, n_head, window_size, scale, rel_pe=None):
+    """Local-window attention of LocalMaskedMHCA (model/blocks.py:479-833) on q, k, v (B, C, T): every token attends to the
+    ``window_size`` positions centred on it, positions outside the sequence take no part; ``rel_pe`` (1, 1, n_head, window_size)
+    is added to the scaled scores.  Returns (B, C, T) in the natural layout (csrc/localattn.hip, one launch)."""
+    _require_gpu(q, k, v)
+    _check_f32(q, k, v)
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    b, c, t = q.shape
+    check_local_attn(c, t, n_head, window_size)
+    rel = _rel_pe_table(rel_pe, n_head, window_size, q)
+    out = torch.empty_like(q)
+    _launch(hip.lib().otp_local_attn, "otp_local_attn", local_attn_args(q, k, v, rel, out, None, n_head, window_size, scale), q)
+    return out
+
+
 def upsample_linear_args(x, out, f, out_coff=0):
     """``x`` (B, C, T) or (B, C, H, W) with T = H * W, written to channels [out_coff, out_coff + C) of ``out``."""
     b, c = x.shape[:2]

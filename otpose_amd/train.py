@@ -369,8 +369,19 @@ class TrainGraph:
                 return self.conv1d(f"{p}.{name}", y)
 
             q, k, v = (branch(n) for n in names)
-        out = T.chan_attn(q, k, v, n_head, 1.0 / math.sqrt(hs))          # attn_pdrop is 0 in OTPose.py:209-216
+        out = self.attention(p, q, k, v, n_head, 1.0 / math.sqrt(hs))
         return self.dropout(self.conv1d(p + ".proj", out), self.mods[p].proj_pdrop)
+
+    def attention(self, p, q, k, v, n_head, scale):
+        """The attention product of module ``p``: the local window of a LocalMaskedMHCA (blocks.py:655-833), else the channel
+        attention (blocks.py:427-447).  No dropout on the attention map: attn_pdrop is 0 in OTPose.py:209-216."""
+        a = self.mods[p]
+        window = getattr(a, "window_size", 0)
+        if window > 1:
+            if self.stochastic and a.attn_pdrop > 0.0:
+                raise NotImplementedError(f"{p}: attn_pdrop = {a.attn_pdrop} > 0 is not implemented in the training graph")
+            return T.local_attn(q, k, v, n_head, window, scale, self.P.get(p + ".rel_pe"))
+        return T.chan_attn(q, k, v, n_head, scale)
 
     def dropout(self, x, rate):
         if self.stochastic and rate > 0.0:

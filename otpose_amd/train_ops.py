@@ -585,6 +585,53 @@ def chan_attn(q, k, v, n_head, scale):
     return ChanAttnFunction.apply(q, k, v, n_head, scale)
 
 
+class LocalAttnFunction(Function):
+    """Local-window attention of model/blocks.py:479-833 (``ops.local_attn``): the forward also writes the softmax band P
+    (B n_head, T, window) and keeps it with q, k, v; the backward is ``otp_local_attn_backward`` (two gather-form launches and a
+    fixed-order fold for ``rel_pe``: deterministic, no atomics)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rel_pe, n_head, window_size, scale):
+        _require_gpu(q, k, v)
+        _check_f32(q, k, v)
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        b, c, t = q.shape
+        ops.check_local_attn(c, t, n_head, window_size)
+        rel = ops._rel_pe_table(rel_pe, n_head, window_size, q)
+        out = torch.empty_like(q)
+        probs = torch.empty((b * n_head, t, window_size), dtype=torch.float32, device=q.device)
+        hip.check(hip.lib().otp_local_attn(*ops.local_attn_args(q, k, v, rel, out, probs, n_head, window_size, scale),
+                                           hip.stream_of(q)), "otp_local_attn")
+        ctx.save_for_backward(q, k, v, probs)
+        ctx.cfg = (n_head, int(window_size), scale)
+        ctx.params = (rel_pe,)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        q, k, v, probs = ctx.saved_tensors
+        n_head, window, scale = ctx.cfg
+        rel_pe = ctx.params[0]
+        b, c, t = q.shape
+        L = hip.lib()
+        gout = gout.contiguous()
+        gq, gk, gv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+        grel = None
+        if rel_pe is not None and ctx.needs_input_grad[3]:
+            slot = grad_slot(rel_pe)
+            grel = slot if slot is not None else torch.empty(rel_pe.shape, dtype=torch.float32, device=q.device)
+        nbytes = L.otp_local_attn_backward_workspace(b, c, t, n_head, window)
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
+        hip.check(L.otp_local_attn_backward(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(probs), hip.ptr(gout), hip.ptr(gq),
+                                            hip.ptr(gk), hip.ptr(gv), hip.ptr(grel), hip.ptr(ws), nbytes, b, c, t, n_head, window,
+                                            scale, hip.stream_of(q)), "otp_local_attn_backward")
+        return gq, gk, gv, grel, None, None, None
+
+
+def local_attn(q, k, v, n_head, window_size, scale, rel_pe=None):
+    return LocalAttnFunction.apply(q, k, v, rel_pe, n_head, window_size, scale)
+
+
 class ScaleResidualFunction(Function):
     """``x + drop_path(scale * a)`` of a TransformerBlock (model/blocks.py:277-279, AffineDropPath :283-316): ``scale`` is the
     (1, C, 1) AffineDropPath parameter, ``mask`` (B,) the per-sample Bernoulli(keep) / keep factors (None: no drop-path)."""

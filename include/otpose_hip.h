@@ -1051,6 +1051,51 @@ int otp_seg_softnms(const void* segs, const void* scores, const void* offsets, i
 int otp_seg_voting(const void* nms_segs, const void* nms_offsets, const void* segs, const void* scores, const void* offsets,
                    int G, int K, int N, float voting_thresh, void* out, void* stream);
 
+/* ---- Temporal detection AP: compute_average_precision_detection, segment_iou and interpolated_prec_rec of the reference's
+ * thirdparty/utils/metrics.py (csrc/segap.hip; the drop-in names are in otpose_amd/segmetrics.py).  All
+ * segments, thresholds and results are float64 and every difference, sum and quotient is rounded on its own, as numpy rounds
+ * them.  No allocation, no synchronisation, no atomics: graph-capturable, and the same input gives the same bytes.
+ *
+ * otp_seg_ap_match: the greedy assignment.  G groups, one per (video, class) pair: group g holds the predictions
+ * pred_offsets[g] .. pred_offsets[g + 1] of pred_seg (N, 2) rows (t0, t1), ALREADY in descending-score order inside the group,
+ * and the ground truths gt_offsets[g] .. gt_offsets[g + 1] of gt_seg (M, 2) rows (c0, c1); both offset tables (G+1) int32,
+ * ascending; either side of a group may be empty.  thresholds: T doubles in HOST memory, passed on by value.
+ *   tIoU           inter = max(min(t1, c1) - max(t0, c0), 0), union = (c1 - c0) + (t1 - t0) - inter, tIoU = inter / union
+ *                  (segment_iou, metrics.py:285-309); min / max hand a NaN operand on, as numpy's do.
+ *   per threshold  the group's predictions in order: of the ground truths not yet locked at this threshold, those with
+ *                  tIoU < thr false (so a NaN tIoU - 0 / 0 of two zero-length segments - qualifies, as in the reference's loop);
+ *                  among them the highest tIoU, a NaN above every number (numpy's argsort()[::-1] puts it first), exactly equal
+ *                  values by the lower row (the reference leaves these to its sort).  That ground truth is the match and is
+ *                  locked; a prediction without one is a false positive.
+ *   output         match (T, N) int32: the matched ground truth's row relative to gt_offsets[g], or -1.  -1 also for every row
+ *                  of a group without ground truth, of a group whose offsets do not describe a range inside [0, N] / [0, M]
+ *                  (nothing of it is read) and of no group at all.
+ * One workgroup per group; wave w of it owns thresholds w, w + 4, ...; a group of up to OTP_SEG_AP_LDS_GT ground truths stages
+ * them in LDS and keeps its locks in registers, a larger one reads them from memory and keeps its locks in its own rows of the
+ * workspace (otp_seg_ap_match_workspace(G, M, T) bytes of device memory, contents irrelevant).  There is no limit on a group's
+ * size.  T <= OTP_SEG_AP_MAX_THRESHOLDS.
+ *
+ * otp_seg_ap: interpolated AP (VOC 2011) of C classes at T thresholds from such a table.  order (N) int32: the rows of match
+ * in class-major order, descending score inside a class; class_offsets (C+1) int32 over order; npos (C) int32: the ground
+ * truths of each class.  Position i of a class is a true positive when match[t][order[i]] >= 0; with k_i true positives up to
+ * and including i, precision_i = k_i / (i + 1) and
+ *   ap[t][c] = sum over the true positives i of (k_i / npos - (k_i - 1) / npos) * max_{j >= i} precision_j,
+ * which is metrics.py:273-282 and 312-321 term by term (recall changes exactly at the true positives; the reference's closing
+ * term has the precision 0).  The terms are added in a fixed order that is not numpy's: per thread over the chunks of 256
+ * positions from the last to the first, a butterfly over the 64 lanes, then the four waves.  ap (T, C) float64; a class without
+ * predictions, with npos <= 0 or with offsets outside [0, N] gets 0; an entry of order outside [0, N) counts as a false positive.
+ *
+ * -1 for null pointers, G, T, C, N or M <= 0, or a NaN threshold; OTP_ERR_UNSUPPORTED for T above the maximum, or N / M >= 2^28;
+ * OTP_ERR_WORKSPACE for a short workspace. */
+#define OTP_SEG_AP_LDS_GT 1024
+#define OTP_SEG_AP_MAX_THRESHOLDS 32
+size_t otp_seg_ap_match_workspace(int G, int M, int T);
+int otp_seg_ap_match(const void* pred_seg, const void* pred_offsets, const void* gt_seg, const void* gt_offsets,
+                     const double* thresholds, int G, int N, int M, int T, void* workspace, size_t workspace_bytes, void* match,
+                     void* stream);
+int otp_seg_ap(const void* match, const void* order, const void* class_offsets, const void* npos, int C, int T, int N, void* ap,
+               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

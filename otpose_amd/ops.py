@@ -2169,3 +2169,66 @@ def seg_voting_groups(nms_segs, nms_offsets, segs, scores, offsets, voting_thres
                 (hip.ptr(nms_segs), hip.ptr(nms_offsets), hip.ptr(segs), hip.ptr(scores), hip.ptr(offsets),
                  offsets.shape[0] - 1, k, segs.shape[0], float(voting_thresh), hip.ptr(out)), segs)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# temporal detection AP (csrc/segap.hip; the reference's thirdparty/utils/metrics.py); the drop-in names are in segmetrics.py
+# ------------------------------------------------------------------------------------------------
+def _check_i32(what, t, min_len):
+    if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] < min_len:
+        raise ValueError(f"{what} must be a 1-D int32 tensor of at least {min_len} entries")
+    return t.contiguous()
+
+
+def seg_ap_match(pred_seg, pred_offsets, gt_seg, gt_offsets, thresholds, workspace=None):
+    """The greedy assignment of ``compute_average_precision_detection`` (metrics.py:243-271) for every (video, class) group
+    and every tIoU threshold in one launch.  Group g is rows ``pred_offsets[g] .. pred_offsets[g + 1]`` of ``pred_seg`` (N, 2)
+    float64, already in descending-score order inside the group, and rows ``gt_offsets[g] .. gt_offsets[g + 1]`` of ``gt_seg``
+    (M, 2) float64.  ``thresholds``: up to ``OTP_SEG_AP_MAX_THRESHOLDS`` host floats.  Returns the device tensor ``match``
+    (T, N) int32: the matched ground truth's row relative to the group's first, or -1 for a false positive."""
+    _require_gpu(pred_seg, pred_offsets, gt_seg, gt_offsets)
+    for what, t in (("pred_seg", pred_seg), ("gt_seg", gt_seg)):
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 2:
+            raise ValueError(f"{what} must be an (n, 2) float64 tensor, got {tuple(t.shape)} {t.dtype}")
+    pred_offsets, gt_offsets = _check_i32("pred_offsets", pred_offsets, 2), _check_i32("gt_offsets", gt_offsets, 2)
+    if pred_offsets.shape != gt_offsets.shape:
+        raise ValueError("pred_offsets and gt_offsets must describe the same G groups")
+    thr = [float(v) for v in thresholds]
+    t, n, m, g, dev = len(thr), pred_seg.shape[0], gt_seg.shape[0], pred_offsets.shape[0] - 1, pred_seg.device
+    if not 1 <= t <= _K["OTP_SEG_AP_MAX_THRESHOLDS"]:
+        raise ValueError(f"1 .. {_K['OTP_SEG_AP_MAX_THRESHOLDS']} thresholds, got {t}")
+    if n == 0 or m == 0:                              # nothing to match: every prediction is a false positive
+        return torch.full((t, n), -1, dtype=torch.int32, device=dev)
+    need = hip.lib().otp_seg_ap_match_workspace(g, m, t)
+    if workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.int32, device=dev)
+    match = torch.empty((t, n), dtype=torch.int32, device=dev)
+    pred_seg, gt_seg = pred_seg.contiguous(), gt_seg.contiguous()
+    _launch(hip.lib().otp_seg_ap_match, "otp_seg_ap_match",
+            (hip.ptr(pred_seg), hip.ptr(pred_offsets), hip.ptr(gt_seg), hip.ptr(gt_offsets),
+             (ctypes.c_double * t)(*thr), g, n, m, t, hip.ptr(workspace), workspace.numel() * workspace.element_size(),
+             hip.ptr(match)), pred_seg)
+    return match
+
+
+def seg_ap(match, order, class_offsets, npos):
+    """Interpolated AP (metrics.py:273-282, 312-321) of every (threshold, class) from ``match`` (T, N) int32 of
+    :func:`seg_ap_match`.  ``order`` (N) int32: the rows of ``match`` in class-major order, descending score inside a class;
+    ``class_offsets`` (C+1) int32 over ``order``; ``npos`` (C) int32: the ground truths of each class.  Returns ``ap`` (T, C)
+    float64 on the device; a class without predictions gets 0."""
+    _require_gpu(match, order, class_offsets, npos)
+    if match.dtype != torch.int32 or match.dim() != 2:
+        raise ValueError("match must be a (T, N) int32 tensor")
+    t, n = match.shape
+    order, class_offsets = _check_i32("order", order, 0), _check_i32("class_offsets", class_offsets, 2)
+    c = class_offsets.shape[0] - 1
+    npos = _check_i32("npos", npos, c)
+    if order.shape[0] != n or npos.shape[0] != c or not 1 <= t <= _K["OTP_SEG_AP_MAX_THRESHOLDS"]:
+        raise ValueError(f"order must have N = {n} entries, npos C = {c}, and T must be 1 .. {_K['OTP_SEG_AP_MAX_THRESHOLDS']}")
+    if n == 0:
+        return torch.zeros((t, c), dtype=torch.float64, device=match.device)
+    ap = torch.empty((t, c), dtype=torch.float64, device=match.device)
+    match = match.contiguous()
+    _launch(hip.lib().otp_seg_ap, "otp_seg_ap",
+            (hip.ptr(match), hip.ptr(order), hip.ptr(class_offsets), hip.ptr(npos), c, t, n, hip.ptr(ap)), match)
+    return ap

@@ -743,6 +743,34 @@ int otp_crop_clips_blur_u8(const void* pool_u8, int S, int Hp, int Wp, const voi
 int otp_crop_clips_pair_u8(const void* pool_u8, int S, int Hp, int Wp, const void* frame_idx, const void* M, void* out,
                            int B, int F, int H, int W, float mean_r, float mean_g, float mean_b, float std_r, float std_g,
                            float std_b, void* stream);
+/* ---- crop plan of the video path on the device (otpose_amd/crop.py: box_to_center_scale, crop_matrix at rotation 0, window
+ * with distance 2; the host functions are the specification) -------------------------------------------------------------
+ * The detector's output - boxes (S, K, 4) float64 x, y, w, h, scores (S, K) float32, counts (S) int32 - becomes dense rows
+ * in (frame, box) order.  A box is kept when its slot s is in [detect_lo, detect_hi), k < counts[s] (clamped to [0, K]) and
+ * its score, widened to double, is not below min_score.  frame_number (S) int32 is each pool slot's frame number as in the
+ * file name, num_frames (S) int32 the length of its sequence; a sequence is a run of slots with one num_frames and strictly
+ * increasing frame numbers, and a frame "is in the pool" when a slot of the person's sequence at most two slots away holds it.
+ * Rows [0, min(total, max_persons)):
+ *   center, scale (P, 2) float32   box_to_center_scale(box, aspect_ratio, enlarge) on float64 boxes, bit for bit (every
+ *                                  product, sum and quotient rounded on its own; center x == -1 is not enlarged)
+ *   M (P, 2, 3) float64            crop_matrix(center, scale, 0, (out_w, out_h)): the three point pairs in float32 as there,
+ *                                  then a = (u2 - u0) / (x2 - cx), d = (v0 - v1) / (cy - y1), b = c = 0, tx = u0 - a cx,
+ *                                  ty = v0 - d cy in float64 (the closed form of the 6 x 6 solve; last bits may differ from it)
+ *   frame_idx (P, 5) int32         pool slots of cur, prev, next, pprev, nnext; prev / next fall back to the current slot
+ *                                  (margin 0) when not in the pool, pprev / nnext become -1 (an empty frame for the crops)
+ *   margin (P, 4) float32          left, right, lleft, rright of crop.window (nnext is the same frame as next)
+ *   box_score (P) float64, person_slot (P) int32: the box's score and pool slot
+ * Rows [min(total, max_persons), max_persons) are padding: center = scale = margin = box_score = 0, M the identity,
+ * frame_idx = person_slot = -1.  pr_off (S + 1) int32: min(persons kept before frame s, max_persons), the CSR offsets of the
+ * rows; total (1) int32: persons kept, NOT capped.  posetrack18 != 0: frame numbers from 0, else from 1.  One launch of one
+ * workgroup, no allocation, no synchronisation.  A degenerate box (zero width and height) gives a non-finite M.
+ * OTP_ERR_BAD_ARG: NULL pointer (boxes / scores may be NULL when K == 0, the row outputs when max_persons == 0), S <= 0,
+ * K < 0, a range outside 0 <= detect_lo <= detect_hi <= S, aspect_ratio / enlarge not positive, min_score NaN, out_w / out_h
+ * not positive; OTP_ERR_UNSUPPORTED: S * K >= 2^31. */
+int otp_pose_plan(const void* boxes, const void* scores, const void* counts, const void* frame_number,
+                  const void* num_frames, int S, int K, int detect_lo, int detect_hi, double min_score, double aspect_ratio,
+                  double enlarge, int out_w, int out_h, int posetrack18, int max_persons, void* center, void* scale, void* M,
+                  void* frame_idx, void* margin, void* box_score, void* person_slot, void* pr_off, void* total, void* stream);
 /* Training targets (PoseTrackDataset.py:403-420, utils/heatmap.py:48-105): joints (B, J, 2) float64 image coordinates,
  * vis (B, J) float32 (joints_3d_vis[:, 0]), M (B, 2, 3) float64 as above, gauss the (2 sigma3 + 1)^2 float32 Gaussian
  * patch (built on the host) -> target (B, J, h, w) float32, target_weight (B, J, 1) float32.  Joints with vis > 0 are

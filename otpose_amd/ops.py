@@ -9,6 +9,7 @@ callers that bind the native module directly.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import math
 import os
@@ -1680,6 +1681,79 @@ def pose_targets(joints, vis, M, sigma, image_size, heatmap_size):
                                          hip.ptr(weight), b, nj, W, H, w, h, 3 * int(sigma), hip.stream_of(target)),
               "otp_pose_targets")
     return target, weight
+
+
+PosePlan = collections.namedtuple("PosePlan", "center scale M frame_idx margin box_score person_slot pr_off total")
+
+
+def _plan_arg(t, dtype, shape, name):
+    """One device input of :func:`pose_plan`: type, then shape, then device (so every argument error shows without a GPU)."""
+    if not torch.is_tensor(t) or t.dtype != dtype:
+        raise TypeError(f"{name} must be a {dtype} tensor")
+    if t.dim() != len(shape) or any(s is not None and t.shape[i] != s for i, s in enumerate(shape)):
+        raise ValueError(f"{name} must have shape {tuple('*' if s is None else s for s in shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def pose_plan(boxes, scores, counts, frame_number, num_frames, *, image_size, max_persons, detect=None, min_score=0.0,
+              enlarge=1.25, posetrack18=True, aspect_ratio=None, window_frames=5):
+    """The crop plan of the video path, on the device in one launch (``otp_pose_plan``, csrc/plan.hip): what
+    ``crop.box_to_center_scale``, ``crop.crop_matrix`` (rotation 0) and ``crop.window`` compute per person on the host,
+    plus the compaction of the detector's (frame, box) grid into dense rows in (frame, box) order.
+
+    ``boxes`` (S, K, 4) float64 ``x, y, w, h``, ``scores`` (S, K) float32 and ``counts`` (S) int32 are
+    ``PersonDetector.detect``'s device output over the pool; ``frame_number`` (S) int32 is each pool frame's number as in
+    the file name and ``num_frames`` (S) int32 the length of its sequence (per frame: one pool may hold several videos,
+    each as a run of consecutive frame numbers).  Only slots in ``detect = (lo, hi)`` (default: all) yield persons, the
+    others are the halo the windows read; boxes scoring below ``min_score`` are dropped.  ``image_size`` = (W, H) is
+    ``MODEL.IMAGE_SIZE`` (the crop size; ``aspect_ratio`` defaults to W / H), ``enlarge`` the box enlargement.
+
+    Returns a :class:`PosePlan` of device tensors with ``P = max_persons`` rows: ``center`` / ``scale`` (P, 2) float32,
+    ``M`` (P, 2, 3) float64, ``frame_idx`` (P, 5) int32 pool slots (cur, prev, next, pprev, nnext; -1: an empty frame),
+    ``margin`` (P, 4) float32, ``box_score`` (P) float64, ``person_slot`` (P) int32, ``pr_off`` (S + 1) int32 per-frame
+    row offsets (capped at P) and ``total`` (1) int32: the persons kept, NOT capped - rows past ``min(total, P)`` are
+    padding (identity ``M``, ``frame_idx`` -1, the rest 0 / -1).  Nothing is read back: ``int(plan.total)`` is the caller's
+    one synchronisation."""
+    if int(window_frames) != 5:
+        raise ValueError(f"pose_plan builds the 5-frame window of crop.window, not {window_frames} frames")
+    i32 = torch.int32
+    boxes = _plan_arg(boxes, torch.float64, (None, None, 4), "boxes")
+    s, k = boxes.shape[:2]
+    scores = _plan_arg(scores, torch.float32, (s, k), "scores")
+    counts = _plan_arg(counts, i32, (s,), "counts")
+    frame_number = _plan_arg(frame_number, i32, (s,), "frame_number")
+    num_frames = _plan_arg(num_frames, i32, (s,), "num_frames")
+    if s < 1:
+        raise ValueError("pose_plan needs at least one pool frame")
+    lo, hi = (0, s) if detect is None else (int(detect[0]), int(detect[1]))
+    if not 0 <= lo <= hi <= s:
+        raise ValueError(f"detect = ({lo}, {hi}) is not a range of the {s} pool frames")
+    w_img, h_img = int(image_size[0]), int(image_size[1])
+    if w_img < 1 or h_img < 1:
+        raise ValueError("image_size must be (W, H) with both positive")
+    ar = w_img * 1.0 / h_img if aspect_ratio is None else float(aspect_ratio)
+    min_score, enlarge, p = float(min_score), float(enlarge), int(max_persons)
+    if not (math.isfinite(ar) and ar > 0 and math.isfinite(enlarge) and enlarge > 0) or math.isnan(min_score):
+        raise ValueError("aspect_ratio and enlarge must be positive and finite, min_score a number")
+    if p < 0:
+        raise ValueError("max_persons must not be negative")
+    tensors = (boxes, scores, counts, frame_number, num_frames)
+    _require_gpu(*tensors)
+    dev = boxes.device
+    if any(t.device != dev for t in tensors):
+        raise ValueError("pose_plan's inputs must share one device")
+    boxes, scores, counts, frame_number, num_frames = (t.contiguous() for t in tensors)
+    f32, f64 = torch.float32, torch.float64
+    plan = PosePlan(torch.empty((p, 2), dtype=f32, device=dev), torch.empty((p, 2), dtype=f32, device=dev),
+                    torch.empty((p, 2, 3), dtype=f64, device=dev), torch.empty((p, 5), dtype=i32, device=dev),
+                    torch.empty((p, 4), dtype=f32, device=dev), torch.empty((p,), dtype=f64, device=dev),
+                    torch.empty((p,), dtype=i32, device=dev), torch.empty((s + 1,), dtype=i32, device=dev),
+                    torch.empty((1,), dtype=i32, device=dev))
+    hip.check(hip.lib().otp_pose_plan(
+        hip.ptr(boxes), hip.ptr(scores), hip.ptr(counts), hip.ptr(frame_number), hip.ptr(num_frames), s, k, lo, hi, min_score,
+        ar, enlarge, w_img, h_img, int(bool(posetrack18)), p, *[hip.ptr(t) for t in plan], hip.stream_of(boxes)),
+        "otp_pose_plan")
+    return plan
 
 
 def st_ohkw_loss(s, t, g, w, topk=8, flags=None, with_grad=False):

@@ -428,6 +428,30 @@ size_t otp_local_attn_backward_workspace(int B, int C, int T, int n_head, int wi
 int otp_local_attn_backward(const void* q, const void* k, const void* v, const void* probs, const void* gout, void* gq, void* gk,
                             void* gv, void* grel, void* ws, size_t ws_bytes, int B, int C, int T, int n_head, int window,
                             float scale, void* stream);
+/* conv embedding layer of ConvTransformer (ConvVideoTransformer.py:60-78, 129-135; csrc/convembd.hip) as one launch, exact fp32
+ * (f32 MFMA = an fmaf chain; mean first, then the centred sum of squares, cross-wave sums in a fixed order):
+ *   z = Conv2d(Cin, Cout, ks, stride 1, padding ks / 2)(x),  x (B, Cin, H, W), zero padding;  v = z + bias[c] (bias may be NULL)
+ *   gamma / beta non-NULL (both or neither):  v = (v - mean_c v) / sqrt(mean_c (v - mean_c v)^2 + eps) * gamma[c] + beta[c]
+ *   out[b][c][t] = max(v, 0) + pe[c][t]  (pe (Cout, H W) may be NULL),  out (B, Cout, T = H W) fp32
+ * A non-NULL `z` (B, Cout, T) also receives the convolution result (without the bias) for the backward.
+ * wpacked: otp_conv_embd_weight_bytes bytes written by otp_conv_embd_pack_weight from the (Cout, Cin, ks, ks) weights.
+ * Supported (otp_conv_embd_supported: 1 / 0): ks 1, 3 or 5, 1 <= Cin, Cout <= 256, B, H, W >= 1 with H W <= 2^30; anything
+ * else - and a gamma without beta - is OTP_ERR_BAD_ARG before any launch. */
+int otp_conv_embd_supported(int B, int Cin, int H, int W, int Cout, int ks);
+size_t otp_conv_embd_weight_bytes(int Cin, int Cout, int ks);
+int otp_conv_embd_pack_weight(const void* weight, void* wpacked, int Cin, int Cout, int ks, void* stream);
+int otp_conv_embd(const void* x, const void* wpacked, const void* bias, const void* gamma, const void* beta, const void* pe,
+                  void* out, void* z, int B, int Cin, int H, int W, int Cout, int ks, float eps, void* stream);
+/* the backward of that epilogue, in front of the convolution's own gradients (otp_conv2d with dgrad weights, otp_conv2d_wgrad):
+ * per token mean, rstd and xhat are recomputed from v = z + bias,  mask = gamma xhat + beta > 0,  g = grad_y mask,  g' = gamma g,
+ *   grad_z = rstd (g' - mean_c g' - xhat mean_c(g' xhat)),   grad_gamma[c] = sum_{b,t} g xhat,   grad_beta[c] = sum_{b,t} g
+ * (grad_gamma / grad_beta (C) may be NULL).  Per-workgroup partial sums in `ws` (otp_conv_embd_backward_pre_workspace bytes)
+ * are added in a fixed order: no atomics, bit-equal between runs.  gamma == beta == NULL (no LayerNorm):
+ * grad_z = grad_y (z + bias > 0), ws unused, grad_gamma / grad_beta must be NULL.  1 <= C <= 256, B <= 65535, T <= 2^30. */
+size_t otp_conv_embd_backward_pre_workspace(int B, int C, int T);
+int otp_conv_embd_backward_pre(const void* z, const void* bias, const void* gamma, const void* beta, const void* grad_y,
+                               void* grad_z, void* grad_gamma, void* grad_beta, void* ws, size_t ws_bytes, int B, int C, int T,
+                               float eps, void* stream);
 /* nn.Upsample(scale_factor=f, mode='linear', align_corners=False) on (B,C,T) -> out (B, out_ctot, T*f) at
  * channel offset out_coff (f = 1 copies) (ConvVideoTransformer.py:108,179; OTPose.py:362-369) */
 int otp_upsample_linear(const void* x, void* out, int B, int C, int T, int f, int out_ctot, int out_coff, void* stream);

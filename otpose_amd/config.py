@@ -13,7 +13,10 @@ Values follow reference configs/Base_PoseTrack17.yaml:36-88 and configs/17/model
 
 Extension keys read with a default when absent (``otpose_amd.model.OTPose``): ``MODEL.WINDOW_FRAMES``, ``MODEL.DTYPE`` and the
 local attention windows ``MODEL.MHA_WIN_SIZE`` (int or per-level list, -1 = off), ``MODEL.USE_REL_PE`` (False) for the two temporal
-encoders and ``MODEL.FLOW_MHA_WIN_SIZE`` (-1) for the flow encoder.
+encoders and ``MODEL.FLOW_MHA_WIN_SIZE`` (-1) for the flow encoder; the conv embedding layers in front of the encoders
+(reference model/ConvVideoTransformer.py:60-78, ``arch[0]``): ``MODEL.EMBD_LAYERS`` (int, 0 = none) for the two temporal encoders,
+``MODEL.FLOW_EMBD_LAYERS`` (0) for the flow encoder, ``MODEL.EMBD_KS`` (3; 1, 3 or 5) and ``MODEL.EMBD_WITH_LN`` (True: a channel
+LayerNorm behind each convolution and no conv bias).  Training takes ``EMBD_KS`` 1 or 3.
 """
 from __future__ import annotations
 

@@ -1029,8 +1029,50 @@ class InferenceEngine:
         ws = self.new(max(nbytes // 4, 1))
         self.call(self.lib.otp_chan_attn, "otp_chan_attn", *ops.chan_attn_args(q, k, v, att, ws, nbytes, a.n_head, a.scale))
 
+    def encoder_pe(self, ct, T):
+        """The (C, T) table the glue kernels add into encoder ``ct``'s input: its positional table, or - for an encoder with conv
+        embedding layers, which adds the table behind its last layer - one cached all-zero table per shape."""
+        if len(ct.embd) == 0:
+            return self.dev_param(ct.pos_embd[0, :, :T])
+        zeros = getattr(self, "_zero_pe", None)
+        if zeros is None:
+            zeros = self._zero_pe = {}
+        key = (ct.n_in, T)
+        if key not in zeros:
+            zeros[key] = torch.zeros((ct.n_in, T), dtype=torch.float32, device=self.dev)
+        return zeros[key]
+
+    def conv_embd(self, ct, x):
+        """The ``arch[0]`` conv embedding layers of ``ct`` (ConvVideoTransformer.py:129-135) on x (B, n_in, T): one otp_conv_embd
+        launch per layer on ping-pong buffers, the last one adding the positional table.  No layer: x itself, no launch."""
+        n = len(ct.embd)
+        if n == 0:
+            return x
+        B, cin, T = x.shape
+        h = int(ct.h)
+        if T % h or T > ct.max_len:
+            raise ValueError(f"conv embedding: {T} tokens do not form an h = {h} grid of at most max_len = {ct.max_len} tokens")
+        C = ct.n_embd
+        pe = self.dev_param(ct.pos_embd[0, :, :T])
+        bufs = [self.new(B, C, T) for _ in range(min(n, 2))]
+        for i, (conv, norm) in enumerate(zip(ct.embd, ct.embd_norm)):
+            ln = hasattr(norm, "weight")                       # modules.LayerNorm, or nn.Identity without the norm
+            wt = self.dev_param(conv.weight)
+            bias, gamma, beta, _ = ops.conv_embd_params((B, cin, h, T // h), wt, conv.bias, norm.weight if ln else None,
+                                                        norm.bias if ln else None, None, self.dev)
+            packed = ops.pack_conv_embd_weight(wt)
+            self._keep += [packed, bias, gamma, beta]
+            out = bufs[i % 2]
+            self.call(self.lib.otp_conv_embd, "otp_conv_embd",
+                      *ops.conv_embd_args(x.view(B, cin, h, T // h), packed, bias, gamma, beta, pe if i == n - 1 else None, out,
+                                          None, C, conv.kernel_size[0], norm.eps if ln else 1e-5))
+            x, cin = out, C
+        return x
+
     def conv_transformer(self, ct, x, stacked):
-        """x (B, C, T) already holds input + positional table; writes levels into stacked (B, L*C, T)."""
+        """x (B, C, T) already holds input + positional table (:meth:`encoder_pe`; the bare input for an encoder with conv
+        embedding layers, whose last launch adds the table); writes levels into stacked (B, L*C, T)."""
+        x = self.conv_embd(ct, x)
         _, C, T = x.shape
         L = self.lib
         for blk in ct.stem:
@@ -1103,7 +1145,7 @@ class InferenceEngine:
 
         total, squeezed, inter = self.new(B, J, h, w), self.new(B, J, h, w), self.new(B, J, h, w)
         flow_in = self.new(B, J, T)
-        pe_f = self.dev_param(m.flow_encoder.pos_embd[0, :, :T])
+        pe_f = self.encoder_pe(m.flow_encoder, T)
         self.call(L.otp_glue_total_n, "otp_glue_total", hip.ptr(rough), hip.ptr(total), hip.ptr(squeezed), hip.ptr(inter),
                   hip.ptr(flow_in), hip.ptr(pe_f), B, J, T, self.F)
         ctx = self.new(B, J, T)
@@ -1115,8 +1157,8 @@ class InferenceEngine:
         self.conv_transformer(m.flow_encoder, flow_in, ctx)
         D = m.num_frames * J                       # stacked maps per joint: 8 (5-frame window) or 12 (7 frames)
         x1, x2, prev_b = self.new(B, D, T), self.new(B, D, T), self.new(B, J, h, w)
-        pe1 = self.dev_param(m.temporal_encoder1.pos_embd[0, :, :T])
-        pe2 = self.dev_param(m.temporal_encoder2.pos_embd[0, :, :T])
+        pe1 = self.encoder_pe(m.temporal_encoder1, T)
+        pe2 = self.encoder_pe(m.temporal_encoder2, T)
         self.call(L.otp_glue_stack_n, "otp_glue_stack", hip.ptr(rough), hip.ptr(self.margin), hip.ptr(squeezed),
                   hip.ptr(inter), hip.ptr(ctx), hip.ptr(pe1), hip.ptr(pe2), hip.ptr(x1), hip.ptr(x2), hip.ptr(prev_b),
                   B, J, T, self.F)

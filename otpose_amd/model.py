@@ -137,6 +137,14 @@ class OTPose(nn.Module):
         rel = bool(get("USE_REL_PE", False))
         win = self._local_windows(get("MHA_WIN_SIZE", -1), self.scale_arch, "MODEL.MHA_WIN_SIZE")
         fwin = self._local_windows(get("FLOW_MHA_WIN_SIZE", -1), self.flow_scale_arch, "MODEL.FLOW_MHA_WIN_SIZE")
+        # extension keys: conv embedding layers in front of the encoders (ConvVideoTransformer.py:60-78; the reference builds its
+        # encoders with arch[0] = 0): MODEL.EMBD_LAYERS for the two temporal encoders, MODEL.FLOW_EMBD_LAYERS for the flow encoder,
+        # MODEL.EMBD_KS / MODEL.EMBD_WITH_LN for all three
+        ekw = self._embd_keys(get, d)
+        if ekw:
+            self.scale_arch = (ekw.pop("layers"),) + self.scale_arch[1:]
+            self.flow_scale_arch = (ekw.pop("flow_layers"),) + self.flow_scale_arch[1:]
+            tkw.update(ekw)
         self.temporal_encoder1 = ConvTransformer(d, d, n_head=2, arch=self.scale_arch, **tkw, **self._local_kw(win, rel))
         self.temporal_encoder2 = ConvTransformer(d, d, n_head=2, arch=self.scale_arch, **tkw, **self._local_kw(win, rel))
         self.flow_encoder = ConvTransformer(self.patch_dim, self.patch_dim, n_head=1,
@@ -186,6 +194,22 @@ class OTPose(nn.Module):
                 check_local_length(t if self.num_patches % 2 ** i == 0 else 0, s,
                                    f"{key}[{i}]: level {i} of the {self.pe_w}x{self.pe_h} heat-map: sequence length")
         return sizes
+
+    def _embd_keys(self, get, d):
+        """The conv embedding keys of the cfg, validated: {} at the defaults (no layer anywhere), else the layer counts and the
+        ConvTransformer keyword arguments."""
+        from .modules import check_conv_embd
+        layers, flow_layers = get("EMBD_LAYERS", 0), get("FLOW_EMBD_LAYERS", 0)
+        ks, with_ln = get("EMBD_KS", 3), get("EMBD_WITH_LN", True)
+        if not isinstance(with_ln, bool):
+            raise ValueError(f"MODEL.EMBD_WITH_LN must be a bool, got {with_ln!r}")
+        # the kernel size is checked even when no layer is asked for: a bad key does not wait for the day a layer is
+        check_conv_embd(d, d, ks, 1, "MODEL.EMBD_KS")
+        check_conv_embd(d, d, ks, layers, "MODEL.EMBD_LAYERS")
+        check_conv_embd(self.patch_dim, self.patch_dim, ks, flow_layers, "MODEL.FLOW_EMBD_LAYERS")
+        if layers == 0 and flow_layers == 0:
+            return {}
+        return {"layers": int(layers), "flow_layers": int(flow_layers), "n_embd_ks": int(ks), "with_ln": with_ln}
 
     @staticmethod
     def _local_kw(windows, use_rel_pe):

@@ -330,13 +330,41 @@ def sinusoid_table(n_position: int, d_hid: int) -> torch.Tensor:
     return torch.from_numpy(table.astype(np.float32)).unsqueeze(0).transpose(1, 2).contiguous()
 
 
+CONV_EMBD_KS = (1, 3, 5)                            # the kernel sizes csrc/convembd.hip is built for
+CONV_EMBD_MAX_CHANNELS = 256
+
+
+def check_conv_embd(n_in, n_embd, ks, layers, what="ConvTransformer"):
+    """Raise ``ValueError`` unless ``layers`` conv embedding layers ``n_in -> n_embd`` with ``ks x ks`` kernels are ones the
+    conv embedding supports; without a layer nothing maps ``n_in`` to ``n_embd``, so the two must be equal (the reference
+    fails later, in the first block's LayerNorm)."""
+    for name, v in (("n_in", n_in), ("n_embd", n_embd), ("arch[0]", layers)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+            raise ValueError(f"{what}: {name} must be an int, got {v!r}")
+    if layers < 0:
+        raise ValueError(f"{what}: the number of conv embedding layers must be >= 0, got {layers}")
+    if layers == 0:
+        if n_in != n_embd:
+            raise ValueError(f"{what}: n_in {n_in} != n_embd {n_embd} needs at least one conv embedding layer (arch[0] > 0)")
+        return
+    if isinstance(ks, bool) or not isinstance(ks, (int, np.integer)) or ks not in CONV_EMBD_KS:
+        raise ValueError(f"{what}: the conv embedding kernel size must be one of {CONV_EMBD_KS}, got {ks!r}")
+    if not (1 <= n_in <= CONV_EMBD_MAX_CHANNELS and 1 <= n_embd <= CONV_EMBD_MAX_CHANNELS):
+        raise ValueError(f"{what}: the conv embedding takes 1 .. {CONV_EMBD_MAX_CHANNELS} channels, got {n_in} -> {n_embd}")
+
+
 class ConvTransformer(_Container):
-    """reference model/ConvVideoTransformer.py:21-111 (arch[0] == 0: no conv embedding is built)."""
+    """reference model/ConvVideoTransformer.py:21-111.  ``arch[0]`` conv embedding layers in front of the stem (:60-78): ``embd[i]``
+    a ``ks x ks`` Conv2d over the (h, w) token grid (bias only without the norm), ``embd_norm[i]`` the channel LayerNorm
+    (``with_ln``; nn.Identity otherwise), then a ReLU (csrc/convembd.hip)."""
 
     def __init__(self, n_in, n_embd, n_head, n_embd_ks, max_len, arch, h=72, scale_factor=2,
-                 attn_pdrop=0.0, proj_pdrop=0.0, path_pdrop=0.0, mha_win_size=-1, use_rel_pe=False):
+                 attn_pdrop=0.0, proj_pdrop=0.0, path_pdrop=0.0, mha_win_size=-1, use_rel_pe=False, with_ln=True):
         super().__init__()
-        assert len(arch) == 3 and arch[0] == 0, "conv embedding (arch[0] > 0) is unused by OTPose"
+        if len(arch) != 3:
+            raise ValueError(f"ConvTransformer: arch is (embedding layers, stem blocks, branch blocks), got {arch!r}")
+        check_conv_embd(n_in, n_embd, n_embd_ks, arch[0])
+        self.n_in, self.n_embd_ks, self.with_ln, self.h = n_in, int(n_embd_ks), bool(with_ln), h
         self.arch, self.max_len, self.n_embd, self.n_head = tuple(arch), max_len, n_embd, n_head
         self.scale_factor = scale_factor
         # local attention window per pyramid level: [0] the stem, [1 + i] branch i (ConvVideoTransformer.py:29,48-49,89,104);
@@ -350,6 +378,10 @@ class ConvTransformer(_Container):
         self.register_buffer("pos_embd", sinusoid_table(max_len, n_embd) / (n_embd ** 0.5))
         self.embd = nn.ModuleList()
         self.embd_norm = nn.ModuleList()
+        for i in range(arch[0]):
+            self.embd.append(_conv(n_in if i == 0 else n_embd, n_embd, self.n_embd_ks, 1, self.n_embd_ks // 2,
+                                   bias=not self.with_ln))
+            self.embd_norm.append(LayerNorm(n_embd) if self.with_ln else nn.Identity())
         kw = dict(attn_pdrop=attn_pdrop, proj_pdrop=proj_pdrop, path_pdrop=path_pdrop, use_rel_pe=use_rel_pe)
         self.stem = nn.ModuleList([TransformerBlock(n_embd, n_head, (1, 1), mha_win_size=self.mha_win_size[0], **kw)
                                    for _ in range(arch[1])])

@@ -1226,6 +1226,83 @@ def local_attn(q, k, v, n_head, window_size, scale, rel_pe=None):
     return out
 
 
+CONV_EMBD_KS = (1, 3, 5)              # the kernel sizes csrc/convembd.hip is built for
+CONV_EMBD_MAX_CHANNELS = 256
+
+
+def check_conv_embd(b, cin, h, w, cout, ks):
+    """Raise ``ValueError`` for a shape the conv embedding does not take (``otp_conv_embd_supported``: ks 1 / 3 / 5, at most 256
+    input and output channels)."""
+    if (isinstance(ks, bool) or not isinstance(ks, int) or min(b, cin, h, w, cout) < 1
+            or not hip.lib().otp_conv_embd_supported(b, cin, h, w, cout, ks)):
+        raise ValueError(f"conv_embd: kernel size must be one of {CONV_EMBD_KS} and 1 <= channels <= {CONV_EMBD_MAX_CHANNELS}, got "
+                         f"ks {ks}, {cin} -> {cout} channels on a ({b}, {cin}, {h}, {w}) input")
+
+
+def pack_conv_embd_weight(weight):
+    """(Cout, Cin, ks, ks) -> the packed [tap][Cin4][CoutP] device tensor of :func:`conv_embd` (csrc/convembd.hip)."""
+    _require_gpu(weight)
+    _check_f32(weight)
+    w = _f32(weight)
+    if w.dim() != 4 or w.shape[2] != w.shape[3]:
+        raise ValueError(f"conv_embd: weight must be (Cout, Cin, ks, ks), got {tuple(weight.shape)}")
+    cout, cin, ks, _ = w.shape
+    L = hip.lib()
+    nbytes = L.otp_conv_embd_weight_bytes(cin, cout, ks)
+    if nbytes == 0:
+        check_conv_embd(1, cin, 1, 1, cout, ks)
+    wp = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
+    _launch(L.otp_conv_embd_pack_weight, "otp_conv_embd_pack_weight", (hip.ptr(w), hip.ptr(wp), cin, cout, ks), w)
+    return wp
+
+
+def conv_embd_params(x_shape, weight, bias, ln_weight, ln_bias, pe, device):
+    """The checked, flattened fp32 forms (bias, gamma, beta, pe) of a conv embedding layer's optional arguments for an input of
+    ``x_shape`` (B, Cin, H, W): ``ValueError`` for anything that does not fit."""
+    if len(x_shape) != 4 or weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
+        raise ValueError(f"conv_embd: x must be (B, Cin, H, W) and weight (Cout, Cin, ks, ks), got {tuple(x_shape)} and "
+                         f"{tuple(weight.shape)}")
+    b, cin, h, w = x_shape
+    cout, cin_w, ks, _ = weight.shape
+    if cin_w != cin:
+        raise ValueError(f"conv_embd: weight takes {cin_w} input channels, x has {cin}")
+    check_conv_embd(b, cin, h, w, cout, int(ks))
+    if (ln_weight is None) != (ln_bias is None):
+        raise ValueError("conv_embd: ln_weight and ln_bias come together (both or neither)")
+    flat = []
+    for name, t in (("bias", bias), ("ln_weight", ln_weight), ("ln_bias", ln_bias)):
+        if t is not None and t.numel() != cout:
+            raise ValueError(f"conv_embd: {name} has {t.numel()} entries, the layer has {cout} output channels")
+        flat.append(None if t is None else _f32(t, device).reshape(cout))
+    if pe is not None:
+        if pe.numel() != cout * h * w:
+            raise ValueError(f"conv_embd: pe must hold ({cout}, {h * w}) entries, got {tuple(pe.shape)}")
+        pe = _f32(pe, device).reshape(cout, h * w)
+    return (*flat, pe)
+
+
+def conv_embd_args(x, wpacked, bias, gamma, beta, pe, out, z, cout, ks, eps):
+    b, cin, h, w = x.shape
+    return (hip.ptr(x), hip.ptr(wpacked), hip.ptr(bias), hip.ptr(gamma), hip.ptr(beta), hip.ptr(pe), hip.ptr(out), hip.ptr(z),
+            b, cin, h, w, cout, int(ks), float(eps))
+
+
+def conv_embd(x, weight, bias, ln_weight, ln_bias, pe=None, eps=1e-5):
+    """One conv embedding layer of ConvTransformer (ConvVideoTransformer.py:60-78, 129-135) as one launch in exact fp32:
+    ``relu(LayerNorm_c(conv2d(x, weight, bias, padding=ks // 2))) (+ pe)`` on x (B, Cin, H, W) -> (B, Cout, H * W).  ``ln_weight`` /
+    ``ln_bias`` ((1, Cout, 1) or None: no norm) are the channel LayerNorm of model/blocks.py:95-110, ``pe`` (Cout, H * W) is
+    added behind the ReLU."""
+    _require_gpu(x, weight)
+    _check_f32(x, weight)
+    x = x.contiguous()
+    bias, gamma, beta, pe = conv_embd_params(x.shape, weight, bias, ln_weight, ln_bias, pe, x.device)
+    cout, ks = weight.shape[0], weight.shape[2]
+    out = torch.empty((x.shape[0], cout, x.shape[2] * x.shape[3]), dtype=torch.float32, device=x.device)
+    _launch(hip.lib().otp_conv_embd, "otp_conv_embd",
+            conv_embd_args(x, pack_conv_embd_weight(weight), bias, gamma, beta, pe, out, None, cout, ks, eps), x)
+    return out
+
+
 def upsample_linear_args(x, out, f, out_coff=0):
     """``x`` (B, C, T) or (B, C, H, W) with T = H * W, written to channels [out_coff, out_coff + C) of ``out``."""
     b, c = x.shape[:2]

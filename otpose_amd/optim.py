@@ -316,6 +316,8 @@ def reference_param_groups(model, cfg):
                 no_decay.add(fpn)
             elif pn.endswith("rel_pe"):
                 no_decay.add(fpn)
+            elif pn == "weight" and isinstance(m, nn.Conv2d) and ".embd." in f".{mn}.":
+                decay.add(fpn)          # conv embedding of a ConvTransformer (its bias and embd_norm.* fall under the rules above)
             elif pn.startswith(("offsets_list", "masks_list", "final_layer")):
                 decay.add(fpn)
     named = dict(model.named_parameters())

@@ -412,6 +412,13 @@ class TrainGraph:
     def conv_transformer(self, p, x4, n_head, arch):
         b, c, h, w = x4.shape
         t = h * w
+        # conv embedding layers in front of the positional table (ConvVideoTransformer.py:129-135), one node each
+        i = 0
+        while self.has(f"{p}.embd.{i}.weight"):
+            x4 = T.conv_embd(x4, self.P[f"{p}.embd.{i}.weight"], self.P.get(f"{p}.embd.{i}.bias"),
+                             self.P.get(f"{p}.embd_norm.{i}.weight"), self.P.get(f"{p}.embd_norm.{i}.bias")).view(b, -1, h, w)
+            i += 1
+        c = x4.shape[1]
         x = x4.reshape(b, c, t) + self.Bf[p + ".pos_embd"][:, :, :t]
         for i in range(arch[1]):
             x = self.tblock(f"{p}.stem.{i}", x, n_head, 1)

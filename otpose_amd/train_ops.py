@@ -632,6 +632,86 @@ def local_attn(q, k, v, n_head, window_size, scale, rel_pe=None):
     return LocalAttnFunction.apply(q, k, v, rel_pe, n_head, window_size, scale)
 
 
+CONV_EMBD_TRAIN_KS = (1, 3)           # the kernel sizes conv2d_grad_weight (otp_conv2d_wgrad) takes
+CONV_EMBD_DGRAD_BLOCK = 32            # output channels per conv2d_grad_input launch of the conv embedding's backward
+
+
+def check_conv_embd_train(weight_shape):
+    """Raise ``ValueError`` for a conv embedding layer whose convolution gradients are not built: ``otp_conv2d_wgrad`` takes 1x1
+    and 3x3 kernels (the forward, ``ops.conv_embd``, also 5x5)."""
+    if weight_shape[2] not in CONV_EMBD_TRAIN_KS:
+        raise ValueError(f"conv_embd: training needs a kernel size in {CONV_EMBD_TRAIN_KS} (the weight gradient kernel), got a "
+                         f"{tuple(weight_shape)} weight")
+
+
+class ConvEmbdFunction(Function):
+    """One conv embedding layer (``ops.conv_embd``): the forward launch also writes z, the convolution result in front of the
+    norm, and keeps it with x and the parameters.  The backward is ``otp_conv_embd_backward_pre`` (grad_z, grad of the LayerNorm
+    parameters: fixed-order sums, deterministic), then ``conv2d_grad_input`` / ``conv2d_grad_weight`` on the exact-fp32 direct
+    kernels and ``channel_sum`` for a bias."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, ln_weight, ln_bias, pe, eps):
+        _require_gpu(x, weight)
+        _check_f32(x, weight)
+        check_conv_embd_train(weight.shape)
+        x, weight = x.contiguous(), weight.contiguous()
+        b_, gamma, beta, pe_ = ops.conv_embd_params(x.shape, weight, bias, ln_weight, ln_bias, pe, x.device)
+        cout, ks = weight.shape[0], weight.shape[2]
+        n, _, h, w = x.shape
+        out = torch.empty((n, cout, h * w), dtype=torch.float32, device=x.device)
+        z = torch.empty_like(out)
+        hip.check(hip.lib().otp_conv_embd(*ops.conv_embd_args(x, ops.pack_conv_embd_weight(weight), b_, gamma, beta, pe_, out, z,
+                                                              cout, ks, eps), hip.stream_of(x)), "otp_conv_embd")
+        ctx.save_for_backward(x, weight, z, b_, gamma, beta)
+        ctx.eps = float(eps)
+        ctx.params = (weight, bias, ln_weight, ln_bias)
+        # the layer is exact fp32 in both directions: no Winograd transform, no split products in its input gradient
+        ctx.routes = dataclasses.replace(current_routes(), use_winograd=False, use_x3=False, use_dense_cc=False)
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight, z, b_, gamma, beta = ctx.saved_tensors
+        pw, pb, pg, pbt = ctx.params
+        n, cout, t = z.shape
+        ks = weight.shape[2]
+        L = hip.lib()
+        gy = gy.contiguous()
+        gz = torch.empty_like(z)
+        gg = gb_ln = ws = None
+        nbytes = 0
+        if gamma is not None:
+            def slot(p):
+                s = grad_slot(p)
+                return s.view(-1) if s is not None else torch.empty(cout, dtype=torch.float32, device=z.device)
+            gg, gb_ln = slot(pg), slot(pbt)
+            nbytes = L.otp_conv_embd_backward_pre_workspace(n, cout, t)
+            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=z.device)
+        hip.check(L.otp_conv_embd_backward_pre(hip.ptr(z), hip.ptr(b_), hip.ptr(gamma), hip.ptr(beta), hip.ptr(gy), hip.ptr(gz),
+                                               hip.ptr(gg), hip.ptr(gb_ln), hip.ptr(ws), nbytes, n, cout, t, ctx.eps,
+                                               hip.stream_of(z)), "otp_conv_embd_backward_pre")
+        gz4 = gz.view(n, cout, x.shape[2], x.shape[3])
+        gx = None
+        if ctx.needs_input_grad[0]:
+            # blocked summation over the output channels: the input-gradient kernel sums its Cout ks^2 terms as one fmaf chain
+            # (1224 terms at 136 channels and 3x3 - four times the rounding error of a vectorised fp32 convolution), so it runs on
+            # slices of CONV_EMBD_DGRAD_BLOCK channels and the slice results are added
+            for c0 in range(0, cout, CONV_EMBD_DGRAD_BLOCK):
+                c1 = min(cout, c0 + CONV_EMBD_DGRAD_BLOCK)
+                part = conv2d_grad_input(gz4[:, c0:c1].contiguous(), weight[c0:c1].contiguous(), x.shape, 1, ks // 2, 1, ctx.routes)
+                gx = part if gx is None else gx.add_(part)
+        gw = conv2d_grad_weight(x, gz4, weight.shape, 1, ks // 2, 1, grad_slot(pw)) if ctx.needs_input_grad[1] else None
+        gbias = channel_sum(gz4, grad_slot(pb)).reshape(pb.shape) if pb is not None and ctx.needs_input_grad[2] else None
+        if gamma is not None:
+            gg, gb_ln = gg.reshape(pg.shape), gb_ln.reshape(pbt.shape)
+        return gx, gw, gbias, gg, gb_ln, None, None
+
+
+def conv_embd(x, weight, bias, ln_weight, ln_bias, pe=None, eps=1e-5):
+    return ConvEmbdFunction.apply(x, weight, bias, ln_weight, ln_bias, pe, eps)
+
+
 class ScaleResidualFunction(Function):
     """``x + drop_path(scale * a)`` of a TransformerBlock (model/blocks.py:277-279, AffineDropPath :283-316): ``scale`` is the
     (1, C, 1) AffineDropPath parameter, ``mask`` (B,) the per-sample Bernoulli(keep) / keep factors (None: no drop-path)."""

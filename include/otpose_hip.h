@@ -345,7 +345,9 @@ int otp_conv2d_wgrad(const void* x, const void* grad_out, void* grad_weight, int
 /* BatchNorm2d, training mode (torch semantics: biased variance for normalisation, unbiased for running_var,
  * running = (1-momentum)*running + momentum*batch), fused with the residual add and ReLU that follow it:
  *   y = relu?( (x - mean_c) * rstd_c * gamma_c + beta_c (+ res) );  save_mean / save_rstd (C) feed the backward.
- * running_mean / running_var may be NULL.  workspace: otp_bn_workspace bytes. */
+ * running_mean / running_var may be NULL.  workspace: otp_bn_workspace bytes.
+ * A channel with at most 256 values (N HW <= 256: the (N, C, 1, 1) gate vectors of RSN_ATTENTION) takes its statistics and its
+ * backward in two fp64 passes, one wave per channel (mean, then centred squares; the backward takes the mean again from x). */
 size_t otp_bn_workspace(int N, int C, int HW);
 int otp_bn_train_forward(const void* x, const void* gamma, const void* beta, const void* res, void* y, void* save_mean,
                          void* save_rstd, void* running_mean, void* running_var, void* workspace, size_t workspace_bytes,
@@ -452,6 +454,34 @@ size_t otp_conv_embd_backward_pre_workspace(int B, int C, int T);
 int otp_conv_embd_backward_pre(const void* z, const void* bias, const void* gamma, const void* beta, const void* grad_y,
                                void* grad_z, void* grad_gamma, void* grad_beta, void* ws, size_t ws_bytes, int B, int C, int T,
                                float eps, void* stream);
+/* RSN attention (Pose Refine Machine) and weight vector of model/RSB.py:142-203 (csrc/prm.hip).  Exact fp32, no float atomics:
+ * every sum runs in a fixed order, two runs are bit-equal.  Inference, BatchNorm (and the conv bias) folded into scale / shift (C):
+ *   otp_prm_gate:  m[n][c] = mean_hw f,  v = relu(scale1 (w1 m) + shift1),  v += m if `residual` (RSN_WEIGHT_VECTOR, RSB.py:162),
+ *                  gate[n][c] = sigmoid(relu(scale2 (w2 v) + shift2));  w1, w2 (C, C) row-major [out][in];  f (N, C, HW), gate (N, C)
+ *   otp_prm_apply: t = relu(scale31 (w31 f) + shift31) per pixel, zero outside the image (the 9x9's padding applies to t),
+ *                  g = sigmoid(relu(scale32 dw9x9(t; w32 (C, 81)) + shift32)),  out = f (1 + gate[n][c] g);  t and g stay in the LDS
+ * Supported (otp_prm_supported: 1 / 0): 1 <= C <= 64, H W <= 2^30; N <= 65535.  Anything else is OTP_ERR_BAD_ARG before any launch. */
+int otp_prm_supported(int C, int H, int W);
+int otp_prm_gate(const void* f, const void* w1, const void* scale1, const void* shift1, const void* w2, const void* scale2,
+                 const void* shift2, void* gate, int N, int C, int HW, int residual, void* stream);
+int otp_prm_apply(const void* f, const void* gate, const void* w31, const void* scale31, const void* shift31, const void* w32,
+                  const void* scale32, const void* shift32, void* out, int N, int C, int H, int W, void* stream);
+/* training pieces of the same modules.  mean (N, C) of x (N, C, HW) and its backward grad_x = grad_mean / HW (any C, N <= 65535) */
+int otp_spatial_mean(const void* x, void* mean, int N, int C, int HW, void* stream);
+int otp_spatial_mean_backward(const void* grad_mean, void* grad_x, int N, int C, int HW, void* stream);
+/* depthwise ks x ks convolution, stride 1, padding ks / 2 (ks = 9 is the one built), weight (C, 1, ks, ks), bias (C) or NULL;
+ * flip != 0 reverses the taps: the input gradient is otp_dwconv2d(grad_y, weight, NULL, grad_x, .., flip = 1).  N C <= 65535.
+ * otp_dwconv2d_wgrad: grad_weight (C, 1, ks, ks), overwritten, from per-workgroup partials in `ws` added in a fixed order. */
+int otp_dwconv2d(const void* x, const void* weight, const void* bias, void* y, int N, int C, int H, int W, int ks, int flip,
+                 void* stream);
+size_t otp_dwconv2d_wgrad_workspace(int N, int C, int H, int W, int ks);
+int otp_dwconv2d_wgrad(const void* x, const void* grad_y, void* grad_weight, void* ws, size_t ws_bytes, int N, int C, int H, int W,
+                       int ks, void* stream);
+/* out = f (1 + sigmoid(a) sigmoid(s)),  f, s, out (N, C, HW), a (N, C); the backward writes grad_f = g (1 + sa ss),
+ * grad_s = g f sa ss (1 - ss) and grad_a[n][c] = sa (1 - sa) sum_hw g f ss */
+int otp_prm_combine(const void* f, const void* a, const void* s, void* out, int N, int C, int HW, void* stream);
+int otp_prm_combine_backward(const void* f, const void* a, const void* s, const void* grad_out, void* grad_f, void* grad_a,
+                             void* grad_s, int N, int C, int HW, void* stream);
 /* nn.Upsample(scale_factor=f, mode='linear', align_corners=False) on (B,C,T) -> out (B, out_ctot, T*f) at
  * channel offset out_coff (f = 1 copies) (ConvVideoTransformer.py:108,179; OTPose.py:362-369) */
 int otp_upsample_linear(const void* x, void* out, int B, int C, int T, int f, int out_ctot, int out_coff, void* stream);

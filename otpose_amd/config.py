@@ -16,7 +16,10 @@ local attention windows ``MODEL.MHA_WIN_SIZE`` (int or per-level list, -1 = off)
 encoders and ``MODEL.FLOW_MHA_WIN_SIZE`` (-1) for the flow encoder; the conv embedding layers in front of the encoders
 (reference model/ConvVideoTransformer.py:60-78, ``arch[0]``): ``MODEL.EMBD_LAYERS`` (int, 0 = none) for the two temporal encoders,
 ``MODEL.FLOW_EMBD_LAYERS`` (0) for the flow encoder, ``MODEL.EMBD_KS`` (3; 1, 3 or 5) and ``MODEL.EMBD_WITH_LN`` (True: a channel
-LayerNorm behind each convolution and no conv bias).  Training takes ``EMBD_KS`` 1 or 3.
+LayerNorm behind each convolution and no conv bias).  Training takes ``EMBD_KS`` 1 or 3.  ``MODEL.PRM`` (a tuple out of
+``("def_fuse", "offset_mask_combine_conv")``, default ``()``): the output of a named RSB chain passes through an ``RSN_ATTENTION`` of
+its channel count (reference model/RSB.py:168-203, RSN's Pose Refine Machine), held as ``def_fuse_prm`` /
+``offset_mask_combine_prm``.  The reference exports that class and has no call site for it: the placement is this package's.
 """
 from __future__ import annotations
 

@@ -540,6 +540,40 @@ __global__ void bn_finish_stats_kernel(const double* __restrict__ part, float* _
     }
 }
 
+// forward statistics of a channel with few values (N * HW <= BN_FEW_VALUES), two passes in fp64: the mean, then the centred sum
+// of squares.  E[x^2] - mean^2 over fp32-rounded squares (channel_sums_kernel) carries a relative error of 2^-24 mean^2 / var in
+// the variance; over a handful of values that lie close together - the (N, C, 1, 1) gate vectors of RSN_ATTENTION, N values per
+// channel with |mean| / sigma up to 31 - that was 6e-5 of the variance and 40 times the error of an fp32 batch norm in y.
+// grid C, one wave per channel; the same outputs as bn_finish_stats_kernel.
+constexpr int BN_FEW_VALUES = 256;
+__global__ __launch_bounds__(64) void bn_few_stats_kernel(const float* __restrict__ x, float* __restrict__ mean,
+                                                          float* __restrict__ rstd, float* running_mean, float* running_var, int N,
+                                                          int HW, int x_ctot, int x_coff, float eps, float momentum) {
+    const int c = blockIdx.x, total = N * HW;
+    auto at = [&](int i) { return (double)x[((size_t)(i / HW) * x_ctot + x_coff + c) * HW + i % HW]; };
+    double s = 0.0;
+    for (int i = threadIdx.x; i < total; i += 64) s += at(i);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    const double count = (double)total, mu = s / count;
+    double q = 0.0;
+    for (int i = threadIdx.x; i < total; i += 64) {
+        const double d = at(i) - mu;
+        q += d * d;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+    if (threadIdx.x != 0) return;
+    const double var = q / count;
+    mean[c] = (float)mu;
+    rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mu;
+    if (running_var) {
+        const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
+        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+    }
+}
+
 // backward reductions -> dgamma = sum g*xhat, dbeta = sum g
 __global__ void bn_finish_grads_kernel(const double* __restrict__ part, float* __restrict__ dgamma,
                                        float* __restrict__ dbeta, int C, int S) {
@@ -583,6 +617,51 @@ __global__ __launch_bounds__(256) void bn_backward_apply_kernel(
         const float xh = (x[((size_t)n * x_ctot + x_coff + c) * HW + p] - mean[c]) * rstd[c];
         if (dres) dres[i] = g;
         dx[i] = gamma[c] * rstd[c] * (g - dbeta[c] * inv_count - xh * dgamma[c] * inv_count);
+    }
+}
+
+// the backward of a channel with few values (N * HW <= BN_FEW_VALUES) in fp64, one wave per channel: the mean is taken again from x
+// in fp64 (the saved fp32 mean is off by up to half an ulp, and sum_i xhat_i = count (mu - mean32) rstd then leaves
+// gamma rstd^2 (mu - mean32) dgamma in sum_i dx_i, which is zero in exact arithmetic - 1e-4 at rstd = 25), the variance is the saved
+// rstd's; dgamma, dbeta and every dx are rounded once.
+__global__ __launch_bounds__(64) void bn_few_backward_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                             const float* __restrict__ y_relu, const float* __restrict__ rstd,
+                                                             const float* __restrict__ gamma, float* dx, float* dres,
+                                                             float* __restrict__ dgamma, float* __restrict__ dbeta, int N, int C, int HW,
+                                                             int dy_ctot, int dy_coff, int x_ctot, int x_coff, int y_ctot, int y_coff) {
+    const int c = blockIdx.x, total = N * HW;
+    auto wsum = [](double v) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        return v;
+    };
+    auto xat = [&](int i) { return (double)x[((size_t)(i / HW) * x_ctot + x_coff + c) * HW + i % HW]; };
+    auto gat = [&](int i) {
+        const int n = i / HW, p = i % HW;
+        const float g = dy[((size_t)n * dy_ctot + dy_coff + c) * HW + p];
+        return (y_relu && !(y_relu[((size_t)n * y_ctot + y_coff + c) * HW + p] > 0.f)) ? 0.f : g;
+    };
+    double s = 0.0;
+    for (int i = threadIdx.x; i < total; i += 64) s += xat(i);
+    const double count = (double)total, mu = wsum(s) / count, rs = (double)rstd[c];
+    double s0 = 0.0, s1 = 0.0;
+    for (int i = threadIdx.x; i < total; i += 64) {
+        const double g = (double)gat(i);
+        s0 += g;
+        s1 += g * ((xat(i) - mu) * rs);
+    }
+    s0 = wsum(s0);
+    s1 = wsum(s1);
+    const double k = (double)gamma[c] * rs;
+    for (int i = threadIdx.x; i < total; i += 64) {
+        const float g = gat(i);
+        const size_t at = ((size_t)(i / HW) * C + c) * HW + i % HW;
+        if (dres) dres[at] = g;
+        dx[at] = (float)(k * ((double)g - s0 / count - (xat(i) - mu) * rs * (s1 / count)));
+    }
+    if (threadIdx.x == 0) {
+        dbeta[c] = (float)s0;
+        dgamma[c] = (float)s1;
     }
 }
 
@@ -864,12 +943,18 @@ extern "C" int otp_bn_train_forward(const void* x, const void* gamma, const void
     auto st = static_cast<hipStream_t>(stream);
     const int S = sums_splits(C, (size_t)N * HW);
     auto f = [](const void* p) { return static_cast<const float*>(p); };
-    hipLaunchKernelGGL(channel_sums_kernel<false>, dim3(C, S), dim3(256), 0, st, f(x), nullptr, nullptr, nullptr, nullptr,
-                       static_cast<double*>(workspace), N, C, HW, x_ctot, x_coff, 0, 0, 0, 0);
-    hipLaunchKernelGGL(bn_finish_stats_kernel, dim3(otp_ceil_div(C, 64)), dim3(64), 0, st,
-                       static_cast<const double*>(workspace), static_cast<float*>(save_mean), static_cast<float*>(save_rstd),
-                       static_cast<float*>(running_mean), static_cast<float*>(running_var), C, S, (double)N * HW, eps,
-                       momentum);
+    if ((size_t)N * HW <= (size_t)BN_FEW_VALUES) {
+        hipLaunchKernelGGL(bn_few_stats_kernel, dim3(C), dim3(64), 0, st, f(x), static_cast<float*>(save_mean),
+                           static_cast<float*>(save_rstd), static_cast<float*>(running_mean), static_cast<float*>(running_var), N, HW,
+                           x_ctot, x_coff, eps, momentum);
+    } else {
+        hipLaunchKernelGGL(channel_sums_kernel<false>, dim3(C, S), dim3(256), 0, st, f(x), nullptr, nullptr, nullptr, nullptr,
+                           static_cast<double*>(workspace), N, C, HW, x_ctot, x_coff, 0, 0, 0, 0);
+        hipLaunchKernelGGL(bn_finish_stats_kernel, dim3(otp_ceil_div(C, 64)), dim3(64), 0, st,
+                           static_cast<const double*>(workspace), static_cast<float*>(save_mean), static_cast<float*>(save_rstd),
+                           static_cast<float*>(running_mean), static_cast<float*>(running_var), C, S, (double)N * HW, eps,
+                           momentum);
+    }
     const size_t total = (size_t)N * C * HW, blocks = (total + 255) / 256;
     hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks > 16384 ? 16384 : (unsigned)blocks), dim3(256), 0, st, f(x),
                        f(save_mean), f(save_rstd), f(gamma), f(beta), f(res), static_cast<float*>(y), C, HW, relu, x_ctot,
@@ -889,6 +974,12 @@ extern "C" int otp_bn_train_backward(const void* grad_y, const void* x, const vo
     auto st = static_cast<hipStream_t>(stream);
     const int S = sums_splits(C, (size_t)N * HW);
     auto f = [](const void* p) { return static_cast<const float*>(p); };
+    if ((size_t)N * HW <= (size_t)BN_FEW_VALUES) {
+        hipLaunchKernelGGL(bn_few_backward_kernel, dim3(C), dim3(64), 0, st, f(grad_y), f(x), f(y_relu), f(save_rstd), f(gamma),
+                           static_cast<float*>(grad_x), static_cast<float*>(grad_res), static_cast<float*>(grad_gamma),
+                           static_cast<float*>(grad_beta), N, C, HW, dy_ctot, dy_coff, x_ctot, x_coff, y_ctot, y_coff);
+        return otp_launch_status();
+    }
     hipLaunchKernelGGL(channel_sums_kernel<true>, dim3(C, S), dim3(256), 0, st, f(grad_y), f(x), f(y_relu), f(save_mean),
                        f(save_rstd), static_cast<double*>(workspace), N, C, HW, dy_ctot, dy_coff, x_ctot, x_coff, y_ctot,
                        y_coff);

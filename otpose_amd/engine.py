@@ -1133,6 +1133,45 @@ class InferenceEngine:
             x = self.rsb_block(blk, x)
         return x
 
+    # ---- RSN attention / weight vector (reference model/RSB.py:142-203, csrc/prm.hip) -----------------
+    def _prm_front(self, layer, x: View) -> View:
+        """The leading 3x3 conv-BN-ReLU through :meth:`conv`, the route of the RSB convs."""
+        n, _, h, w = x.t.shape
+        ops.check_prm(layer.conv.out_channels, h, w)
+        f = View(self.new(n, layer.conv.out_channels, h, w))
+        return self.conv(x, layer.conv.weight, f, 1, 1, 1, bn=layer.bn, bias=layer.conv.bias, act=ACT_RELU)
+
+    def _prm_layer(self, layer, taps):
+        folded = ops.prm_layer(layer, taps, self.dev)
+        self._keep += list(folded)
+        return folded
+
+    def _prm_gate(self, f: View, l1, l2, residual):
+        gate = self.new(f.t.shape[0], f.C, 1, 1)
+        self.call(self.lib.otp_prm_gate, "otp_prm_gate",
+                  *ops.prm_gate_args(f.t, self._prm_layer(l1, f.C), self._prm_layer(l2, f.C), gate, residual))
+        return gate
+
+    def rsn_attention(self, m, x: View) -> View:
+        """``modules.RSN_ATTENTION`` on the stream being emitted on: the 3x3 conv, otp_prm_gate, otp_prm_apply."""
+        f = self._prm_front(m.conv_bn_relu_prm_1, x)
+        gate = self._prm_gate(f, m.conv_bn_relu_prm_2_1, m.conv_bn_relu_prm_2_2, False)
+        out = View(self.new(*f.t.shape))
+        self.call(self.lib.otp_prm_apply, "otp_prm_apply",
+                  *ops.prm_apply_args(f.t, gate, self._prm_layer(m.conv_bn_relu_prm_3_1, f.C),
+                                      self._prm_layer(m.conv_bn_relu_prm_3_2, 81), out.t))
+        return out
+
+    def rsn_weight_vector(self, m, x: View):
+        """``modules.RSN_WEIGHT_VECTOR`` -> the (N, C, 1, 1) gate tensor."""
+        f = self._prm_front(m.conv_bn_relu_1, x)
+        return self._prm_gate(f, m.conv_bn_relu_2, m.conv_bn_relu_3, True)
+
+    def _prm_after(self, name, x: View) -> View:
+        """Extension key MODEL.PRM: the chain's output through the model's ``<name>_prm`` module when it has one."""
+        m = getattr(self.model, name, None)
+        return x if m is None else self.rsn_attention(m, x)
+
     # ---- whole forward ------------------------------------------------------------------------------
     def _build(self):
         m, B, J, h, w = self.model, self.B, self.J, self.h, self.w
@@ -1152,7 +1191,7 @@ class InferenceEngine:
         # def_fuse only needs `total`: it runs on a side stream next to the flow encoder and the temporal encoders
         self.fork((2,))
         self.on_stream(2)
-        def_h = self.rsb_chain(m.def_fuse, View(total))
+        def_h = self._prm_after("def_fuse_prm", self.rsb_chain(m.def_fuse, View(total)))
         self.on_stream(0)
         self.conv_transformer(m.flow_encoder, flow_in, ctx)
         D = m.num_frames * J                       # stacked maps per joint: 8 (5-frame window) or 12 (7 frames)
@@ -1195,6 +1234,7 @@ class InferenceEngine:
         self.on_stream(0)
         self.join((1, 2))
         trans = self.rsb_chain(m.offset_mask_combine_conv, View(cat3))
+        trans = self._prm_after("offset_mask_combine_prm", trans)
         out = self.new(B, J, h, w)
         nd = len(m.deformable_conv_dilations)
         dils = [int(d) for d in m.deformable_conv_dilations]

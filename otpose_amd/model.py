@@ -14,7 +14,7 @@ import os
 import torch
 from torch import nn
 
-from .modules import (CHAIN_RSB_BLOCKS, ConvTransformer, HRNet, _Container)
+from .modules import (CHAIN_RSB_BLOCKS, RSN_ATTENTION, ConvTransformer, HRNet, _Container)
 from . import ops
 
 
@@ -161,6 +161,13 @@ class OTPose(nn.Module):
         def_ch, n_blocks = m.DEFORMABLE_CONV_CH, m.OFFSET_MASK_COMBINE_CONV
         self.offset_mask_combine_conv = CHAIN_RSB_BLOCKS(self.num_joints * 3, def_ch, n_blocks)
         self.def_fuse = CHAIN_RSB_BLOCKS(self.num_joints, self.num_joints, n_blocks)
+        # extension key MODEL.PRM: the output of a named chain goes through an RSN_ATTENTION of its channel count (RSB.py:168-203, a
+        # class the reference exports and never calls); () = the reference's model
+        self.prm = self._prm_keys(get("PRM", ()))
+        if "def_fuse" in self.prm:
+            self.def_fuse_prm = RSN_ATTENTION(self.num_joints)
+        if "offset_mask_combine_conv" in self.prm:
+            self.offset_mask_combine_prm = RSN_ATTENTION(def_ch)
         k, j = 3, self.num_joints
         self.offsets_list = nn.ModuleList(
             [nn.Sequential(_plain_conv(def_ch, j * 2 * k * k, dd)) for dd in self.deformable_conv_dilations])
@@ -194,6 +201,16 @@ class OTPose(nn.Module):
                 check_local_length(t if self.num_patches % 2 ** i == 0 else 0, s,
                                    f"{key}[{i}]: level {i} of the {self.pe_w}x{self.pe_h} heat-map: sequence length")
         return sizes
+
+    PRM_CHAINS = ("def_fuse", "offset_mask_combine_conv")
+
+    @classmethod
+    def _prm_keys(cls, value):
+        """MODEL.PRM validated: a tuple / list of distinct names out of :attr:`PRM_CHAINS`."""
+        if not isinstance(value, (tuple, list)) or any(not isinstance(v, str) or v not in cls.PRM_CHAINS for v in value) \
+                or len(set(value)) != len(value):
+            raise ValueError(f"MODEL.PRM must be a tuple of distinct names out of {cls.PRM_CHAINS}, got {value!r}")
+        return tuple(value)
 
     def _embd_keys(self, get, d):
         """The conv embedding keys of the cfg, validated: {} at the defaults (no layer anywhere), else the layer counts and the

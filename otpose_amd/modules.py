@@ -395,9 +395,10 @@ class ConvTransformer(_Container):
 # RSB heads (reference model/RSB.py)
 # ----------------------------------------------------------------------------------------------
 class conv_bn_relu(_Container):  # noqa: N801 - reference class name
-    def __init__(self, in_planes, out_planes, kernel_size, stride, padding, has_bn=True, has_relu=True):
+    def __init__(self, in_planes, out_planes, kernel_size, stride, padding, has_bn=True, has_relu=True, efficient=False, groups=1):
         super().__init__()
-        self.conv = nn.Conv2d(in_planes, out_planes, kernel_size, stride, padding)  # bias=True
+        # ``efficient`` is the reference's activation checkpointing (RSB.py:134-135): accepted, nothing to do here
+        self.conv = nn.Conv2d(in_planes, out_planes, kernel_size, stride, padding, groups=groups)  # bias=True
         self.bn = nn.BatchNorm2d(out_planes)
         self.has_bn, self.has_relu = has_bn, has_relu
 
@@ -426,3 +427,42 @@ class CHAIN_RSB_BLOCKS(_Container):  # noqa: N801
         blocks = [RSB_BLOCK(in_planes, out_planes, 1, downsample=down)]
         blocks += [RSB_BLOCK(out_planes, out_planes, 1) for _ in range(1, num_blocks)]
         self.layers = nn.Sequential(*blocks)
+
+
+PRM_MAX_CHANNELS = 64                               # what csrc/prm.hip takes (otp_prm_supported)
+
+
+def check_prm_channels(c, what):
+    """Raise ``ValueError`` unless ``c`` is a channel count the PRM kernels take."""
+    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 1 <= c <= PRM_MAX_CHANNELS:
+        raise ValueError(f"{what}: the channel count must be an int in 1 .. {PRM_MAX_CHANNELS}, got {c!r}")
+
+
+class RSN_WEIGHT_VECTOR(_Container):  # noqa: N801
+    """reference model/RSB.py:142-165: 3x3 conv-BN-ReLU, global average pool, two 1x1 conv-BN-ReLU with an inner residual, sigmoid
+    -> (N, C, 1, 1) (``ops.rsn_weight_vector``, csrc/prm.hip)."""
+
+    def __init__(self, input_chn_num, output_chl_num):
+        super().__init__()
+        check_prm_channels(output_chl_num, "RSN_WEIGHT_VECTOR")
+        self.input_chm_num, self.output_chl_num = input_chn_num, output_chl_num
+        c = output_chl_num
+        self.conv_bn_relu_1 = conv_bn_relu(input_chn_num, c, 3, 1, 1)
+        self.conv_bn_relu_2 = conv_bn_relu(c, c, 1, 1, 0)
+        self.conv_bn_relu_3 = conv_bn_relu(c, c, 1, 1, 0)
+
+
+class RSN_ATTENTION(_Container):  # noqa: N801
+    """reference model/RSB.py:168-203, RSN's Pose Refine Machine: f = 3x3 conv-BN-ReLU; a channel gate (global average pool, two
+    1x1 conv-BN-ReLU, sigmoid); a spatial gate (1x1 conv-BN-ReLU, depthwise 9x9 conv-BN-ReLU, sigmoid); f (1 + gate_c gate_s)
+    (``ops.rsn_attention``, csrc/prm.hip)."""
+
+    def __init__(self, output_chl_num, efficient=False):
+        super().__init__()
+        check_prm_channels(output_chl_num, "RSN_ATTENTION")
+        self.output_chl_num = c = output_chl_num
+        self.conv_bn_relu_prm_1 = conv_bn_relu(c, c, 3, 1, 1)
+        self.conv_bn_relu_prm_2_1 = conv_bn_relu(c, c, 1, 1, 0)
+        self.conv_bn_relu_prm_2_2 = conv_bn_relu(c, c, 1, 1, 0)
+        self.conv_bn_relu_prm_3_1 = conv_bn_relu(c, c, 1, 1, 0)
+        self.conv_bn_relu_prm_3_2 = conv_bn_relu(c, c, 9, 1, 4, groups=c)

@@ -298,7 +298,8 @@ def reference_param_groups(model, cfg):
     from . import modules as M
     from .model import DeformableCONV
 
-    white = (nn.Linear, nn.Conv1d, DeformableCONV, M.CHAIN_RSB_BLOCKS, nn.ConvTranspose1d)
+    # RSN_ATTENTION: the MODEL.PRM modules go where the chains they follow go (def_fuse_prm.* also matches the prefix rule below)
+    white = (nn.Linear, nn.Conv1d, DeformableCONV, M.CHAIN_RSB_BLOCKS, M.RSN_ATTENTION, nn.ConvTranspose1d)
     black = (M.LayerNorm, nn.GroupNorm)
     decay, no_decay, pretrained = set(), set(), set()
     for mn, m in model.named_modules():

@@ -461,6 +461,37 @@ class TrainGraph:
             i += 1
         return x
 
+    # ---- RSN attention / weight vector (model/RSB.py:142-203), batch statistics layer by layer ------------------------------
+    def _prm_batch(self, p, x):
+        """The gate layers normalise (N, C, 1, 1) tensors: N values per channel.  ``nn.BatchNorm2d`` refuses one value per channel
+        in training mode, and so does this, before any launch."""
+        if x.dim() != 4 or x.shape[0] < 2:
+            raise ValueError(f"{p}: Expected more than 1 value per channel when training, got input size "
+                             f"{[int(x.shape[0]), int(x.shape[1]), 1, 1]} (the BatchNorm of the channel gate; eval mode takes N = 1)")
+
+    def rsn_attention(self, p, x):
+        """f (1 + sigmoid(gate_c) sigmoid(gate_s)) of RSB.py:192-203; both gates end in a ReLU in front of their sigmoid."""
+        self._prm_batch(p, x)
+        f = self.cbr(p + ".conv_bn_relu_prm_1", x, 1)
+        a = self.cbr(p + ".conv_bn_relu_prm_2_1", T.spatial_mean(f), 0)
+        a = self.cbr(p + ".conv_bn_relu_prm_2_2", a, 0)
+        s = self.cbr(p + ".conv_bn_relu_prm_3_1", f, 0)
+        q = p + ".conv_bn_relu_prm_3_2"
+        s = self.bn(q + ".bn", T.dwconv2d(s, self.P[q + ".conv.weight"], self.P.get(q + ".conv.bias")), None, True)
+        return T.prm_combine(f, a, s)
+
+    def rsn_weight_vector(self, p, x):
+        """RSB.py:158-165 -> (N, C, 1, 1)."""
+        self._prm_batch(p, x)
+        o0 = T.spatial_mean(self.cbr(p + ".conv_bn_relu_1", x, 1))
+        o1 = self.cbr(p + ".conv_bn_relu_2", o0, 0)
+        return torch.sigmoid(self.cbr(p + ".conv_bn_relu_3", o1 + o0, 0))
+
+    def prm_after(self, p, x):
+        """Extension key MODEL.PRM: the output of chain ``p`` through the RSN_ATTENTION held as ``<p minus _conv>_prm``."""
+        q = (p[:-len("_conv")] if p.endswith("_conv") else p) + "_prm"
+        return self.rsn_attention(q, x) if self.has(q + ".conv_bn_relu_prm_1.conv.weight") else x
+
     # ---- dilated offset / mask convs in front of the DCNs (model/OTPose.py:168-177, 381-383) ---------------------------
     def offset_mask_input(self, trans):
         return trans
@@ -527,7 +558,7 @@ class TrainGraph:
         # of small fp32 launches, ~7 ms alone at a third of the chip) comes between encoder 2's and encoder 1's and overlaps with
         # encoder 1's on the other stream - emitted first it came last, alone, in front of the backbone's backward
         with torch.cuda.stream(st[2]):
-            def_h = self.rsb_chain("def_fuse", total_b)
+            def_h = self.prm_after("def_fuse", self.rsb_chain("def_fuse", total_b))
         t2 = self.conv_transformer("temporal_encoder2", x2, 2, (0, 6, 2))
         s2 = torch.stack(t2, 1).contiguous().view(B, -1, pe_h, pe_w)
         f2 = self.conv("final_layer2", s2, 1, fk // 2)
@@ -537,6 +568,7 @@ class TrainGraph:
             for t in (f1, def_h) + tuple(t1):
                 t.record_stream(main)
         trans = self.rsb_chain("offset_mask_combine_conv", torch.cat([f1, f2, def_h], 1))
+        trans = self.prm_after("offset_mask_combine_conv", trans)
         out = None
         if self.taps is not None:
             self.taps.update(x1=x1, x2=x2, t1_0=t1[0], t2_0=t2[0], f1=f1, f2=f2, def_h=def_h, trans=trans)

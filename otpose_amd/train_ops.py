@@ -712,6 +712,128 @@ def conv_embd(x, weight, bias, ln_weight, ln_bias, pe=None, eps=1e-5):
     return ConvEmbdFunction.apply(x, weight, bias, ln_weight, ln_bias, pe, eps)
 
 
+class SpatialMeanFunction(Function):
+    """``F.adaptive_avg_pool2d(x, (1, 1))``: (N, C, H, W) -> (N, C, 1, 1), thread-strided sums added in a fixed order
+    (csrc/prm.hip); the backward broadcasts ``g / (H W)``."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _require_gpu(x)
+        _check_f32(x)
+        if x.dim() != 4:
+            raise ValueError(f"spatial_mean: x must be (N, C, H, W), got {tuple(x.shape)}")
+        x = x.contiguous()
+        n, c, h, w = x.shape
+        out = torch.empty((n, c, 1, 1), dtype=torch.float32, device=x.device)
+        hip.check(hip.lib().otp_spatial_mean(hip.ptr(x), hip.ptr(out), n, c, h * w, hip.stream_of(x)), "otp_spatial_mean")
+        ctx.shape = tuple(x.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        n, c, h, w = ctx.shape
+        g = g.contiguous()
+        gx = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
+        hip.check(hip.lib().otp_spatial_mean_backward(hip.ptr(g), hip.ptr(gx), n, c, h * w, hip.stream_of(g)),
+                  "otp_spatial_mean_backward")
+        return gx
+
+
+def spatial_mean(x):
+    return SpatialMeanFunction.apply(x)
+
+
+DWCONV2D_KS = (9,)                    # the kernel sizes csrc/prm.hip instantiates
+
+
+class DwConv2dFunction(Function):
+    """``F.conv2d(x, w (C, 1, k, k), bias, 1, k // 2, 1, groups=C)`` for k = 9 (RSB.py:187-189).  The input gradient is the same
+    gather with the taps reversed, the weight gradient comes from per-workgroup partial sums added in a fixed order, the bias
+    gradient from ``channel_sum``: deterministic."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        _require_gpu(x, w)
+        _check_f32(x, w)
+        if x.dim() != 4 or w.dim() != 4 or w.shape[1] != 1 or w.shape[0] != x.shape[1] or w.shape[2] != w.shape[3]:
+            raise ValueError(f"dwconv2d: x must be (N, C, H, W) and w (C, 1, k, k), got {tuple(x.shape)} and {tuple(w.shape)}")
+        if w.shape[2] not in DWCONV2D_KS:
+            raise ValueError(f"dwconv2d: the kernel size must be one of {DWCONV2D_KS}, got {w.shape[2]}")
+        if bias is not None and bias.numel() != w.shape[0]:
+            raise ValueError(f"dwconv2d: bias has {bias.numel()} entries, the layer has {w.shape[0]} channels")
+        x, w = x.contiguous(), w.contiguous()
+        n, c, h, wd = x.shape
+        y = torch.empty_like(x)
+        b_ = None if bias is None else bias.detach().contiguous()
+        hip.check(hip.lib().otp_dwconv2d(hip.ptr(x), hip.ptr(w), hip.ptr(b_), hip.ptr(y), n, c, h, wd, w.shape[2], 0,
+                                         hip.stream_of(x)), "otp_dwconv2d")
+        ctx.save_for_backward(x, w)
+        ctx.params = (w, bias)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        pw, pb = ctx.params
+        n, c, h, wd = x.shape
+        ks = w.shape[2]
+        L = hip.lib()
+        gy = gy.contiguous()
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            hip.check(L.otp_dwconv2d(hip.ptr(gy), hip.ptr(w), None, hip.ptr(gx), n, c, h, wd, ks, 1, hip.stream_of(x)),
+                      "otp_dwconv2d")
+        if ctx.needs_input_grad[1]:
+            slot = grad_slot(pw)
+            gw = slot if slot is not None else torch.empty_like(w)
+            nbytes = L.otp_dwconv2d_wgrad_workspace(n, c, h, wd, ks)
+            ws = _workspace(x.device, nbytes)
+            hip.check(L.otp_dwconv2d_wgrad(hip.ptr(x), hip.ptr(gy), hip.ptr(gw), hip.ptr(ws), nbytes, n, c, h, wd, ks,
+                                           hip.stream_of(x)), "otp_dwconv2d_wgrad")
+        if pb is not None and ctx.needs_input_grad[2]:
+            gb = channel_sum(gy, grad_slot(pb))
+        return gx, gw, gb
+
+
+def dwconv2d(x, w, bias=None):
+    return DwConv2dFunction.apply(x, w, bias)
+
+
+class PrmCombineFunction(Function):
+    """``f * (1 + sigmoid(a) * sigmoid(s))`` (RSB.py:198, 201-202): f, s (N, C, H, W), a (N, C, 1, 1), both gates pre-sigmoid.
+    The backward is one launch; the per-(n, c) sum of grad_a runs in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, f, a, s):
+        _require_gpu(f, a, s)
+        _check_f32(f, a, s)
+        if f.dim() != 4 or s.shape != f.shape or a.numel() != f.shape[0] * f.shape[1]:
+            raise ValueError(f"prm_combine: f and s must be (N, C, H, W) and a (N, C, 1, 1), got {tuple(f.shape)}, {tuple(s.shape)}, "
+                             f"{tuple(a.shape)}")
+        f, a, s = f.contiguous(), a.contiguous(), s.contiguous()
+        n, c, h, w = f.shape
+        out = torch.empty_like(f)
+        hip.check(hip.lib().otp_prm_combine(hip.ptr(f), hip.ptr(a), hip.ptr(s), hip.ptr(out), n, c, h * w, hip.stream_of(f)),
+                  "otp_prm_combine")
+        ctx.save_for_backward(f, a, s)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        f, a, s = ctx.saved_tensors
+        n, c, h, w = f.shape
+        g = g.contiguous()
+        gf, ga, gs = torch.empty_like(f), torch.empty_like(a), torch.empty_like(s)
+        hip.check(hip.lib().otp_prm_combine_backward(hip.ptr(f), hip.ptr(a), hip.ptr(s), hip.ptr(g), hip.ptr(gf), hip.ptr(ga),
+                                                     hip.ptr(gs), n, c, h * w, hip.stream_of(f)), "otp_prm_combine_backward")
+        return gf, ga, gs
+
+
+def prm_combine(f, a, s):
+    return PrmCombineFunction.apply(f, a, s)
+
+
 class ScaleResidualFunction(Function):
     """``x + drop_path(scale * a)`` of a TransformerBlock (model/blocks.py:277-279, AffineDropPath :283-316): ``scale`` is the
     (1, C, 1) AffineDropPath parameter, ``mask`` (B,) the per-sample Bernoulli(keep) / keep factors (None: no drop-path)."""

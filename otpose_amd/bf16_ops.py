@@ -14,7 +14,7 @@ import torch
 from torch.autograd import Function
 
 from . import hip
-from .ops import _out_hw, _require_gpu
+from .ops import out_hw, require_gpu
 from .train_ops import TrainRoutes, channel_sum, current_routes, grad_slot
 
 BF16 = torch.bfloat16
@@ -36,7 +36,7 @@ def _new(shape, dtype, like):
 def to_nhwc(x: torch.Tensor, frame_split: int = 0) -> torch.Tensor:
     """(N, C, H, W) fp32 -> (N, H, W, CS) bf16.  ``frame_split = B``: ``x`` is the (B, 5*C', H, W) clip tensor read as
     (5B, C', H, W) in the reference's frame order (model/OTPose.py:317) without materialising the re-layout."""
-    _require_gpu(x)
+    require_gpu(x)
     x = x.contiguous()
     if x.dtype != torch.float32:
         raise TypeError("to_nhwc expects float32")
@@ -53,7 +53,7 @@ def to_nhwc(x: torch.Tensor, frame_split: int = 0) -> torch.Tensor:
 
 def to_nchw(x: torch.Tensor, c: int) -> torch.Tensor:
     """(N, H, W, CS) bf16 -> (N, c, H, W) fp32."""
-    _require_gpu(x)
+    require_gpu(x)
     n, h, w, _ = x.shape
     out = _new((n, c, h, w), torch.float32, x)
     hip.check(hip.lib().otp_nhwc_bf16_to_nchw_f32(hip.ptr(x.contiguous()), hip.ptr(out), n, c, h, w, hip.stream_of(x)),
@@ -168,7 +168,7 @@ def conv_forward(x, weight, bias=None, stride=1, pad=0, dil=1, out_mode=0, want_
     assert cins == cs(cin) and x.dtype == BF16 and x.is_contiguous()
     d = _desc(n, h, w, cin, cout, kh, kw, stride, pad, dil, out_mode)
     wp = _pack(weight.contiguous(), d, 0, packs)
-    ho, wo = _out_hw(h, w, kh, kw, stride, pad, dil)
+    ho, wo = out_hw(h, w, kh, kw, stride, pad, dil)
     L = hip.lib()
     stats, rows = None, 0
     if out_mode == 0:
@@ -328,7 +328,7 @@ def conv_bn_forward(x, weight, gamma, beta, res, running_mean, running_var, stri
     assert cins == cs(cin) and x.dtype == BF16 and x.is_contiguous()
     d = _desc(n, h, w, cin, cout, kh, kw, stride, pad, 1, 0)
     wp = _pack(weight.contiguous(), d, 0, packs)
-    ho, wo = _out_hw(h, w, kh, kw, stride, pad, 1)
+    ho, wo = out_hw(h, w, kh, kw, stride, pad, 1)
     L = hip.lib()
     csz = cs(cout)
     c = _new((n, ho, wo, csz), BF16, x)
@@ -349,7 +349,7 @@ class ConvBnFunction(Function):
 
     @staticmethod
     def forward(ctx, x, weight, gamma, beta, res, running_mean, running_var, stride, pad, relu, momentum, eps):
-        _require_gpu(x, weight, gamma, beta)
+        require_gpu(x, weight, gamma, beta)
         x = x.contiguous()
         cout = weight.shape[0]
         ctx.packs, ctx.routes = _ACTIVE_PACKS, current_routes()
@@ -387,7 +387,7 @@ class BasicBlockFunction(Function):
 
     @staticmethod
     def forward(ctx, x, w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, momentum, eps):
-        _require_gpu(x, w1, w2)
+        require_gpu(x, w1, w2)
         x = x.contiguous()
         ctx.packs, ctx.routes = _ACTIVE_PACKS, current_routes()
         c1, m1, vec1, y1 = conv_bn_forward(x, w1, g1, b1, None, rm1, rv1, 1, 1, True, momentum, eps, ctx.packs)
@@ -424,7 +424,7 @@ class ConvOutFunction(Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, pad, dil):
-        _require_gpu(x, weight)
+        require_gpu(x, weight)
         x = x.contiguous()
         ctx.packs, ctx.routes = _ACTIVE_PACKS, current_routes()
         out, _, _ = conv_forward(x, weight, bias, stride, pad, dil, out_mode=1, packs=ctx.packs)
@@ -454,7 +454,7 @@ class UpsampleAddFunction(Function):
 
     @staticmethod
     def forward(ctx, low, res, f, relu):
-        _require_gpu(low, res)
+        require_gpu(low, res)
         low, res = low.contiguous(), res.contiguous()
         n, h, w, c = res.shape
         out = torch.empty_like(res)
@@ -501,7 +501,7 @@ class ConvBiasFunction(Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, pad, dil):
-        _require_gpu(x, weight)
+        require_gpu(x, weight)
         x = x.contiguous()
         ctx.packs, ctx.routes = _ACTIVE_PACKS, current_routes()
         out, _, _ = conv_forward(x, weight, bias, stride, pad, dil, out_mode=0, want_stats=False, packs=ctx.packs)
@@ -531,7 +531,7 @@ class GeluFunction(Function):
 
     @staticmethod
     def forward(ctx, x):
-        _require_gpu(x)
+        require_gpu(x)
         x = x.contiguous()
         y = torch.empty_like(x)
         hip.check(hip.lib().otp_gelu_bf16_forward(hip.ptr(x), hip.ptr(y), x.numel(), hip.stream_of(x)), "otp_gelu_bf16_forward")
@@ -565,7 +565,7 @@ class GeluDropoutFunction(Function):
 
     @staticmethod
     def forward(ctx, x, p, seed):
-        _require_gpu(x)
+        require_gpu(x)
         x = x.contiguous()
         y = torch.empty_like(x)
         keep = torch.empty(x.numel() // 8, dtype=torch.uint8, device=x.device)
@@ -600,7 +600,7 @@ class MlpInteriorFunction(Function):
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, p, seed):
-        _require_gpu(x, w1, w2)
+        require_gpu(x, w1, w2)
         x = x.contiguous()
         n, h, w, _ = x.shape
         hid, cin = w1.shape[:2]

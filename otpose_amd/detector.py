@@ -89,7 +89,7 @@ class _Plan:
                 pad = (k - 1) // 2 if int(d["pad"]) else 0
                 if d["activation"] not in ("leaky", "linear"):
                     raise NotImplementedError(f"Darknet block {i}: activation {d['activation']!r}")
-                ho, wo = ops._out_hw(prev[1], prev[2], k, k, s, pad, 1)
+                ho, wo = ops.out_hw(prev[1], prev[2], k, k, s, pad, 1)
                 self.shape.append((int(d["filters"]), ho, wo))
                 self.src.append([i - 1])
             elif t == "upsample":
@@ -259,8 +259,8 @@ class PersonDetector(nn.Module):
     def forward(self, x, return_heads=False):
         """The reference's eval output (B, N, 5 + C) for a letterboxed batch ``x`` (B, channels, img_size, img_size); with
         ``return_heads`` also the list of the raw maps the yolo layers decode."""
-        ops._require_gpu(x)
-        ops._check_f32(x)
+        ops.require_gpu(x)
+        ops.check_f32(x)
         c = int(self.hyperparams.get("channels", 3))
         if x.dim() != 4 or tuple(x.shape[1:]) != (c, self.img_size, self.img_size):
             raise ValueError(f"x must be (B, {c}, {self.img_size}, {self.img_size}), got {tuple(x.shape)}")

@@ -1014,7 +1014,7 @@ class InferenceEngine:
         if getattr(a, "window_size", 0) > 1:
             B, C, T = q.shape
             ops.check_local_attn(C, T, a.n_head, a.window_size)
-            rel = ops._rel_pe_table(getattr(a, "rel_pe", None), a.n_head, a.window_size, q)
+            rel = ops.rel_pe_table(getattr(a, "rel_pe", None), a.n_head, a.window_size, q)
             if rel is not None:
                 self._keep.append(rel)
             self.call(self.lib.otp_local_attn, "otp_local_attn",

@@ -39,8 +39,8 @@ def _whole(segs):
 
 
 def _check(segs, scores, cls_idxs=None):
-    ops._require_gpu(segs, scores, cls_idxs)
-    ops._check_f32(segs, scores)
+    ops.require_gpu(segs, scores, cls_idxs)
+    ops.check_f32(segs, scores)
 
 
 def _empty(segs, cls_idxs):

@@ -91,7 +91,7 @@ class JointsMseLossFunction(Function):
 
     @staticmethod
     def forward(ctx, o, g, w, ohkm, topk, eff):
-        res, go = ops._joints_mse(o, g, w, topk, ohkm, eff, True)
+        res, go = ops.joints_mse(o, g, w, topk, ohkm, eff, True)
         ctx.save_for_backward(go)
         ctx.mark_non_differentiable(res)
         return res[2].clone(), res

@@ -16,7 +16,7 @@ import torch
 from torch.autograd import Function
 
 from . import hip, ops
-from .ops import (ACT_NONE, View, _check_f32, _out_hw, _require_gpu, conv2d_launch, conv2d_wino_launch, conv_desc,
+from .ops import (ACT_NONE, View, check_f32, out_hw, require_gpu, conv2d_launch, conv2d_wino_launch, conv_desc,
                   pack_conv_weight, pack_wino_weight)
 
 
@@ -99,7 +99,7 @@ def conv_route(routes, cin, cout, d, hw):
 def conv2d_forward(x, weight, bias, stride, pad, dil, routes=None):
     routes = routes or TrainRoutes.from_env()
     cout, cin, kh, kw = weight.shape
-    ho, wo = _out_hw(x.shape[2], x.shape[3], kh, kw, stride, pad, dil)
+    ho, wo = out_hw(x.shape[2], x.shape[3], kh, kw, stride, pad, dil)
     out = torch.empty((x.shape[0], cout, ho, wo), dtype=torch.float32, device=x.device)
     iv, ov = View(x), View(out)
     d = conv_desc(iv, ov, cout, kh, kw, stride, pad, dil, ACT_NONE)
@@ -201,8 +201,8 @@ class Conv2dFunction(Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, pad, dil):
-        _require_gpu(x, weight)
-        _check_f32(x, weight)
+        require_gpu(x, weight)
+        check_f32(x, weight)
         x, weight = x.contiguous(), weight.contiguous()
         ctx.save_for_backward(x, weight)
         ctx.cfg = (stride, pad, dil, bias is not None)
@@ -234,8 +234,8 @@ class BatchNormReluFunction(Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, res, running_mean, running_var, momentum, eps, relu):
-        _require_gpu(x, gamma, beta)
-        _check_f32(x, gamma, beta)
+        require_gpu(x, gamma, beta)
+        check_f32(x, gamma, beta)
         x = x.contiguous()
         n, c, h, w = x.shape
         L = hip.lib()
@@ -323,8 +323,8 @@ class LayerNormFunction(Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps):
-        _require_gpu(x)
-        _check_f32(x)
+        require_gpu(x)
+        check_f32(x)
         x = x.contiguous()
         g, be = gamma.reshape(-1).contiguous(), beta.reshape(-1).contiguous()
         y = _ln_fwd(x, g, be, eps)
@@ -367,7 +367,7 @@ class DwConv3Function(Function):
 
     @staticmethod
     def forward(ctx, x, w, stride):
-        _require_gpu(x, w)
+        require_gpu(x, w)
         x, w = x.contiguous(), w.contiguous()
         y = _dw_fwd(x, w, stride)
         ctx.save_for_backward(x, w)
@@ -396,8 +396,8 @@ class AttnFrontFunction(Function):
 
     @staticmethod
     def forward(ctx, x, stride, eps, g1, b1, *bp):
-        _require_gpu(x)
-        _check_f32(x)
+        require_gpu(x)
+        check_f32(x)
         x = x.contiguous()
         ctx.cfg = (stride, eps)
         ctx.params = (g1, b1) + tuple(bp)
@@ -453,7 +453,7 @@ def attn_front(x, stride, eps, ln1, branches):
 class GeluFunction(Function):
     @staticmethod
     def forward(ctx, x):
-        _require_gpu(x)
+        require_gpu(x)
         x = x.contiguous()
         y = torch.empty_like(x)
         hip.check(hip.lib().otp_gelu_forward(hip.ptr(x), hip.ptr(y), x.numel(), hip.stream_of(x)), "otp_gelu_forward")
@@ -477,7 +477,7 @@ class MaxPool3s2Function(Function):
 
     @staticmethod
     def forward(ctx, x):
-        _require_gpu(x)
+        require_gpu(x)
         x = x.contiguous()
         b, c, t = x.shape
         y = torch.empty((b, c, (t + 2 - 3) // 2 + 1), dtype=torch.float32, device=x.device)
@@ -504,7 +504,7 @@ class UpsampleLinearFunction(Function):
 
     @staticmethod
     def forward(ctx, x, f):
-        _require_gpu(x)
+        require_gpu(x)
         x = x.contiguous()
         b, c, t = x.shape
         y = torch.empty((b, c, t * f), dtype=torch.float32, device=x.device)
@@ -533,7 +533,7 @@ class ChanAttnFunction(Function):
 
     @staticmethod
     def forward(ctx, q, k, v, n_head, scale):
-        _require_gpu(q, k, v)
+        require_gpu(q, k, v)
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         b, c, t = q.shape
         L = hip.lib()
@@ -592,12 +592,12 @@ class LocalAttnFunction(Function):
 
     @staticmethod
     def forward(ctx, q, k, v, rel_pe, n_head, window_size, scale):
-        _require_gpu(q, k, v)
-        _check_f32(q, k, v)
+        require_gpu(q, k, v)
+        check_f32(q, k, v)
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         b, c, t = q.shape
         ops.check_local_attn(c, t, n_head, window_size)
-        rel = ops._rel_pe_table(rel_pe, n_head, window_size, q)
+        rel = ops.rel_pe_table(rel_pe, n_head, window_size, q)
         out = torch.empty_like(q)
         probs = torch.empty((b * n_head, t, window_size), dtype=torch.float32, device=q.device)
         hip.check(hip.lib().otp_local_attn(*ops.local_attn_args(q, k, v, rel, out, probs, n_head, window_size, scale),
@@ -652,8 +652,8 @@ class ConvEmbdFunction(Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, ln_weight, ln_bias, pe, eps):
-        _require_gpu(x, weight)
-        _check_f32(x, weight)
+        require_gpu(x, weight)
+        check_f32(x, weight)
         check_conv_embd_train(weight.shape)
         x, weight = x.contiguous(), weight.contiguous()
         b_, gamma, beta, pe_ = ops.conv_embd_params(x.shape, weight, bias, ln_weight, ln_bias, pe, x.device)
@@ -718,8 +718,8 @@ class SpatialMeanFunction(Function):
 
     @staticmethod
     def forward(ctx, x):
-        _require_gpu(x)
-        _check_f32(x)
+        require_gpu(x)
+        check_f32(x)
         if x.dim() != 4:
             raise ValueError(f"spatial_mean: x must be (N, C, H, W), got {tuple(x.shape)}")
         x = x.contiguous()
@@ -753,8 +753,8 @@ class DwConv2dFunction(Function):
 
     @staticmethod
     def forward(ctx, x, w, bias):
-        _require_gpu(x, w)
-        _check_f32(x, w)
+        require_gpu(x, w)
+        check_f32(x, w)
         if x.dim() != 4 or w.dim() != 4 or w.shape[1] != 1 or w.shape[0] != x.shape[1] or w.shape[2] != w.shape[3]:
             raise ValueError(f"dwconv2d: x must be (N, C, H, W) and w (C, 1, k, k), got {tuple(x.shape)} and {tuple(w.shape)}")
         if w.shape[2] not in DWCONV2D_KS:
@@ -806,8 +806,8 @@ class PrmCombineFunction(Function):
 
     @staticmethod
     def forward(ctx, f, a, s):
-        _require_gpu(f, a, s)
-        _check_f32(f, a, s)
+        require_gpu(f, a, s)
+        check_f32(f, a, s)
         if f.dim() != 4 or s.shape != f.shape or a.numel() != f.shape[0] * f.shape[1]:
             raise ValueError(f"prm_combine: f and s must be (N, C, H, W) and a (N, C, 1, 1), got {tuple(f.shape)}, {tuple(s.shape)}, "
                              f"{tuple(a.shape)}")
@@ -840,8 +840,8 @@ class ScaleResidualFunction(Function):
 
     @staticmethod
     def forward(ctx, x, a, scale, mask):
-        _require_gpu(x, a, scale)
-        _check_f32(x, a)
+        require_gpu(x, a, scale)
+        check_f32(x, a)
         x, a = x.contiguous(), a.contiguous()
         b, c, t = x.shape
         sc = scale.reshape(-1).contiguous()

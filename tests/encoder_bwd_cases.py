@@ -88,7 +88,7 @@ LN_SPLIT_MAX_C = 136
 
 
 def ln_branch(c, t, direct=False):
-    """``direct``: otp_ln_channel_backward (dx and dy * xhat out); else otp_ln_channel_backward_params as train_ops._ln_bwd calls
+    """``direct``: otp_ln_channel_backward (dx and dy * xhat out); else otp_ln_channel_backward_params as ``_ln_bwd`` of train_ops calls
     it whenever the library reports a workspace (C <= 136).  tiles = workgroups along T; last = tokens of the last one; the
     channel split over the waves as (channels per wave, channels of the last non-empty wave, empty waves)."""
     if c > LN_SPLIT_MAX_C:

@@ -75,7 +75,7 @@ def test_direct_pack_and_job_table_pack_write_the_same_bits(case, dgrad, monkeyp
 def test_sizes_packer_and_launch_take_the_same_descriptors(case, hb, monkeypatch):
     from otpose_amd import hip
     from otpose_amd.bf16_ops import cs
-    from otpose_amd.ops import _out_hw
+    from otpose_amd.ops import out_hw
     cin, cout, k, stride, pad, dil, h, w, _ = case
     _set_hb(monkeypatch, hb)
     L = hip.lib()
@@ -87,7 +87,7 @@ def test_sizes_packer_and_launch_take_the_same_descriptors(case, hb, monkeypatch
     wp = torch.zeros(max(nbytes, 1 << 20) // 2, dtype=BF, device=_dev())
     rc = L.otp_nhwc_conv_pack(hip.ptr(wt), hip.ptr(wp), ctypes.byref(d), 0, hip.stream_of(wt))
     assert (nbytes != 0) == (rc == hip.OTP_OK), (nbytes, rc)
-    ho, wo = _out_hw(h, w, k, k, stride, pad, dil)
+    ho, wo = out_hw(h, w, k, k, stride, pad, dil)
     x = torch.randn(1, h, w, cs(cin), generator=g).to(BF).to(_dev())
     out = torch.zeros(1, max(ho, 1), max(wo, 1), cs(cout), dtype=BF, device=_dev())
     extra = 8

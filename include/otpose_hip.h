@@ -430,6 +430,26 @@ size_t otp_local_attn_backward_workspace(int B, int C, int T, int n_head, int wi
 int otp_local_attn_backward(const void* q, const void* k, const void* v, const void* probs, const void* gout, void* gq, void* gk,
                             void* gv, void* grel, void* ws, size_t ws_bytes, int B, int C, int T, int n_head, int window,
                             float scale, void* stream);
+/* token x token self-attention of the DETR-style TransformerEncoder (OTPose.py:26-159; csrc/tokattn.hip), flash style in exact
+ * fp32 (f32 MFMA = an fmaf chain): q, k, v (B, C, T) viewed as (B, nh, hd, T), head h owns channels h hd .. (h + 1) hd - 1,
+ *   S[i][j] = scale * sum_c q[c][i] k[c][j],  P = softmax_j(S),  out[c][i] = sum_j P[i][j] v[c][j]          (out (B, C, T))
+ * with online softmax over 64-key tiles: no buffer grows with T^2 except the explicit map.  key_mask: NULL or (B, T) uint8,
+ * 1 = this key is padding (it gets -inf before the maximum).  lse (B, nh, T) receives the row log-sum-exp; NULL when neither
+ * a backward nor a map follows.  A sample whose keys are ALL masked is outside the contract (its rows divide by zero).
+ * otp_token_attn_backward: dq, dk, dv (B, C, T) from two launches, deterministic and atomic-free (every word has one writer;
+ * masked keys receive exactly zero dk / dv); workspace: otp_token_attn_workspace(B, nh, T, hd) = 4 B nh T bytes, the row sums
+ * D = sum_c dout o out.  otp_token_attn_map: map (B, T, T) = mean over heads of P = exp(S - lse), one pass.
+ * Supported (otp_token_attn_supported: 1 / 0): C % nh == 0, 1 <= hd = C / nh <= 136, 1 <= T <= 2^30; anything else - and a NULL
+ * required pointer or B <= 0 - is OTP_ERR_BAD_ARG before any launch; more than 2^31 - 1 workgroups is OTP_ERR_UNSUPPORTED. */
+int otp_token_attn_supported(int C, int nh, int T);
+size_t otp_token_attn_workspace(int B, int nh, int T, int hd);
+int otp_token_attn_forward(const void* q, const void* k, const void* v, const void* key_mask, void* out, void* lse, int B, int C,
+                           int nh, int T, float scale, void* stream);
+int otp_token_attn_backward(const void* q, const void* k, const void* v, const void* key_mask, const void* out, const void* lse,
+                            const void* dout, void* dq, void* dk, void* dv, void* workspace, int B, int C, int nh, int T,
+                            float scale, void* stream);
+int otp_token_attn_map(const void* q, const void* k, const void* key_mask, const void* lse, void* map, int B, int C, int nh, int T,
+                       float scale, void* stream);
 /* conv embedding layer of ConvTransformer (ConvVideoTransformer.py:60-78, 129-135; csrc/convembd.hip) as one launch, exact fp32
  * (f32 MFMA = an fmaf chain; mean first, then the centred sum of squares, cross-wave sums in a fixed order):
  *   z = Conv2d(Cin, Cout, ks, stride 1, padding ks / 2)(x),  x (B, Cin, H, W), zero padding;  v = z + bias[c] (bias may be NULL)

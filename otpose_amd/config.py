@@ -20,6 +20,13 @@ LayerNorm behind each convolution and no conv bias).  Training takes ``EMBD_KS``
 ``("def_fuse", "offset_mask_combine_conv")``, default ``()``): the output of a named RSB chain passes through an ``RSN_ATTENTION`` of
 its channel count (reference model/RSB.py:168-203, RSN's Pose Refine Machine), held as ``def_fuse_prm`` /
 ``offset_mask_combine_prm``.  The reference exports that class and has no call site for it: the placement is this package's.
+The token encoders (reference model/OTPose.py:26-159, the DETR-style ``TransformerEncoder`` it exports and never calls):
+``MODEL.TOKEN_LAYERS`` (int, 0 = none) puts one of that many layers in front of each temporal encoder (``token_encoder1`` /
+``token_encoder2``, over the h w tokens of width 8 J), ``MODEL.FLOW_TOKEN_LAYERS`` (0) in front of the flow encoder
+(``flow_token_encoder``, width J, one head, FFN 2 J); ``MODEL.TOKEN_HEADS`` (2; divides the width, heads of at most 136 channels),
+``MODEL.TOKEN_FFN`` (2 x the width), ``MODEL.TOKEN_PRE_NORM`` (False), ``MODEL.TOKEN_PE`` (``"sine"``, ``"learnable"`` or
+``"none"``: the tables ``temporal_pos_embedding`` / ``flow_pos_embedding`` of OTPose.py:259-279; with ``"sine"`` the flow encoder
+runs without a table, width J = 17 has none).  A malformed value raises ``ValueError`` also when no layer is asked for.
 """
 from __future__ import annotations
 

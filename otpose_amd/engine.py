@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import ctypes
 import dataclasses
+import math
 import os
 import sys
 import warnings
@@ -1069,6 +1070,63 @@ class InferenceEngine:
             x, cin = out, C
         return x
 
+    def _ln(self, norm, x):
+        B, C, T = x.shape
+        y = self.new(B, C, T)
+        p = self.dev_param
+        self.call(self.lib.otp_ln_channel, "otp_ln_channel", hip.ptr(x), hip.ptr(p(norm.weight)), hip.ptr(p(norm.bias)), hip.ptr(y),
+                  None, B, C, T, norm.eps)
+        return y
+
+    def token_encoder(self, name, pos_name, x):
+        """Extension keys MODEL.TOKEN_LAYERS / FLOW_TOKEN_LAYERS: the model's ``modules.TransformerEncoder`` ``name`` (eval mode)
+        on x (B, C, T) as T tokens of width C, when the model has one; else x itself and no launch.  Per layer: three 1x1
+        projections, ``otp_token_attn_forward``, the out-projection with the residual in its epilogue, the two channel
+        LayerNorms, and the FFN as two 1x1 convolutions with bias + activation / bias + residual epilogues.  ``pos`` goes to
+        q and k only; W (x + pos) + b is launched as W x + b + (W pos), the last term a table built once per engine and added
+        as the epilogue's residual, so the sum x + pos never costs a pass of its own."""
+        enc = getattr(self.model, name, None)
+        if enc is None:
+            return x
+        B, C, T = x.shape
+        pos = getattr(self.model, pos_name, None)
+        if pos is not None:
+            if pos.shape[1] != T:
+                raise ValueError(f"{pos_name}: a table of {pos.shape[1]} tokens for {T} tokens")
+            pos = pos.detach().to(self.dev, torch.float32)[0].t().contiguous()                   # (C, T)
+        for layer in enc.layers:
+            a, E = layer.self_attn, layer.d_model
+            w, b = a.in_proj_weight.detach(), a.in_proj_bias.detach()
+            src = self._ln(layer.norm1, x) if layer.normalize_before else x
+            q, k, v, att, y = (self.new(B, C, T) for _ in range(5))
+            for out, lo in ((q, 0), (k, E)):
+                res = None
+                if pos is not None:
+                    res = (w[lo:lo + E].to(self.dev, torch.float32) @ pos).unsqueeze(0).expand(B, C, T).contiguous()
+                    self._keep.append(res)
+                self.conv(self.v3(src), w[lo:lo + E].reshape(E, E, 1, 1), self.v3(out), bias=b[lo:lo + E],
+                          res=None if res is None else self.v3(res))
+            self.conv(self.v3(x), w[2 * E:].reshape(E, E, 1, 1), self.v3(v), bias=b[2 * E:])
+            self.call(self.lib.otp_token_attn_forward, "otp_token_attn_forward", hip.ptr(q), hip.ptr(k), hip.ptr(v), None,
+                      hip.ptr(att), None, B, C, layer.nhead, T, 1.0 / math.sqrt(E // layer.nhead))
+            self.conv(self.v3(att), a.out_proj.weight.reshape(E, E, 1, 1), self.v3(y), bias=a.out_proj.bias, res=self.v3(x))
+            act = ACT_GELU if layer.activation == "gelu" else ACT_RELU
+            F = layer.linear1.out_features
+            hdn, z = self.new(B, F, T), self.new(B, C, T)
+            if layer.normalize_before:
+                self.conv(self.v3(self._ln(layer.norm2, y)), layer.linear1.weight.reshape(F, E, 1, 1), self.v3(hdn),
+                          bias=layer.linear1.bias, act=act)
+                self.conv(self.v3(hdn), layer.linear2.weight.reshape(E, F, 1, 1), self.v3(z), bias=layer.linear2.bias, res=self.v3(y))
+                x = z
+            else:
+                y = self._ln(layer.norm1, y)
+                self.conv(self.v3(y), layer.linear1.weight.reshape(F, E, 1, 1), self.v3(hdn), bias=layer.linear1.bias, act=act)
+                self.conv(self.v3(hdn), layer.linear2.weight.reshape(E, F, 1, 1), self.v3(z), bias=layer.linear2.bias, res=self.v3(y))
+                x = self._ln(layer.norm2, z)
+            if enc.pe_only_at_begin:
+                pos = None
+        return x if enc.norm is None else self._ln(enc.norm, x)
+
     def conv_transformer(self, ct, x, stacked):
         """x (B, C, T) already holds input + positional table (:meth:`encoder_pe`; the bare input for an encoder with conv
         embedding layers, whose last launch adds the table); writes levels into stacked (B, L*C, T)."""
@@ -1193,8 +1251,8 @@ class InferenceEngine:
         self.on_stream(2)
         def_h = self._prm_after("def_fuse_prm", self.rsb_chain(m.def_fuse, View(total)))
         self.on_stream(0)
-        self.conv_transformer(m.flow_encoder, flow_in, ctx)
-        D = m.num_frames * J                       # stacked maps per joint: 8 (5-frame window) or 12 (7 frames)
+        self.conv_transformer(m.flow_encoder, self.token_encoder("flow_token_encoder", "flow_pos_embedding", flow_in), ctx)
+        D = m.num_frames * J                      # stacked maps per joint: 8 (5-frame window) or 12 (7 frames)
         x1, x2, prev_b = self.new(B, D, T), self.new(B, D, T), self.new(B, J, h, w)
         pe1 = self.encoder_pe(m.temporal_encoder1, T)
         pe2 = self.encoder_pe(m.temporal_encoder2, T)
@@ -1226,10 +1284,10 @@ class InferenceEngine:
         self.copy_into(def_h, View(cat3, 2 * J, J))
         self.on_stream(0)
         self.fork((1,))
-        self.conv_transformer(m.temporal_encoder1, x1, s1)
+        self.conv_transformer(m.temporal_encoder1, self.token_encoder("token_encoder1", "temporal_pos_embedding", x1), s1)
         final(m.final_layer1, s1, 0)
         self.on_stream(0 if self.routes.te_serial else 1)
-        self.conv_transformer(m.temporal_encoder2, x2, s2)
+        self.conv_transformer(m.temporal_encoder2, self.token_encoder("token_encoder2", "temporal_pos_embedding", x2), s2)
         final(m.final_layer2, s2, 1)
         self.on_stream(0)
         self.join((1, 2))

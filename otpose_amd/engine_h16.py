@@ -24,6 +24,13 @@ from .ops import ACT_NONE, ACT_RELU, H8, View
 class InferenceEngineH16(InferenceEngine):
     h16 = True
 
+    def _build(self):
+        """The fp16-storage engine does not carry the token-encoder keys: ``ValueError`` at construction, before any launch."""
+        if any(getattr(self.model, n, None) is not None for n in ("token_encoder1", "token_encoder2", "flow_token_encoder")):
+            raise ValueError("MODEL.TOKEN_LAYERS / MODEL.FLOW_TOKEN_LAYERS: the fp16-storage engine does not carry the token "
+                             "encoders (exact-fp32 attention); use the fp32 engine")
+        super()._build()
+
     # ---- emitters -------------------------------------------------------------------------------------------------------------
     def h8(self, n, c, h, w) -> H8:
         """A static H8 activation buffer (2 bytes per element)."""

@@ -14,7 +14,9 @@ import os
 import torch
 from torch import nn
 
-from .modules import (CHAIN_RSB_BLOCKS, RSN_ATTENTION, ConvTransformer, HRNet, _Container)
+from .modules import (CHAIN_RSB_BLOCKS, RSN_ATTENTION, ConvTransformer, HRNet, TransformerEncoder, TransformerEncoderLayer,
+                      _Container)
+from .token_attn import sine_position_embedding
 from . import ops
 
 
@@ -150,6 +152,29 @@ class OTPose(nn.Module):
         self.flow_encoder = ConvTransformer(self.patch_dim, self.patch_dim, n_head=1,
                                             arch=self.flow_scale_arch, **tkw, **self._local_kw(fwin, False))
 
+        # extension keys: a DETR-style TransformerEncoder (OTPose.py:26-159, exported and never called by the reference) over the
+        # h w heat-map tokens in front of each ConvTransformer, on exactly the tensor the ConvTransformer is handed; all off by
+        # default.  The positional tables keep the reference's names (OTPose.py:259-279).
+        tk = self._token_keys(get, d)
+        self.token_keys = tk
+        for name, width, layers, heads, ffn in (("token_encoder1", d, tk["layers"], tk["heads"], tk["ffn"]),
+                                                ("token_encoder2", d, tk["layers"], tk["heads"], tk["ffn"]),
+                                                ("flow_token_encoder", self.patch_dim, tk["flow_layers"], 1, tk["flow_ffn"])):
+            if layers > 0:
+                layer = TransformerEncoderLayer(width, heads, ffn, dropout=0.1, activation="gelu", normalize_before=tk["pre_norm"])
+                setattr(self, name, TransformerEncoder(layer, layers))
+        pe, flow_pe = tk["pe"], tk["pe"]
+        if flow_pe == "sine" and tk["flow_layers"] > 0:
+            flow_pe = "none"                   # width 17 has no sine table (d_model % 4), in the reference either
+            self.logger.info("MODEL.TOKEN_PE = 'sine': the flow token encoder runs without a positional table (width %d)",
+                             self.patch_dim)
+        for name, width, layers, kind in (("temporal_pos_embedding", d, tk["layers"], pe),
+                                          ("flow_pos_embedding", self.patch_dim, tk["flow_layers"], flow_pe)):
+            if layers > 0 and kind == "learnable":
+                setattr(self, name, nn.Parameter(torch.randn(1, self.num_patches, width)))
+            elif layers > 0 and kind == "sine":
+                setattr(self, name, nn.Parameter(sine_position_embedding(self.pe_h, self.pe_w, width), requires_grad=False))
+
         self.deformable_conv_dilations = list(m.DEFORMABLE_CONV.DILATION)
         self.deformable_aggregation_type = m.DEFORMABLE_CONV.AGGREGATION_TYPE
         assert self.deformable_aggregation_type == "weighted_sum"
@@ -211,6 +236,35 @@ class OTPose(nn.Module):
                 or len(set(value)) != len(value):
             raise ValueError(f"MODEL.PRM must be a tuple of distinct names out of {cls.PRM_CHAINS}, got {value!r}")
         return tuple(value)
+
+    TOKEN_PE_KINDS = ("sine", "learnable", "none")
+
+    def _token_keys(self, get, d):
+        """The token-encoder keys of the cfg, validated (also when no layer is asked for: a bad key does not wait for the day a
+        layer is): layer counts, heads, FFN widths, pre-norm flag and the kind of positional table."""
+        from .token_attn import MAX_HEAD_WIDTH
+
+        def integer(key, default, low):
+            v = get(key, default)
+            if isinstance(v, bool) or not isinstance(v, int) or v < low:
+                raise ValueError(f"MODEL.{key} must be an int of at least {low}, got {v!r}")
+            return v
+        layers, flow_layers = integer("TOKEN_LAYERS", 0, 0), integer("FLOW_TOKEN_LAYERS", 0, 0)
+        heads = integer("TOKEN_HEADS", 2, 1)
+        if d % heads or d // heads > MAX_HEAD_WIDTH:
+            raise ValueError(f"MODEL.TOKEN_HEADS = {heads} must divide the token width {d} into heads of at most {MAX_HEAD_WIDTH} "
+                             "channels")
+        ffn, flow_ffn = integer("TOKEN_FFN", 2 * d, 1), 2 * self.patch_dim
+        pre = get("TOKEN_PRE_NORM", False)
+        if not isinstance(pre, bool):
+            raise ValueError(f"MODEL.TOKEN_PRE_NORM must be a bool, got {pre!r}")
+        pe = get("TOKEN_PE", "sine")
+        if not isinstance(pe, str) or pe not in self.TOKEN_PE_KINDS:
+            raise ValueError(f"MODEL.TOKEN_PE must be one of {self.TOKEN_PE_KINDS}, got {pe!r}")
+        if pe == "sine" and layers > 0 and d % 4:
+            raise ValueError(f"MODEL.TOKEN_PE = 'sine' needs a token width that is a multiple of 4, got {d}")
+        return {"layers": layers, "flow_layers": flow_layers, "heads": heads, "ffn": ffn, "flow_ffn": flow_ffn, "pre_norm": pre,
+                "pe": pe}
 
     def _embd_keys(self, get, d):
         """The conv embedding keys of the cfg, validated: {} at the defaults (no layer anywhere), else the layer counts and the

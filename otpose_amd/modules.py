@@ -466,3 +466,161 @@ class RSN_ATTENTION(_Container):  # noqa: N801
         self.conv_bn_relu_prm_2_2 = conv_bn_relu(c, c, 1, 1, 0)
         self.conv_bn_relu_prm_3_1 = conv_bn_relu(c, c, 1, 1, 0)
         self.conv_bn_relu_prm_3_2 = conv_bn_relu(c, c, 9, 1, 4, groups=c)
+
+
+# ----------------------------------------------------------------------------------------------
+# DETR-style token encoder (reference model/OTPose.py:26-159): unlike the containers above these two
+# modules can run themselves on the library's launches (the training graph calls forward_cm); inside
+# OTPose in eval mode the inference engine emits their launches (InferenceEngine.token_encoder)
+# ----------------------------------------------------------------------------------------------
+class _SelfAttnParams(nn.Module):
+    """The parameters of ``nn.MultiheadAttention(E, nhead)`` under its names: ``in_proj_weight`` (3E, E), ``in_proj_bias`` (3E),
+    ``out_proj.weight`` (E, E), ``out_proj.bias`` (E), with its initialisation (xavier-uniform in-projection, zero biases)."""
+
+    def __init__(self, d_model):
+        super().__init__()
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * d_model, d_model))
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * d_model))
+        self.out_proj = nn.Linear(d_model, d_model)
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        nn.init.zeros_(self.out_proj.bias)
+
+
+def _pointwise(x, weight, bias):
+    """``F.linear`` over the channel axis of (N, Cin, L) as a 1x1 convolution launch (``train_ops.conv2d``: forward and backward
+    in HIP) -> (N, Cout, L)."""
+    from . import train_ops as T
+    n, c, length = x.shape
+    return T.conv2d(x.reshape(n, c, 1, length), weight.reshape(weight.shape[0], c, 1, 1), bias).reshape(n, weight.shape[0], length)
+
+
+class TransformerEncoderLayer(nn.Module):
+    """reference model/OTPose.py:84-159 with its constructor signature, ``state_dict`` keys and ``forward`` on sequence-first
+    (L, N, E) tensors.  Inside, the layer works channel-major on (N, E, L) (:meth:`forward_cm`): the in-projection, the
+    out-projection and the two FFN linears are 1x1 convolutions (``train_ops.conv2d``, exact fp32: the scores feed an exp, so
+    the split-product route of the C -> C layers is switched off for this module), the two LayerNorms the channel LayerNorm
+    (``train_ops.layer_norm``, eps 1e-5, biased variance, as ``nn.LayerNorm(E)``), GELU ``train_ops.gelu``, the attention core
+    ``token_attn`` (csrc/tokattn.hip).  Residual adds, the ``pos`` add, ReLU and dropout are PyTorch element-wise operators.
+
+    Deviations, each raising: a dense ``src_mask`` -> ``NotImplementedError``; ``activation`` is ``relu`` or ``gelu`` (``glu``
+    halves the width in the reference and then fails in ``linear2``) -> ``ValueError``; attention-probability dropout is not
+    built: ``dropout`` acts at the reference's three ``nn.Dropout`` places only, and the separate ``attn_dropout`` must be 0
+    (the reference hands ``dropout`` to ``nn.MultiheadAttention`` as well).  With ``return_atten_map`` the map comes from
+    ``token_attn_map`` and carries no gradient."""
+
+    def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1, activation="gelu", normalize_before=False,
+                 return_atten_map=False, attn_dropout=0.0):
+        super().__init__()
+        from .token_attn import MAX_HEAD_WIDTH
+        for name, val in (("d_model", d_model), ("nhead", nhead), ("dim_feedforward", dim_feedforward)):
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or val < 1:
+                raise ValueError(f"TransformerEncoderLayer: {name} must be a positive int, got {val!r}")
+        if d_model % nhead or d_model // nhead > MAX_HEAD_WIDTH:
+            raise ValueError(f"TransformerEncoderLayer: nhead = {nhead} must divide d_model = {d_model} into heads of at most "
+                             f"{MAX_HEAD_WIDTH} channels")
+        if activation not in ("relu", "gelu"):
+            raise ValueError(f"TransformerEncoderLayer: activation must be 'relu' or 'gelu', got {activation!r}")
+        if attn_dropout != 0.0:
+            raise ValueError("TransformerEncoderLayer: attention-probability dropout is not built, attn_dropout must be 0")
+        self.self_attn = _SelfAttnParams(d_model)
+        self.linear1 = nn.Linear(d_model, dim_feedforward)
+        self.linear2 = nn.Linear(dim_feedforward, d_model)
+        self.norm1 = nn.LayerNorm(d_model)
+        self.norm2 = nn.LayerNorm(d_model)
+        self.d_model, self.nhead, self.p_drop, self.activation = d_model, nhead, float(dropout), activation
+        self.normalize_before, self.return_atten_map = normalize_before, return_atten_map
+
+    def _drop(self, x):
+        return torch.nn.functional.dropout(x, self.p_drop, True) if self._stochastic and self.p_drop > 0 else x
+
+    def _norm(self, norm, x):
+        from . import train_ops as T
+        return T.layer_norm(x, norm.weight, norm.bias, norm.eps)
+
+    def _attention(self, qk, value, mask):
+        """q = k from ``qk``, v from ``value`` (both (N, E, L)) -> (attention output after the out-projection, map or None)."""
+        from .token_attn import token_attn, token_attn_map
+        e, a = self.d_model, self.self_attn
+        w, b = a.in_proj_weight, a.in_proj_bias
+        q = _pointwise(qk, w[:e], b[:e])
+        k = _pointwise(qk, w[e:2 * e], b[e:2 * e])
+        v = _pointwise(value, w[2 * e:], b[2 * e:])
+        scale = 1.0 / math.sqrt(e // self.nhead)
+        out = _pointwise(token_attn(q, k, v, self.nhead, scale, mask), a.out_proj.weight, a.out_proj.bias)
+        amap = token_attn_map(q.detach(), k.detach(), self.nhead, scale, mask) if self.return_atten_map else None
+        return out, amap
+
+    def _ffn(self, x):
+        from . import train_ops as T
+        h = _pointwise(x, self.linear1.weight, self.linear1.bias)
+        h = T.gelu(h) if self.activation == "gelu" else torch.relu(h)
+        return _pointwise(self._drop(h), self.linear2.weight, self.linear2.bias)
+
+    def forward_cm(self, x, mask=None, pos=None, stochastic=None):
+        """The layer on channel-major tensors: ``x`` (N, E, L), ``pos`` None or broadcastable to it, ``mask`` (N, L) bool
+        (True = padding) -> (output (N, E, L), attention map (N, L, L) or None).  The reference's forward_post / forward_pre."""
+        import dataclasses
+        from . import train_ops as T
+        self._stochastic = self.training if stochastic is None else bool(stochastic)   # dropout on (the training graph decides)
+        with T.active_routes(dataclasses.replace(T.current_routes(), use_x3=False)):
+            if self.normalize_before:
+                y = self._norm(self.norm1, x)
+                a, amap = self._attention(y if pos is None else (y + pos).contiguous(), x, mask)
+                x = x + self._drop(a)
+                return x + self._drop(self._ffn(self._norm(self.norm2, x))), amap
+            a, amap = self._attention(x if pos is None else (x + pos).contiguous(), x, mask)
+            x = self._norm(self.norm1, x + self._drop(a))
+            return self._norm(self.norm2, x + self._drop(self._ffn(x))), amap
+
+    def forward(self, src, src_mask=None, src_key_padding_mask=None, pos=None):
+        out, amap = _encoder_forward([self], None, False, src, src_mask, src_key_padding_mask, pos)
+        return (out, amap[0]) if self.return_atten_map else out
+
+
+def _encoder_forward(layers, norm, pe_only_at_begin, src, mask, key_padding_mask, pos):
+    """(L, N, E) -> (N, E, L) once, the layers, the optional final LayerNorm, and back once; ``pos`` (L, 1 or N, E) likewise."""
+    if mask is not None:
+        raise NotImplementedError("TransformerEncoder: a dense attention mask (attn_mask, L x L) is not built; "
+                                  "use src_key_padding_mask")
+    if src.dim() != 3:
+        raise ValueError(f"TransformerEncoder: src is (L, N, E), got {tuple(src.shape)}")
+    x = src.permute(1, 2, 0).contiguous()
+    p = None if pos is None else pos.permute(1, 2, 0).contiguous()
+    maps = []
+    for layer in layers:
+        x, amap = layer.forward_cm(x, key_padding_mask, p)
+        maps.append(amap)
+        if pe_only_at_begin:
+            p = None
+    if norm is not None:
+        from . import train_ops as T
+        x = T.layer_norm(x, norm.weight, norm.bias, norm.eps)
+    return x.permute(2, 0, 1).contiguous(), maps
+
+
+class TransformerEncoder(nn.Module):
+    """reference model/OTPose.py:26-66: ``num_layers`` deep copies of ``encoder_layer``, an optional final ``norm``
+    (``nn.LayerNorm(E)``), xavier-uniform on every parameter of more than one dimension.  ``forward`` moves to (N, E, L) once at
+    entry and back once at exit; with ``return_atten_map`` it also returns the (layers, N, L, L) stack of maps."""
+
+    def __init__(self, encoder_layer, num_layers, norm=None, pe_only_at_begin=False, return_atten_map=False):
+        super().__init__()
+        import copy
+        if not isinstance(encoder_layer, TransformerEncoderLayer):
+            raise ValueError("TransformerEncoder: encoder_layer must be a modules.TransformerEncoderLayer")
+        if isinstance(num_layers, bool) or not isinstance(num_layers, (int, np.integer)) or num_layers < 1:
+            raise ValueError(f"TransformerEncoder: num_layers must be a positive int, got {num_layers!r}")
+        if norm is not None and not isinstance(norm, nn.LayerNorm):
+            raise ValueError("TransformerEncoder: norm must be None or an nn.LayerNorm")
+        self.layers = nn.ModuleList([copy.deepcopy(encoder_layer) for _ in range(num_layers)])
+        self.num_layers, self.norm = num_layers, norm
+        self.pe_only_at_begin, self.return_atten_map = pe_only_at_begin, return_atten_map
+        for layer in self.layers:
+            layer.return_atten_map = return_atten_map
+        for p in self.parameters():
+            if p.dim() > 1:
+                nn.init.xavier_uniform_(p)
+
+    def forward(self, src, mask=None, src_key_padding_mask=None, pos=None):
+        out, maps = _encoder_forward(self.layers, self.norm, self.pe_only_at_begin, src, mask, src_key_padding_mask, pos)
+        return (out, torch.stack(maps)) if self.return_atten_map else out

@@ -300,7 +300,9 @@ def reference_param_groups(model, cfg):
 
     # RSN_ATTENTION: the MODEL.PRM modules go where the chains they follow go (def_fuse_prm.* also matches the prefix rule below)
     white = (nn.Linear, nn.Conv1d, DeformableCONV, M.CHAIN_RSB_BLOCKS, M.RSN_ATTENTION, nn.ConvTranspose1d)
-    black = (M.LayerNorm, nn.GroupNorm)
+    # the token encoders (MODEL.TOKEN_LAYERS / FLOW_TOKEN_LAYERS; the reference's make_optimizer has no rule for them and would
+    # assert): in_proj_weight, out_proj.weight, linear{1,2}.weight decay; every bias, norm*.weight and the positional tables do not
+    black = (M.LayerNorm, nn.GroupNorm, nn.LayerNorm)
     decay, no_decay, pretrained = set(), set(), set()
     for mn, m in model.named_modules():
         for pn, _ in m.named_parameters():
@@ -315,8 +317,10 @@ def reference_param_groups(model, cfg):
                 no_decay.add(fpn)
             elif pn.endswith("scale") and isinstance(m, M.AffineDropPath):
                 no_decay.add(fpn)
-            elif pn.endswith("rel_pe"):
+            elif pn.endswith("rel_pe") or pn in ("temporal_pos_embedding", "flow_pos_embedding"):
                 no_decay.add(fpn)
+            elif pn == "in_proj_weight" and isinstance(m, M._SelfAttnParams):
+                decay.add(fpn)
             elif pn == "weight" and isinstance(m, nn.Conv2d) and ".embd." in f".{mn}.":
                 decay.add(fpn)          # conv embedding of a ConvTransformer (its bias and embd_norm.* fall under the rules above)
             elif pn.startswith(("offsets_list", "masks_list", "final_layer")):

@@ -1,0 +1,147 @@
+"""Token x token self-attention on the GPU (csrc/tokattn.hip): the attention core of the DETR-style ``TransformerEncoder`` of the
+reference's model/OTPose.py:26-159, flash style - online softmax over key tiles, a recomputing backward, no T x T buffer.
+
+Operands are the library's own layout: ``q, k, v`` fp32 ``(B, C, T)``, contiguous, head ``h`` owning channels
+``h * hd .. (h + 1) * hd - 1`` (``nn.MultiheadAttention``'s head split with the token axis last):
+
+    S[i][j] = scale * sum_c q[c][i] k[c][j],   P = softmax_j(S),   O[c][i] = sum_j P[i][j] v[c][j]
+
+``key_padding_mask`` is ``(B, T)`` bool, True = this key is padding, as in PyTorch.  A sample whose keys are all padding is
+outside the contract (PyTorch returns NaN rows there; this kernel divides by zero).  Supported: ``C % n_head == 0`` and a head
+width of at most 136; everything else raises ``ValueError`` before any launch.  CPU tensors raise ``NotImplementedError``,
+like every operator here.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+from torch.autograd import Function
+
+from . import hip
+from .ops import require_gpu
+
+__all__ = ["token_attn", "token_attn_map", "sine_position_embedding", "check_token_attn", "MAX_HEAD_WIDTH"]
+
+MAX_HEAD_WIDTH = 136
+
+
+def check_token_attn(c, n_head, t):
+    """Raise ``ValueError`` for a shape the kernels do not take (``otp_token_attn_supported``)."""
+    if not isinstance(n_head, int) or isinstance(n_head, bool) or n_head <= 0 or c % n_head:
+        raise ValueError(f"token_attn: {c} channels do not split into {n_head!r} heads")
+    if not hip.lib().otp_token_attn_supported(int(c), n_head, int(t)):
+        raise ValueError(f"token_attn: the head width C / n_head must be in [1, {MAX_HEAD_WIDTH}] and T at least 1, got C = {c}, "
+                         f"n_head = {n_head}, T = {t}")
+
+
+def _check(q, k, v, n_head, key_padding_mask):
+    """Validate the operands and return (B, C, T, mask as uint8 or None)."""
+    tensors = [x for x in (q, k, v) if x is not None]
+    for x in tensors:
+        if not isinstance(x, torch.Tensor) or x.dim() != 3:
+            raise ValueError("token_attn: q, k, v are (B, C, T) tensors")
+        if x.dtype != torch.float32:
+            raise ValueError(f"token_attn: built for float32, got {x.dtype}")
+        if not x.is_contiguous():
+            raise ValueError("token_attn: q, k, v must be contiguous (B, C, T) tensors")
+        if x.shape != q.shape or x.device != q.device:
+            raise ValueError(f"token_attn: operands of different shapes or devices: {tuple(x.shape)} and {tuple(q.shape)}")
+    b, c, t = q.shape
+    if b < 1:
+        raise ValueError("token_attn: an empty batch")
+    check_token_attn(c, n_head, t)
+    mask = None
+    if key_padding_mask is not None:
+        if not isinstance(key_padding_mask, torch.Tensor) or key_padding_mask.dtype != torch.bool:
+            raise ValueError("token_attn: key_padding_mask is a bool tensor (True = padding)")
+        if tuple(key_padding_mask.shape) != (b, t) or key_padding_mask.device != q.device:
+            raise ValueError(f"token_attn: key_padding_mask must be ({b}, {t}) on the operands' device, got "
+                             f"{tuple(key_padding_mask.shape)}")
+        mask = key_padding_mask.contiguous().view(torch.uint8)
+    require_gpu(*tensors)
+    return b, c, t, mask
+
+
+def _forward(q, k, v, mask, n_head, scale, want_lse):
+    b, c, t = q.shape
+    out = torch.empty_like(q)
+    lse = torch.empty((b, n_head, t), dtype=torch.float32, device=q.device) if want_lse else None
+    hip.check(hip.lib().otp_token_attn_forward(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(mask), hip.ptr(out), hip.ptr(lse),
+                                               b, c, n_head, t, scale, hip.stream_of(q)), "otp_token_attn_forward")
+    return out, lse
+
+
+class TokenAttnFunction(Function):
+    """``token_attn`` with a backward: the forward keeps q, k, v, the output and the row log-sum-exp (B, n_head, T); the backward
+    is ``otp_token_attn_backward`` (pass A: D and dq per query tile, pass B: dk and dv per key tile; deterministic, no atomics)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, n_head, scale):
+        out, lse = _forward(q, k, v, mask, n_head, scale, True)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.mask, ctx.cfg = mask, (n_head, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        q, k, v, out, lse = ctx.saved_tensors
+        n_head, scale = ctx.cfg
+        b, c, t = q.shape
+        L = hip.lib()
+        gout = gout.contiguous()
+        gq, gk, gv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+        ws = torch.empty(L.otp_token_attn_workspace(b, n_head, t, c // n_head) // 4, dtype=torch.float32, device=q.device)
+        hip.check(L.otp_token_attn_backward(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(ctx.mask), hip.ptr(out), hip.ptr(lse),
+                                            hip.ptr(gout), hip.ptr(gq), hip.ptr(gk), hip.ptr(gv), hip.ptr(ws), b, c, n_head, t,
+                                            scale, hip.stream_of(q)), "otp_token_attn_backward")
+        return gq, gk, gv, None, None, None
+
+
+def token_attn(q, k, v, n_head, scale, key_padding_mask=None):
+    """softmax(scale q^T k) v per head, ``(B, C, T)`` in and out.  Under ``torch.no_grad()`` or with no operand requiring a
+    gradient: one forward launch that stores no log-sum-exp; otherwise an autograd Function."""
+    _, _, _, mask = _check(q, k, v, n_head, key_padding_mask)
+    scale = float(scale)
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        return TokenAttnFunction.apply(q, k, v, mask, n_head, scale)
+    return _forward(q, k, v, mask, n_head, scale, False)[0]
+
+
+def token_attn_map(q, k, n_head, scale, key_padding_mask=None):
+    """``(B, T, T)``: the mean over heads of P, what ``nn.MultiheadAttention`` returns as its second value.  Two launches: a
+    forward for the row log-sum-exp (its output is dropped), then one pass that recomputes ``exp(S - lse)``.
+
+    The map carries NO gradient (a documented deviation: in PyTorch the averaged weights are differentiable)."""
+    b, c, t, mask = _check(q, k, None, n_head, key_padding_mask)
+    scale = float(scale)
+    q, k = q.detach(), k.detach()
+    _, lse = _forward(q, k, k, mask, n_head, scale, True)
+    out = torch.empty((b, t, t), dtype=torch.float32, device=q.device)
+    hip.check(hip.lib().otp_token_attn_map(hip.ptr(q), hip.ptr(k), hip.ptr(mask), hip.ptr(lse), hip.ptr(out), b, c, n_head, t,
+                                           scale, hip.stream_of(q)), "otp_token_attn_map")
+    return out
+
+
+def sine_position_embedding(h, w, d_model, temperature=10000, scale=2 * math.pi):
+    """The fixed 2-D sine table of ``_make_sine_position_embedding`` (OTPose.py:281-305) for an ``h x w`` token grid:
+    ``(1, h * w, d_model)``, the first half of the width encoding the row, the second half the column, each as interleaved
+    sin / cos pairs of the normalised position over a geometric ladder of wavelengths.  ``d_model`` must be a multiple of 4
+    (each direction needs whole sin / cos pairs; the reference's own stack / cat fails or yields another width otherwise)."""
+    if not isinstance(d_model, int) or d_model <= 0 or d_model % 4:
+        raise ValueError(f"sine_position_embedding: d_model must be a positive multiple of 4, got {d_model!r}")
+    if h < 1 or w < 1:
+        raise ValueError(f"sine_position_embedding: an empty {h} x {w} grid")
+    half = d_model // 2
+    rows = torch.arange(1, h + 1, dtype=torch.float32) / (h + 1e-6) * scale
+    cols = torch.arange(1, w + 1, dtype=torch.float32) / (w + 1e-6) * scale
+    ladder = torch.arange(half, dtype=torch.float32)
+    ladder = temperature ** (2 * torch.div(ladder, 2, rounding_mode="floor") / half)
+
+    def direction(coord):                                          # (n) -> (n, half): sin on even, cos on odd features
+        ang = coord[:, None] / ladder
+        return torch.stack((ang[:, 0::2].sin(), ang[:, 1::2].cos()), dim=2).flatten(1)
+
+    py = direction(rows)[:, None, :].expand(h, w, half)
+    px = direction(cols)[None, :, :].expand(h, w, half)
+    return torch.cat((py, px), dim=2).reshape(1, h * w, d_model).contiguous()

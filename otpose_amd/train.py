@@ -409,9 +409,36 @@ class TrainGraph:
         h = self.conv1d(p + ".3", self.dropout(T.gelu(h), pdrop))
         return self.dropout(h, pdrop)
 
+    TOKEN_ENCODERS = {"temporal_encoder1": ("token_encoder1", "temporal_pos_embedding"),
+                      "temporal_encoder2": ("token_encoder2", "temporal_pos_embedding"),
+                      "flow_encoder": ("flow_token_encoder", "flow_pos_embedding")}
+
+    def token_encoder(self, p, x):
+        """Extension keys MODEL.TOKEN_LAYERS / FLOW_TOKEN_LAYERS: the ``modules.TransformerEncoder`` in front of ConvTransformer
+        ``p`` on x (B, C, T), on exactly the tensor the inference engine hands it (the input plus the ConvTransformer's
+        positional table, or the bare input when conv embedding layers follow); x itself when the model has none."""
+        name, pos_name = self.TOKEN_ENCODERS.get(p, (None, None))
+        enc = self.mods.get(name) if name else None
+        if enc is None:
+            return x
+        pos = self.P.get(pos_name)
+        if pos is None:
+            pos = self.Bf.get(pos_name)
+        pos = None if pos is None else pos.permute(0, 2, 1).contiguous()
+        for layer in enc.layers:
+            x, _ = layer.forward_cm(x, None, pos, stochastic=self.stochastic)
+            if enc.pe_only_at_begin:
+                pos = None
+        return x if enc.norm is None else T.layer_norm(x, enc.norm.weight, enc.norm.bias, enc.norm.eps)
+
     def conv_transformer(self, p, x4, n_head, arch):
         b, c, h, w = x4.shape
         t = h * w
+        if not self.has(f"{p}.embd.0.weight"):
+            # no conv embedding: the positional table first, as the inference engine's glue kernels add it, then the token encoder
+            x = self.token_encoder(p, x4.reshape(b, c, t) + self.Bf[p + ".pos_embd"][:, :, :t])
+            return self._conv_transformer_levels(p, x, n_head, arch)
+        x4 = self.token_encoder(p, x4.reshape(b, c, t).contiguous()).view(b, c, h, w)
         # conv embedding layers in front of the positional table (ConvVideoTransformer.py:129-135), one node each
         i = 0
         while self.has(f"{p}.embd.{i}.weight"):
@@ -419,7 +446,9 @@ class TrainGraph:
                              self.P.get(f"{p}.embd_norm.{i}.weight"), self.P.get(f"{p}.embd_norm.{i}.bias")).view(b, -1, h, w)
             i += 1
         c = x4.shape[1]
-        x = x4.reshape(b, c, t) + self.Bf[p + ".pos_embd"][:, :, :t]
+        return self._conv_transformer_levels(p, x4.reshape(b, c, t) + self.Bf[p + ".pos_embd"][:, :, :t], n_head, arch)
+
+    def _conv_transformer_levels(self, p, x, n_head, arch):
         for i in range(arch[1]):
             x = self.tblock(f"{p}.stem.{i}", x, n_head, 1)
         outs = [x]

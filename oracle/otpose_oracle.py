@@ -38,7 +38,7 @@ BN_EPS = 1e-5
 # graph the bf16 activations (2^-9 per stored value) flip ~1 % of the ReLU gates and move the whole gradient by 0.1 relative L2
 # - a bound that would not notice a wrong kernel.  Inside ``with bf16_points():`` this restatement rounds to bfloat16 exactly
 # where otpose_amd/train.py::TrainGraphBF16 stores bfloat16 - the HRNet input, every HRNet conv result (BatchNorm statistics
-# are taken from the rounded values, as csrc/nhwc.hip does), every BatchNorm (+ residual) (+ ReLU) result, every fuse-row
+# are taken from the rounded values, as csrc/nhwc_conv.hip does), every BatchNorm (+ residual) (+ ReLU) result, every fuse-row
 # accumulation, the MLP interior of the temporal encoders, the input of the offset / mask convs, the weights of those
 # layers (fp32 masters, straight-through) - and rounds the GRADIENTS at the same tensors in the backward pass (the product's
 # input-gradient convs and BatchNorm backward kernels store bf16).  Accumulation stays in the oracle's precision, as the
@@ -117,7 +117,7 @@ def _conv(sd: SD, p: str, x, stride=1, pad=0, dil=1):
 
 def _conv_bn(sd, conv, bn, x, stride=1, pad=0, relu=False, training=False, res=None):
     if _BF16_POINTS:
-        # csrc/nhwc.hip: bf16 operands, fp32 accumulation, the result stored as bf16 (statistics from the stored values), then
+        # csrc/nhwc_conv.hip: bf16 operands, fp32 accumulation, the result stored as bf16 (statistics from the stored values), then
         # one pass y = act(c * scale + shift (+ res)) stored as bf16; ``_rb(x)`` rounds this consumer's input gradient
         c = _rb(F.conv2d(_rb(x), _rbw(sd[conv + ".weight"]), None, stride, pad))
         y = _bn(sd, bn, c, training)

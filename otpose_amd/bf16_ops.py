@@ -1,4 +1,4 @@
-"""bf16 training operators of the backbone over the C-ABI (``csrc/nhwc.hip``; BASELINE configs[2], reference step
+"""bf16 training operators of the backbone over the C-ABI (``csrc/nhwc_conv.hip``, ``nhwc_wgrad.hip``, ``nhwc_bn.hip``, ``nhwc_pass.hip``; BASELINE configs[2], reference step
 script/Common.py:118-144 over model/HRNet.py:116-152).
 
 Activations are NHWC bfloat16 tensors ``(N, H, W, CS)`` with ``CS`` = channels rounded up to 8 (padding channels are
@@ -63,7 +63,7 @@ def to_nchw(x: torch.Tensor, c: int) -> torch.Tensor:
 
 def _pack(weight, d, dgrad, packs=None):
     """The packed bf16 operator of ``weight`` for descriptor ``d``: from ``packs`` (a :class:`PackCache`) when given, else one
-    ``otp_nhwc_conv_pack`` launch.  Both run the library's one packer (``pack_unit`` of ``csrc/nhwc.hip``) under the one route
+    ``otp_nhwc_conv_pack`` launch.  Both run the library's one packer (``pack_unit`` of ``csrc/nhwc_conv.hip``) under the one route
     decision that also sizes the buffer and picks the kernel of the launch."""
     if packs is not None:
         return packs.get(weight, d, dgrad)

@@ -37,7 +37,7 @@ static inline int otp_launch_status() {
 static inline int otp_ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // the vector types of every kernel file (16-bit element vectors: otp_x3x2 / otp_x3x8 below; csrc/h16_kernels.h takes its element
-// type from a traits parameter, csrc/nhwc.hip is bfloat16 only)
+// type from a traits parameter, csrc/nhwc.h is bfloat16 only)
 typedef float otp_f32x4 __attribute__((ext_vector_type(4)));
 typedef float otp_f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int otp_u32x4 __attribute__((ext_vector_type(4)));
@@ -68,7 +68,7 @@ __device__ __forceinline__ float otp_kslot_sum(float v) {  // sum over the four 
     return v;
 }
 // sum over the 16 lanes of a DPP row (one MFMA pixel column group) with four VALU adds; every lane ends with the total.
-// (__shfl_xor with offsets 4 and 8 lowers to ds_bpermute on gfx950: 96 LDS round trips in the old epilogue of csrc/nhwc.hip)
+// (__shfl_xor with offsets 4 and 8 lowers to ds_bpermute on gfx950: 96 LDS round trips in the old epilogue of csrc/nhwc_conv.hip)
 template <int CTRL>
 __device__ __forceinline__ float otp_dpp_mov(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));

@@ -1,7 +1,7 @@
 // The 16-bit record kernels two translation units instantiate: the 3x3 window / weight-stream convolution and the register-resident
 // 1x1 convolution, with their plans and launches.  csrc/h16.hip runs them on IEEE half H8 images (the fp16 eval engine: folded
 // BatchNorm, range guard), csrc/hb.hip on bfloat16 NHWC tensors (the training step's forward / input-gradient convolutions, reached
-// through csrc/nhwc.hip: per-tile channel statistics instead of the folded BatchNorm).  Same window, weight stream and MFMA schedule;
+// through csrc/nhwc_conv.hip: per-tile channel statistics instead of the folded BatchNorm).  Same window, weight stream and MFMA schedule;
 // the records' addresses are (pixel stride, group stride) pairs, and what differs is the element traits T below.  Internal linkage
 // throughout, as in the .hip files: each translation unit gets its own copies.
 #pragma once
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? OTP_H16_MINWG : 2) void h16_conv
     }
     HSTAMP(17);
     if constexpr (T::training) {
-        // training form (csrc/nhwc.hip's contract): out = bf16(conv + bias); the per-tile channel sums / sums of squares are those of
+        // training form (csrc/nhwc_conv.hip's contract): out = bf16(conv + bias); the per-tile channel sums / sums of squares are those of
         // the ROUNDED values (what BatchNorm will normalise); a residual is added to the rounded result and the sum rounded again -
         // bit for bit a separate bf16 add.  Sums: 16 lanes of a DPP row hold the 16 pixels of a tile -> row sum -> the four waves'
         // partials through the LDS behind the weight image, added in a fixed order.
@@ -623,7 +623,7 @@ int h16_conv_dispatch(const void* xs, const void* wpk, const float* fs, const vo
 // memory, 16 bytes, no conversion; the weights stream through the LDS in blocks of one cout-tile pair (32 output channels: 2 KS
 // KB, LDS-DMA, double buffered); a pair's two 16 x 16 results per pixel tile are 8 consecutive channels per lane = one record.
 // (csrc/hb.hip: the same kernel on bfloat16 NHWC tensors - the TransformerBlock MLP's two projections and their input gradients in
-//  the training step, reached through csrc/nhwc.hip's otp_nhwc_conv_* - with the bias as a separate fp32 vector.)
+//  the training step, reached through csrc/nhwc_conv.hip's otp_nhwc_conv_* - with the bias as a separate fp32 vector.)
 struct HPw {
     const unsigned char* x;
     const unsigned char* packed;
@@ -729,7 +729,7 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : (KS <= 8 ? 3 : 2)) void h16_poin
             }
             if constexpr (T::training) {
                 if (A.res) {
-                    // csrc/nhwc.hip's contract: the residual is added to the ROUNDED result and the sum rounded again (a separate bf16 add)
+                    // csrc/nhwc_conv.hip's contract: the residual is added to the ROUNDED result and the sum rounded again (a separate bf16 add)
                     const otp_u32x4 q = T::pack8((const float(&)[8])f);
                     const otp_f32x2 w0 = T::widen(q[0]), w1 = T::widen(q[1]), w2 = T::widen(q[2]), w3 = T::widen(q[3]);
                     const float g[8] = {w0.x, w0.y, w1.x, w1.y, w2.x, w2.y, w3.x, w3.y};
@@ -759,7 +759,7 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : (KS <= 8 ? 3 : 2)) void h16_poin
                 }
             }
             if constexpr (EPI == 1) {
-                // per-tile channel sums of the ROUNDED values (csrc/nhwc.hip's contract: what BatchNorm will normalise): the 16 lanes of
+                // per-tile channel sums of the ROUNDED values (csrc/nhwc_conv.hip's contract: what BatchNorm will normalise): the 16 lanes of
                 // a DPP row hold 16 pixels of the lane's 8 channels
                 const otp_u32x4 qv = T::pack8((const float(&)[8])f);
                 const otp_f32x2 w0 = T::widen(qv[0]), w1 = T::widen(qv[1]), w2 = T::widen(qv[2]), w3 = T::widen(qv[3]);

@@ -1,5 +1,5 @@
 // csrc/hb.hip (csrc/h16_kernels.h instantiated for bfloat16, NHWC addressing): the training step's 3x3 convolutions on the window /
-// weight-stream kernel of the fp16 engine, its 1x1 convolutions on that engine's pointwise kernel.  Internal interface between csrc/nhwc.hip (which owns the C ABI: otp_nhwc_conv_*)
+// weight-stream kernel of the fp16 engine, its 1x1 convolutions on that engine's pointwise kernel.  Internal interface between csrc/nhwc_conv.hip (which owns the C ABI: otp_nhwc_conv_*)
 // and that translation unit, plus the layout of the packed weights both sides must agree on.
 #pragma once
 #include "x3.h"
@@ -33,7 +33,7 @@ inline int otp_hbpw_ks(int Cin) {               // the instantiated k-step count
     const int k = (Cin + 31) / 32;
     return k <= 2 ? 2 : (k <= 4 ? 4 : (k == 5 ? 5 : (k <= 8 ? 8 : (k <= 12 ? 12 : (k <= 17 ? 17 : 0)))));
 }
-// Dropout draws of the bf16 training path (csrc/nhwc.hip: gelu_dropout_bf16_*, csrc/hb.hip: the MLP up-projection's epilogue): a
+// Dropout draws of the bf16 training path (csrc/nhwc_pass.hip: gelu_dropout_bf16_*, csrc/hb.hip: the MLP up-projection's epilogue): a
 // counter-based hash of (element pair, seed), two 16-bit uniforms per 32-bit hash (lowbias32 finaliser), keep <=> u16 >= round(65536 p).
 // Unit u = elements 8 u .. 8 u + 7 of the tensor; bit j of the result = element 8 u + j is kept.
 __device__ __forceinline__ uint32_t otp_drop_hash(size_t pair, uint32_t s0, uint32_t s1) {

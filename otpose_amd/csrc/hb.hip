@@ -1,6 +1,6 @@
 // The fp16 engine's window / weight-stream 3x3 kernel and its pointwise kernel (csrc/h16_kernels.h) instantiated with the Bf16
 // traits on bfloat16 NHWC tensors: the training step's 3x3 forward / input-gradient convolutions and the TransformerBlock MLP's
-// projections (otp_hb_* / otp_hbpw_* of csrc/hb.h, reached through csrc/nhwc.hip's otp_nhwc_conv_*).
+// projections (otp_hb_* / otp_hbpw_* of csrc/hb.h, reached through csrc/nhwc_conv.hip's otp_nhwc_conv_*).
 #include "h16_kernels.h"
 #include <cstring>
 #include <map>

@@ -1,6 +1,6 @@
 // What the split-product ("x3") kernels share beyond csrc/common.h: the 8-float split into hi / lo records, and the conventions of
 // the record-format 3x3 convolutions - S8 (csrc/convs.hip, csrc/convs2.hip: split fp32) and H8 (csrc/h16_kernels.h in csrc/h16.hip and csrc/hb.hip, with
-// csrc/nhwc.hip's packer: one 16-bit piece).  A weight packer and the kernels that read its image must agree on these, so they are
+// csrc/nhwc_conv.hip's packer: one 16-bit piece).  A weight packer and the kernels that read its image must agree on these, so they are
 // written once, here.
 #pragma once
 #include "common.h"

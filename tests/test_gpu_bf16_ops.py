@@ -1,4 +1,4 @@
-"""bf16 NHWC training operators (csrc/nhwc.hip) against plain PyTorch fp32 references of the same ops on the SAME
+"""bf16 NHWC training operators (csrc/nhwc_conv.hip, csrc/nhwc_wgrad.hip, csrc/nhwc_bn.hip, csrc/nhwc_pass.hip) against plain PyTorch fp32 references of the same ops on the SAME
 bf16-rounded operands: the conv products are exact in fp32, so forward outputs differ from the reference only by the
 final rounding to bf16 (2^-9 relative) and fp32 summation order; weight gradients are fp32 end to end.
 Reference ops: nn.Conv2d / nn.BatchNorm2d(training) / nearest upsample + add as composed in model/HRNet.py:416-571."""

@@ -1,4 +1,4 @@
-"""Packed bf16 weights of the NHWC training convolutions (csrc/nhwc.hip): the direct packer (otp_nhwc_conv_pack) and the job-table
+"""Packed bf16 weights of the NHWC training convolutions (csrc/nhwc_conv.hip): the direct packer (otp_nhwc_conv_pack) and the job-table
 packer (otp_nhwc_conv_pack_job + otp_nhwc_conv_pack_batch) must write the same bits on each of the three routes (nhwc_conv_kernel,
 csrc/hb.hip's 3x3 window kernel, its pointwise kernel), and the byte count, the statistics row count, the packer and the launch must
 agree on which descriptors they take."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Stand-alone timing of the bf16 NHWC backbone kernels (csrc/nhwc.hip) at the HRNet-W48 cfg2 shapes, HIP events on the
+"""Stand-alone timing of the bf16 NHWC backbone kernels (csrc/nhwc_conv.hip, csrc/nhwc_wgrad.hip) at the HRNet-W48 cfg2 shapes, HIP events on the
 launch stream: forward conv, input-gradient conv, weight gradient, BatchNorm passes.  Development tool (GPU box)."""
 import ctypes
 import os

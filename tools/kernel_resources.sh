@@ -1,5 +1,5 @@
 #!/bin/bash
-# register / spill / occupancy table of one .hip source: tools/kernel_resources.sh otpose_amd/csrc/nhwc.hip [filter]
+# register / spill / occupancy table of one .hip source: tools/kernel_resources.sh otpose_amd/csrc/nhwc_conv.hip [filter]
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage -c "$1" -o /tmp/kr.o 2>&1 \
  | grep -E "Function Name|VGPRs:|AGPRs:|VGPRs Spill|SGPRs Spill|Occupancy|LDS Size" \
  | sed 's/.*remark: *//; s/\[-Rpass.*//' \

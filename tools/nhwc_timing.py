@@ -1,9 +1,9 @@
 #!/usr/bin/env python
 """Phase stamps of nhwc_conv_kernel from a development build of the library (-DOTP_NHWC_TIMING), GPU box only:
-    cd otpose_amd/csrc && hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DOTP_NHWC_TIMING -c nhwc.hip -o /tmp/nhwc_t.o &&
-    hipcc --offload-arch=gfx950 -shared -o /tmp/libotp_t.so /tmp/nhwc_t.o $(ls *.o | grep -v nhwc.o) && cd ../.. &&
+    cd otpose_amd/csrc && hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DOTP_NHWC_TIMING -c nhwc_conv.hip -o /tmp/nhwc_t.o &&
+    hipcc --offload-arch=gfx950 -shared -o /tmp/libotp_t.so /tmp/nhwc_t.o $(ls *.o | grep -v nhwc_conv.o) && cd ../.. &&
     OTPOSE_HIP_LIB=/tmp/libotp_t.so OTP_NHWC_NO_PIPE=1 python tools/nhwc_timing.py 48 48 96 72
-prints, per phase, the median / p90 over workgroups in shader cycles, and the workgroup start / end spread."""
+(only the stamped kernel's translation unit takes the define: nhwc_wgrad.hip in place of nhwc_conv.hip for the wgrad form) and prints, per phase, the median / p90 over workgroups in shader cycles, and the workgroup start / end spread."""
 import ctypes
 import os
 import sys

@@ -450,6 +450,39 @@ int otp_token_attn_backward(const void* q, const void* k, const void* v, const v
                             float scale, void* stream);
 int otp_token_attn_map(const void* q, const void* k, const void* key_mask, const void* lse, void* map, int B, int C, int nh, int T,
                        float scale, void* stream);
+/* ---- attention dropout mask: attention-probability dropout of the three attentions above (training; blocks.py:392,572, the
+ * `dropout` OTPose.py:93 hands to nn.MultiheadAttention).  The probability matrix of an attention is (G groups, R rows, Ccols
+ * columns) with G = B * n_head and
+ *     token attention    R = T (query),  Ccols = T (key)
+ *     local attention    R = T,          Ccols = window (slot j of the band, also at positions outside the sequence)
+ *     channel attention  R = hs (row of the hs x hs matrix, not padded to 16),  Ccols = hs
+ * and entry (g, i, j) is kept or dropped by a counter-based draw:
+ *     thr  = (uint32)(p * 65536.f + 0.5f)                      p in [0, 1); thr == 0: no dropout, the plain entry point runs
+ *     pair = ((uint64)g * R + i) * ((Ccols + 1) / 2) + (j >> 1)
+ *     h    = pair_lo * 0x9E3779B1 + seed_lo;  h ^= (pair_hi + seed_hi) * 0x85EBCA77;                        (uint32 arithmetic)
+ *            h ^= h >> 16;  h *= 0x21F0AAAD;  h ^= h >> 15;  h *= 0x735A2D97;  h ^= h >> 15
+ *     u16  = (j & 1) ? (h >> 16) : (h & 0xFFFF);    keep <=> u16 >= thr;    a survivor is multiplied by 65536.f / (65536 - thr)
+ * A pure function of (seed, g, i, j, p): independent of tile sizes, launch geometry and the direction of the pass, so the forward
+ * and the backward passes evaluate it in place and no mask tensor exists.  The softmax statistics stay those of the undropped P
+ * (lse, the saved probs band, the saved channel matrix); only the operand of the P v product is masked and scaled, and the backward
+ * uses dS = P (m dP - sum_j P m dP), dv from m P.  p outside [0, 1), or so close to 1 that thr reaches 65536 (p >= 1 - 2^-17), is OTP_ERR_BAD_ARG.  Everything else - shapes, workspaces,
+ * determinism (no atomics) - is as for the entry point without the suffix.
+ * otp_attn_dropout_keep writes the mask itself, keep_u8 (G, R, Ccols) uint8, 1 = kept: for tests and debugging. */
+int otp_attn_dropout_keep(void* keep_u8, int G, int R, int Ccols, float p, unsigned long long seed, void* stream);
+int otp_token_attn_forward_dropout(const void* q, const void* k, const void* v, const void* key_mask, void* out, void* lse, int B,
+                                   int C, int nh, int T, float scale, float p, unsigned long long seed, void* stream);
+int otp_token_attn_backward_dropout(const void* q, const void* k, const void* v, const void* key_mask, const void* out,
+                                    const void* lse, const void* dout, void* dq, void* dk, void* dv, void* workspace, int B, int C,
+                                    int nh, int T, float scale, float p, unsigned long long seed, void* stream);
+int otp_local_attn_dropout(const void* q, const void* k, const void* v, const void* rel_pe, void* out, void* probs, int B, int C,
+                           int T, int n_head, int window, float scale, float p, unsigned long long seed, void* stream);
+int otp_local_attn_backward_dropout(const void* q, const void* k, const void* v, const void* probs, const void* gout, void* gq,
+                                    void* gk, void* gv, void* grel, void* ws, size_t ws_bytes, int B, int C, int T, int n_head,
+                                    int window, float scale, float p, unsigned long long seed, void* stream);
+/* channel attention: the workspace holds one more (B n_head, HSP, HSP) matrix, m P, behind the undropped P that the backward keeps */
+size_t otp_chan_attn_dropout_workspace(int B, int C, int T, int n_head);
+int otp_chan_attn_dropout(const void* q, const void* k, const void* v, void* out, void* workspace, size_t workspace_bytes, int B,
+                          int C, int T, int n_head, float scale, float p, unsigned long long seed, void* stream);
 /* conv embedding layer of ConvTransformer (ConvVideoTransformer.py:60-78, 129-135; csrc/convembd.hip) as one launch, exact fp32
  * (f32 MFMA = an fmaf chain; mean first, then the centred sum of squares, cross-wave sums in a fixed order):
  *   z = Conv2d(Cin, Cout, ks, stride 1, padding ks / 2)(x),  x (B, Cin, H, W), zero padding;  v = z + bias[c] (bias may be NULL)
@@ -670,6 +703,10 @@ int otp_transpose_scale(const void* in, void* out, int batches, int R, int Cc, f
 /* slabs (BH, NS, HSP, HSP) partial dP, P (BH, HSP, HSP) -> dS, dS^T, P^T (BH, HSP, HSP), HSP = hs rounded up to 16 */
 int otp_softmax_backward(const void* slabs, const void* P, void* dS, void* dST, void* PT, int BH, int hs, int NS,
                          void* stream);
+/* the same under attention-probability dropout (the mask definition above, G = BH, R = Ccols = hs): dP is multiplied by the mask
+ * before softmax', and PT receives (m P)^T, the matrix dv is formed with */
+int otp_softmax_backward_dropout(const void* slabs, const void* P, void* dS, void* dST, void* PT, int BH, int hs, int NS, float p,
+                                 unsigned long long seed, void* stream);
 /* channel LayerNorm backward: grad_x, and dy_xhat = grad_y * xhat so that grad_gamma = otp_channel_sum(dy_xhat),
  * grad_beta = otp_channel_sum(grad_y) */
 int otp_ln_channel_backward(const void* x, const void* grad_y, const void* gamma, void* grad_x, void* dy_xhat, int B, int C,

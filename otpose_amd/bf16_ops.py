@@ -14,6 +14,7 @@ import torch
 from torch.autograd import Function
 
 from . import hip
+from .attn_dropout import draw_seed
 from .ops import out_hw, require_gpu
 from .train_ops import TrainRoutes, channel_sum, current_routes, grad_slot
 
@@ -550,15 +551,6 @@ class GeluFunction(Function):
 gelu = GeluFunction.apply
 
 
-def _draw_seed(device):
-    """A 64-bit seed for a counter-based draw from PyTorch's CUDA generator state (seed, Philox offset), advancing the offset like a
-    random op does: ``torch.manual_seed`` makes the step's draws repeat, consecutive calls differ.  Host side only."""
-    gen = torch.cuda.default_generators[device.index if device.index is not None else torch.cuda.current_device()]
-    off = gen.get_offset()
-    gen.set_offset(off + 4)
-    return (gen.initial_seed() * 0x9E3779B97F4A7C15 + (off + 1) * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
-
-
 class GeluDropoutFunction(Function):
     """``dropout(gelu(x), p)`` of the TransformerBlock MLP (model/blocks.py:250-251, training mode) on bf16 as ONE pass each way
     (``otp_gelu_dropout_bf16_*``): the separate GELU + ``F.dropout`` launches cost a 240 MB pass forward and a 360 MB one backward more."""
@@ -588,7 +580,7 @@ def gelu_dropout(x, p, seed=None):
     """``F.dropout(gelu(x), p, training=True)`` on a bf16 tensor (numel % 8 == 0); ``seed``: None draws one from the CUDA generator."""
     if not p > 0.0:
         return gelu(x)
-    return GeluDropoutFunction.apply(x, p, _draw_seed(x.device) if seed is None else seed)
+    return GeluDropoutFunction.apply(x, p, draw_seed(x.device) if seed is None else seed)
 
 
 class MlpInteriorFunction(Function):
@@ -655,7 +647,7 @@ def mlp_interior_supported(x, w1, w2):
 
 def mlp_interior(x, w1, b1, w2, b2, p, seed=None):
     """The MLP interior on a (B, 1, T, CS) bf16 tensor -> (B, C, 1, T) fp32; ``p`` = dropout rate behind the GELU (0: none)."""
-    return MlpInteriorFunction.apply(x, w1, b1, w2, b2, p, _draw_seed(x.device) if (seed is None and p > 0.0) else (seed or 0))
+    return MlpInteriorFunction.apply(x, w1, b1, w2, b2, p, draw_seed(x.device) if (seed is None and p > 0.0) else (seed or 0))
 
 
 class ToNhwcFunction(Function):

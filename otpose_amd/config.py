@@ -27,6 +27,10 @@ The token encoders (reference model/OTPose.py:26-159, the DETR-style ``Transform
 ``MODEL.TOKEN_FFN`` (2 x the width), ``MODEL.TOKEN_PRE_NORM`` (False), ``MODEL.TOKEN_PE`` (``"sine"``, ``"learnable"`` or
 ``"none"``: the tables ``temporal_pos_embedding`` / ``flow_pos_embedding`` of OTPose.py:259-279; with ``"sine"`` the flow encoder
 runs without a table, width J = 17 has none).  A malformed value raises ``ValueError`` also when no layer is asked for.
+Attention-probability dropout, training only (reference model/blocks.py:392,572 and the ``dropout`` OTPose.py:93 hands to
+``nn.MultiheadAttention``; its OTPose.py:209-216 leaves the rate at 0): ``MODEL.ATTN_PDROP`` (0.0) for the two temporal encoders,
+``MODEL.FLOW_ATTN_PDROP`` (0.0) for the flow encoder, ``MODEL.TOKEN_ATTN_DROPOUT`` (0.0) for the token encoders; floats in [0, 1).
+The training graph applies the first two to the channel attention; together with local windows for the same encoder they raise ``ValueError``.
 """
 from __future__ import annotations
 

@@ -81,6 +81,42 @@ __device__ __forceinline__ float otp_row16_sum(float v) {
     return v;
 }
 
+// ---- counter-based dropout draws ------------------------------------------------------------------------------------------------
+// A hash of (element pair, 64-bit seed) with the lowbias32 finaliser: two 16-bit uniforms per 32-bit hash, keep <=> u16 >= round(65536 p).
+// Users: the bf16 training path (csrc/hb.h: otp_drop_keep8) and the attention-probability dropout below.
+__device__ __forceinline__ uint32_t otp_drop_hash(size_t pair, uint32_t s0, uint32_t s1) {
+    uint32_t h = (uint32_t)pair * 0x9E3779B1u + s0;
+    h ^= ((uint32_t)(pair >> 32) + s1) * 0x85EBCA77u;
+    h ^= h >> 16; h *= 0x21F0AAADu; h ^= h >> 15; h *= 0x735A2D97u; h ^= h >> 15;
+    return h;
+}
+// Attention-probability dropout (include/otpose_hip.h, "attention dropout mask"): the probability matrix of an attention is
+// (G groups, R rows, Ccols columns); entry (g, i, j) draws from pair ((g R + i) ceil(Ccols / 2) + j / 2), the low half of the hash
+// for an even j, the high half for an odd one.  A pure function of (seed, g, i, j, p): every kernel that needs the mask - forward,
+// both backward passes, the mask writer - evaluates it in place through these three functions.
+struct otp_attn_drop {
+    uint32_t s0, s1, thr;
+    float keep_scale;                                              // 65536 / (65536 - thr): what a survivor is multiplied by
+};
+// a rate is p in [0, 1) whose threshold stays below 65536 (p < 1 - 2^-17: from there on every entry would be dropped); false for NaN
+static inline bool otp_attn_drop_rate_ok(float p) { return p >= 0.f && p < 1.f && (uint32_t)(p * 65536.f + 0.5f) < 65536u; }
+static inline otp_attn_drop otp_attn_drop_make(float p, unsigned long long seed) {   // p: otp_attn_drop_rate_ok
+    const uint32_t thr = (uint32_t)(p * 65536.f + 0.5f);
+    return otp_attn_drop{(uint32_t)seed, (uint32_t)(seed >> 32), thr, 65536.f / (float)(65536u - thr)};
+}
+// first pair of row (g R + i): add j / 2 for the pair of column j
+__device__ __forceinline__ uint64_t otp_attn_drop_row(uint64_t row, int Ccols) { return row * (uint64_t)((Ccols + 1) >> 1); }
+__device__ __forceinline__ uint32_t otp_attn_drop_draw(const otp_attn_drop& d, uint64_t pair) {
+    return otp_drop_hash((size_t)pair, d.s0, d.s1);
+}
+// the factor of column j (only its parity counts) from its pair's hash: keep_scale for a survivor, 0 for a dropped entry
+__device__ __forceinline__ float otp_attn_drop_factor(const otp_attn_drop& d, uint32_t h, int j) {
+    return ((j & 1) ? (h >> 16) : (h & 0xFFFFu)) >= d.thr ? d.keep_scale : 0.f;
+}
+__device__ __forceinline__ float otp_attn_drop_at(const otp_attn_drop& d, uint64_t row_pair, int j) {
+    return otp_attn_drop_factor(d, otp_attn_drop_draw(d, row_pair + (uint64_t)(j >> 1)), j);
+}
+
 // ---- GELU ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float otp_gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
 // erf-GELU on a pair of accumulator values, branch-free and in packed-f32 form (v_pk_fma_f32): erf(t) = t P(t^2) / Q(t^2)

@@ -33,15 +33,9 @@ inline int otp_hbpw_ks(int Cin) {               // the instantiated k-step count
     const int k = (Cin + 31) / 32;
     return k <= 2 ? 2 : (k <= 4 ? 4 : (k == 5 ? 5 : (k <= 8 ? 8 : (k <= 12 ? 12 : (k <= 17 ? 17 : 0)))));
 }
-// Dropout draws of the bf16 training path (csrc/nhwc_pass.hip: gelu_dropout_bf16_*, csrc/hb.hip: the MLP up-projection's epilogue): a
-// counter-based hash of (element pair, seed), two 16-bit uniforms per 32-bit hash (lowbias32 finaliser), keep <=> u16 >= round(65536 p).
+// Dropout draws of the bf16 training path (csrc/nhwc_pass.hip: gelu_dropout_bf16_*, csrc/hb.hip: the MLP up-projection's epilogue): the
+// counter-based hash of (element pair, seed) of csrc/common.h (otp_drop_hash), keep <=> u16 >= round(65536 p).
 // Unit u = elements 8 u .. 8 u + 7 of the tensor; bit j of the result = element 8 u + j is kept.
-__device__ __forceinline__ uint32_t otp_drop_hash(size_t pair, uint32_t s0, uint32_t s1) {
-    uint32_t h = (uint32_t)pair * 0x9E3779B1u + s0;
-    h ^= ((uint32_t)(pair >> 32) + s1) * 0x85EBCA77u;
-    h ^= h >> 16; h *= 0x21F0AAADu; h ^= h >> 15; h *= 0x735A2D97u; h ^= h >> 15;
-    return h;
-}
 __device__ __forceinline__ unsigned otp_drop_keep8(size_t u, uint32_t s0, uint32_t s1, uint32_t thr) {
     unsigned bits = 0;
 #pragma unroll

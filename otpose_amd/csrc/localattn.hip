@@ -201,14 +201,31 @@ __device__ __forceinline__ void la_band_store(float* __restrict__ band, const fl
     }
 }
 
-// grid (tiles, B * n_head)
+// Attention-probability dropout (csrc/common.h: otp_attn_drop): the band is entry (g = bh, i = t, j = slot) of a (B nh, T, W)
+// matrix, slots outside the sequence included (P is zero there).  band[m][j] *= the factor of (bh, t0 + m, j): W / 2 + 1 hashes a row
 template <int w>
-__global__ __launch_bounds__(LA_THREADS) void local_attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                                    const float* __restrict__ v, const float* __restrict__ rel_pe,
-                                                                    float* __restrict__ out, float* __restrict__ probs, int hs,
-                                                                    int T, int n_head, float scale, int vec_i) {
+__device__ __forceinline__ void la_band_drop(float (&band)[LA_TPT][la_dims<w>::W], const otp_attn_drop& drop, int bh, int T, int t0) {
     typedef la_dims<w> D;
-    __shared__ __attribute__((aligned(16))) float lds[D::LDS_WORDS];
+#pragma unroll
+    for (int m = 0; m < LA_TPT; ++m) {
+        const uint64_t row = otp_attn_drop_row((uint64_t)bh * T + (uint64_t)(t0 + m), D::W);
+#pragma unroll
+        for (int j2 = 0; j2 <= w; ++j2) {
+            const uint32_t h = otp_attn_drop_draw(drop, row + j2);
+            band[m][2 * j2] *= otp_attn_drop_factor(drop, h, 0);
+            if (2 * j2 + 1 < D::W) band[m][2 * j2 + 1] *= otp_attn_drop_factor(drop, h, 1);
+        }
+    }
+}
+
+// The three kernels are bodies with a DROP flag under two __global__ wrappers each (grid (tiles, B * n_head)): DROP = false is the
+// code without a hash in it, under the kernel name and arguments it always had.
+template <int w, bool DROP>
+__device__ __forceinline__ void local_attn_fwd_body(float* lds, const float* __restrict__ q, const float* __restrict__ k,
+                                                    const float* __restrict__ v, const float* __restrict__ rel_pe,
+                                                    float* __restrict__ out, float* __restrict__ probs, int hs,
+                                                    int T, int n_head, float scale, int vec_i, const otp_attn_drop& drop) {
+    typedef la_dims<w> D;
     const bool vec = vec_i != 0;
     const int bh = blockIdx.y, head = bh % n_head;
     const int tile0 = blockIdx.x * LA_TILE, t0 = tile0 + threadIdx.x * LA_TPT;
@@ -240,25 +257,43 @@ __global__ __launch_bounds__(LA_THREADS) void local_attn_fwd_kernel(const float*
 #pragma unroll
         for (int j = 0; j < D::W; ++j) s[m][j] *= inv;
     }
-    if (probs) la_band_store<w>(probs + (size_t)bh * T * D::W, s, T, t0, vec);
+    if (probs) la_band_store<w>(probs + (size_t)bh * T * D::W, s, T, t0, vec);     // the undropped band
+    if (DROP) la_band_drop<w>(s, drop, bh, T, t0);
     la_band_apply<w>(s, v + base, lds, out + base, 1.f, hs, T, tile0, t0, vec);
+}
+template <int w>
+__global__ __launch_bounds__(LA_THREADS) void local_attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                    const float* __restrict__ v, const float* __restrict__ rel_pe,
+                                                                    float* __restrict__ out, float* __restrict__ probs, int hs,
+                                                                    int T, int n_head, float scale, int vec_i) {
+    __shared__ __attribute__((aligned(16))) float lds[la_dims<w>::LDS_WORDS];
+    local_attn_fwd_body<w, false>(lds, q, k, v, rel_pe, out, probs, hs, T, n_head, scale, vec_i, otp_attn_drop{});
+}
+template <int w>
+__global__ __launch_bounds__(LA_THREADS) void local_attn_fwd_drop_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                         const float* __restrict__ v, const float* __restrict__ rel_pe,
+                                                                         float* __restrict__ out, float* __restrict__ probs, int hs,
+                                                                         int T, int n_head, float scale, int vec_i, otp_attn_drop drop) {
+    __shared__ __attribute__((aligned(16))) float lds[la_dims<w>::LDS_WORDS];
+    local_attn_fwd_body<w, true>(lds, q, k, v, rel_pe, out, probs, hs, T, n_head, scale, vec_i, drop);
 }
 
 // backward A: dS (BH, T, W), dq, and partial[(bh * tiles + tile) * W + j] = sum over the tile's tokens of dS[.][j] when non-null
-template <int w>
-__global__ __launch_bounds__(LA_THREADS) void local_attn_bwd_a_kernel(const float* __restrict__ k, const float* __restrict__ v,
-                                                                      const float* __restrict__ probs, const float* __restrict__ gout,
-                                                                      float* __restrict__ gq, float* __restrict__ ds,
-                                                                      float* __restrict__ partial, int hs, int T, float scale,
-                                                                      int vec_i) {
+// with DROP: dS = P (m dP - sum_j P m dP)
+template <int w, bool DROP>
+__device__ __forceinline__ void local_attn_bwd_a_body(float* lds, const float* __restrict__ k, const float* __restrict__ v,
+                                                      const float* __restrict__ probs, const float* __restrict__ gout,
+                                                      float* __restrict__ gq, float* __restrict__ ds,
+                                                      float* __restrict__ partial, int hs, int T, float scale,
+                                                      int vec_i, const otp_attn_drop& drop) {
     typedef la_dims<w> D;
-    __shared__ __attribute__((aligned(16))) float lds[D::LDS_WORDS];
     const bool vec = vec_i != 0;
     const int bh = blockIdx.y;
     const int tile0 = blockIdx.x * LA_TILE, t0 = tile0 + threadIdx.x * LA_TPT;
     const size_t base = (size_t)bh * hs * T, band = (size_t)bh * T * D::W;
     float d[LA_TPT][D::W];
     la_band_scores<w>(gout + base, v + base, lds, d, hs, T, tile0, t0, vec);           // dP
+    if (DROP) la_band_drop<w>(d, drop, bh, T, t0);
     {
         float p[LA_TPT][D::W];
         la_band_load<w>(probs + band, p, T, t0, vec);      // zero at positions outside the sequence and for tokens past T
@@ -285,6 +320,24 @@ __global__ __launch_bounds__(LA_THREADS) void local_attn_bwd_a_kernel(const floa
     }
     la_band_apply<w>(d, k + base, lds, gq + base, scale, hs, T, tile0, t0, vec);
 }
+template <int w>
+__global__ __launch_bounds__(LA_THREADS) void local_attn_bwd_a_kernel(const float* __restrict__ k, const float* __restrict__ v,
+                                                                      const float* __restrict__ probs, const float* __restrict__ gout,
+                                                                      float* __restrict__ gq, float* __restrict__ ds,
+                                                                      float* __restrict__ partial, int hs, int T, float scale,
+                                                                      int vec_i) {
+    __shared__ __attribute__((aligned(16))) float lds[la_dims<w>::LDS_WORDS];
+    local_attn_bwd_a_body<w, false>(lds, k, v, probs, gout, gq, ds, partial, hs, T, scale, vec_i, otp_attn_drop{});
+}
+template <int w>
+__global__ __launch_bounds__(LA_THREADS) void local_attn_bwd_a_drop_kernel(const float* __restrict__ k, const float* __restrict__ v,
+                                                                           const float* __restrict__ probs,
+                                                                           const float* __restrict__ gout, float* __restrict__ gq,
+                                                                           float* __restrict__ ds, float* __restrict__ partial, int hs,
+                                                                           int T, float scale, int vec_i, otp_attn_drop drop) {
+    __shared__ __attribute__((aligned(16))) float lds[la_dims<w>::LDS_WORDS];
+    local_attn_bwd_a_body<w, true>(lds, k, v, probs, gout, gq, ds, partial, hs, T, scale, vec_i, drop);
+}
 
 // the transposed band of the thread's tokens: r[m][j'] = band[u + j' - w][2w - j'] with u = t0 + m, zero where that row is
 // outside the sequence (the entry itself then refers to position u, which is inside whenever u < T)
@@ -300,14 +353,29 @@ __device__ __forceinline__ void la_band_gather(const float* __restrict__ band, f
         }
 }
 
-// backward B: dk and dv in gather form
+// the factors of the transposed band: r[m][j'] *= the factor of (bh, u + j' - w, 2w - j'), one hash each (rows outside the
+// sequence hold zeros already)
 template <int w>
-__global__ __launch_bounds__(LA_THREADS) void local_attn_bwd_b_kernel(const float* __restrict__ q, const float* __restrict__ probs,
-                                                                      const float* __restrict__ ds, const float* __restrict__ gout,
-                                                                      float* __restrict__ gk, float* __restrict__ gv, int hs, int T,
-                                                                      float scale, int vec_i) {
+__device__ __forceinline__ void la_band_gather_drop(float (&r)[LA_TPT][la_dims<w>::W], const otp_attn_drop& drop, int bh, int T, int t0) {
     typedef la_dims<w> D;
-    __shared__ __attribute__((aligned(16))) float lds[D::LDS_WORDS];
+#pragma unroll
+    for (int m = 0; m < LA_TPT; ++m) {
+        const uint64_t row0 = otp_attn_drop_row((uint64_t)bh * T + (uint64_t)(t0 + m) - (uint64_t)w, D::W);     // row u - w (wraps below 0: unused)
+#pragma unroll
+        for (int j = 0; j < D::W; ++j) {
+            const int t = t0 + m + j - w;
+            if (t >= 0 && t < T) r[m][j] *= otp_attn_drop_at(drop, row0 + (uint64_t)(j * (w + 1)), 2 * w - j);
+        }
+    }
+}
+
+// backward B: dk and dv in gather form; with DROP dv gathers m P
+template <int w, bool DROP>
+__device__ __forceinline__ void local_attn_bwd_b_body(float* lds, const float* __restrict__ q, const float* __restrict__ probs,
+                                                      const float* __restrict__ ds, const float* __restrict__ gout,
+                                                      float* __restrict__ gk, float* __restrict__ gv, int hs, int T,
+                                                      float scale, int vec_i, const otp_attn_drop& drop) {
+    typedef la_dims<w> D;
     const bool vec = vec_i != 0;
     const int bh = blockIdx.y;
     const int tile0 = blockIdx.x * LA_TILE, t0 = tile0 + threadIdx.x * LA_TPT;
@@ -316,7 +384,24 @@ __global__ __launch_bounds__(LA_THREADS) void local_attn_bwd_b_kernel(const floa
     la_band_gather<w>(ds + band, c, T, t0);
     la_band_apply<w>(c, q + base, lds, gk + base, scale, hs, T, tile0, t0, vec);
     la_band_gather<w>(probs + band, c, T, t0);
+    if (DROP) la_band_gather_drop<w>(c, drop, bh, T, t0);
     la_band_apply<w>(c, gout + base, lds, gv + base, 1.f, hs, T, tile0, t0, vec);
+}
+template <int w>
+__global__ __launch_bounds__(LA_THREADS) void local_attn_bwd_b_kernel(const float* __restrict__ q, const float* __restrict__ probs,
+                                                                      const float* __restrict__ ds, const float* __restrict__ gout,
+                                                                      float* __restrict__ gk, float* __restrict__ gv, int hs, int T,
+                                                                      float scale, int vec_i) {
+    __shared__ __attribute__((aligned(16))) float lds[la_dims<w>::LDS_WORDS];
+    local_attn_bwd_b_body<w, false>(lds, q, probs, ds, gout, gk, gv, hs, T, scale, vec_i, otp_attn_drop{});
+}
+template <int w>
+__global__ __launch_bounds__(LA_THREADS) void local_attn_bwd_b_drop_kernel(const float* __restrict__ q, const float* __restrict__ probs,
+                                                                           const float* __restrict__ ds, const float* __restrict__ gout,
+                                                                           float* __restrict__ gk, float* __restrict__ gv, int hs,
+                                                                           int T, float scale, int vec_i, otp_attn_drop drop) {
+    __shared__ __attribute__((aligned(16))) float lds[la_dims<w>::LDS_WORDS];
+    local_attn_bwd_b_body<w, true>(lds, q, probs, ds, gout, gk, gv, hs, T, scale, vec_i, drop);
 }
 
 // grel[head][j] = sum over b, then tile, of the workgroup partials (one thread per word, fixed order)
@@ -375,6 +460,22 @@ extern "C" int otp_local_attn(const void* q, const void* k, const void* v, const
     return otp_launch_status();
 }
 
+extern "C" int otp_local_attn_dropout(const void* q, const void* k, const void* v, const void* rel_pe, void* out, void* probs, int B,
+                                      int C, int T, int n_head, int window, float scale, float p, unsigned long long seed,
+                                      void* stream) {
+    if (!q || !k || !v || !out || !la_shape_ok(B, C, T, n_head, window) || !otp_attn_drop_rate_ok(p)) return OTP_ERR_BAD_ARG;
+    const otp_attn_drop drop = otp_attn_drop_make(p, seed);
+    if (!drop.thr) return otp_local_attn(q, k, v, rel_pe, out, probs, B, C, T, n_head, window, scale, stream);
+    const int hs = C / n_head, w = window / 2;
+    const int vec = T % 4 == 0 && la_aligned16({q, k, v, out, probs});
+    const dim3 grid(otp_ceil_div(T, LA_TILE), B * n_head);
+    auto st = static_cast<hipStream_t>(stream);
+    LA_DISPATCH(w, hipLaunchKernelGGL(local_attn_fwd_drop_kernel<LW>, grid, dim3(LA_THREADS), 0, st, static_cast<const float*>(q),
+                                      static_cast<const float*>(k), static_cast<const float*>(v), static_cast<const float*>(rel_pe),
+                                      static_cast<float*>(out), static_cast<float*>(probs), hs, T, n_head, scale, vec, drop));
+    return otp_launch_status();
+}
+
 // dS (B nh, T, window) and the per-workgroup column sums of dS (B nh, tiles, window), both fp32
 extern "C" size_t otp_local_attn_backward_workspace(int B, int C, int T, int n_head, int window) {
     if (!la_shape_ok(B, C, T, n_head, window)) return 0;
@@ -401,6 +502,36 @@ extern "C" int otp_local_attn_backward(const void* q, const void* k, const void*
                            grel ? partial : nullptr, hs, T, scale, vec);
         hipLaunchKernelGGL(local_attn_bwd_b_kernel<LW>, grid, dim3(LA_THREADS), 0, st, qf, pf, static_cast<const float*>(ds), gf,
                            static_cast<float*>(gk), static_cast<float*>(gv), hs, T, scale, vec);
+    });
+    if (grel)
+        hipLaunchKernelGGL(local_attn_grel_kernel, dim3(otp_ceil_div(n_head * window, 64)), dim3(64), 0, st,
+                           static_cast<const float*>(partial), static_cast<float*>(grel), B, n_head, tiles, window);
+    return otp_launch_status();
+}
+
+extern "C" int otp_local_attn_backward_dropout(const void* q, const void* k, const void* v, const void* probs, const void* gout,
+                                               void* gq, void* gk, void* gv, void* grel, void* ws, size_t ws_bytes, int B, int C, int T,
+                                               int n_head, int window, float scale, float p, unsigned long long seed, void* stream) {
+    if (!q || !k || !v || !probs || !gout || !gq || !gk || !gv || !ws || !la_shape_ok(B, C, T, n_head, window) ||
+        !otp_attn_drop_rate_ok(p))
+        return OTP_ERR_BAD_ARG;
+    const otp_attn_drop drop = otp_attn_drop_make(p, seed);
+    if (!drop.thr)
+        return otp_local_attn_backward(q, k, v, probs, gout, gq, gk, gv, grel, ws, ws_bytes, B, C, T, n_head, window, scale, stream);
+    if (ws_bytes < otp_local_attn_backward_workspace(B, C, T, n_head, window)) return OTP_ERR_WORKSPACE;
+    const int hs = C / n_head, w = window / 2, tiles = otp_ceil_div(T, LA_TILE);
+    float* ds = static_cast<float*>(ws);
+    float* partial = ds + (size_t)B * n_head * T * window;
+    const int vec = T % 4 == 0 && la_aligned16({q, k, v, probs, gout, gq, gk, gv, ws});
+    const dim3 grid(tiles, B * n_head);
+    auto st = static_cast<hipStream_t>(stream);
+    const float *qf = static_cast<const float*>(q), *kf = static_cast<const float*>(k), *vf = static_cast<const float*>(v),
+                *pf = static_cast<const float*>(probs), *gf = static_cast<const float*>(gout);
+    LA_DISPATCH(w, {
+        hipLaunchKernelGGL(local_attn_bwd_a_drop_kernel<LW>, grid, dim3(LA_THREADS), 0, st, kf, vf, pf, gf, static_cast<float*>(gq),
+                           ds, grel ? partial : nullptr, hs, T, scale, vec, drop);
+        hipLaunchKernelGGL(local_attn_bwd_b_drop_kernel<LW>, grid, dim3(LA_THREADS), 0, st, qf, pf, static_cast<const float*>(ds), gf,
+                           static_cast<float*>(gk), static_cast<float*>(gv), hs, T, scale, vec, drop);
     });
     if (grel)
         hipLaunchKernelGGL(local_attn_grel_kernel, dim3(otp_ceil_div(n_head * window, 64)), dim3(64), 0, st,

@@ -111,11 +111,15 @@ __device__ __forceinline__ void ta_stage_keys(float* kbias, bool live) {
     if (threadIdx.x < TA_TILE) kbias[threadIdx.x] = live ? 0.f : -INFINITY;
 }
 
-template <int NCB>
-__global__ __launch_bounds__(TA_THREADS) void tokattn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                                 const float* __restrict__ v, const unsigned char* __restrict__ mask,
-                                                                 float* __restrict__ out, float* __restrict__ lse, int C, int nh,
-                                                                 int T, float scale, int tiles) {
+// The three training kernels are bodies with a DROP flag (attention-probability dropout, csrc/common.h: otp_attn_drop) under two
+// __global__ wrappers each: DROP = false is the code without a hash in it, under the kernel name and arguments it always had.
+// The mask of P[i][j] of head bh is entry (g = bh, i, j) of a (B nh, T, T) matrix; a lane's 16 staged tokens 16 g + 4 r + kb of a
+// tile are consecutive, so where the staged side is the key side (forward, backward A) one hash serves kb = 0, 1 and one kb = 2, 3.
+template <int NCB, bool DROP>
+__device__ __forceinline__ void tokattn_fwd_body(const float* __restrict__ q, const float* __restrict__ k,
+                                                 const float* __restrict__ v, const unsigned char* __restrict__ mask,
+                                                 float* __restrict__ out, float* __restrict__ lse, int C, int nh,
+                                                 int T, float scale, int tiles, const otp_attn_drop& drop) {
     extern __shared__ __attribute__((aligned(16))) float ta_smem[];
     float* Ks = ta_smem;
     float* Vs = Ks + 16 * NCB * TA_STRIDE;
@@ -132,6 +136,7 @@ __global__ __launch_bounds__(TA_THREADS) void tokattn_fwd_kernel(const float* __
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) o[cb] = otp_f32x4{0.f, 0.f, 0.f, 0.f};
     float m = -INFINITY, l = 0.f;
+    const uint64_t drop_row = DROP ? otp_attn_drop_row((uint64_t)bh * T + tq, T) : 0;
 
     for (int kt = 0; kt < tiles; ++kt) {
         const bool live = ta_key_live(mask_row, T, kt * TA_TILE);
@@ -173,19 +178,46 @@ __global__ __launch_bounds__(TA_THREADS) void tokattn_fwd_kernel(const float* __
         m = m_new;
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) o[cb] *= alpha;
+        if (DROP) {                                                // l and m above are the undropped ones: only the operand of P v
+            const uint64_t pair0 = drop_row + (uint64_t)((kt * TA_TILE + 16 * g) >> 1);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int h2 = 0; h2 < 2; ++h2) {
+                    const uint32_t h = otp_attn_drop_draw(drop, pair0 + 2 * r + h2);
+                    s[2 * h2][r] *= otp_attn_drop_factor(drop, h, 0);
+                    s[2 * h2 + 1][r] *= otp_attn_drop_factor(drop, h, 1);
+                }
+        }
         ta_second<NCB>(o, Vs, s);
     }
     ta_store<NCB>(out + head, o, 1.f / l, hd, T, tq);
     if (lse && g == 0 && tq < T) lse[(size_t)bh * T + tq] = m + logf(l);
 }
-
 template <int NCB>
-__global__ __launch_bounds__(TA_THREADS) void tokattn_bwd_a_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                                   const float* __restrict__ v, const unsigned char* __restrict__ mask,
-                                                                   const float* __restrict__ out, const float* __restrict__ lse,
-                                                                   const float* __restrict__ dout, float* __restrict__ dq,
-                                                                   float* __restrict__ dsum, int C, int nh, int T, float scale,
-                                                                   int tiles) {
+__global__ __launch_bounds__(TA_THREADS) void tokattn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                 const float* __restrict__ v, const unsigned char* __restrict__ mask,
+                                                                 float* __restrict__ out, float* __restrict__ lse, int C, int nh,
+                                                                 int T, float scale, int tiles) {
+    tokattn_fwd_body<NCB, false>(q, k, v, mask, out, lse, C, nh, T, scale, tiles, otp_attn_drop{});
+}
+template <int NCB>
+__global__ __launch_bounds__(TA_THREADS) void tokattn_fwd_drop_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                      const float* __restrict__ v,
+                                                                      const unsigned char* __restrict__ mask, float* __restrict__ out,
+                                                                      float* __restrict__ lse, int C, int nh, int T, float scale,
+                                                                      int tiles, otp_attn_drop drop) {
+    tokattn_fwd_body<NCB, true>(q, k, v, mask, out, lse, C, nh, T, scale, tiles, drop);
+}
+
+// with DROP: dP[i][j] = m[i][j] (dO_i . v_j); D = sum_c dO O is the row sum of P m dP already, O being the dropped output
+template <int NCB, bool DROP>
+__device__ __forceinline__ void tokattn_bwd_a_body(const float* __restrict__ q, const float* __restrict__ k,
+                                                   const float* __restrict__ v, const unsigned char* __restrict__ mask,
+                                                   const float* __restrict__ out, const float* __restrict__ lse,
+                                                   const float* __restrict__ dout, float* __restrict__ dq,
+                                                   float* __restrict__ dsum, int C, int nh, int T, float scale,
+                                                   int tiles, const otp_attn_drop& drop) {
     extern __shared__ __attribute__((aligned(16))) float ta_smem[];
     float* Ks = ta_smem;
     float* Vs = Ks + 16 * NCB * TA_STRIDE;
@@ -211,6 +243,7 @@ __global__ __launch_bounds__(TA_THREADS) void tokattn_bwd_a_kernel(const float* 
     otp_f32x4 acc[NCB];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) acc[cb] = otp_f32x4{0.f, 0.f, 0.f, 0.f};
+    const uint64_t drop_row = DROP ? otp_attn_drop_row((uint64_t)bh * T + tq, T) : 0;
 
     for (int kt = 0; kt < tiles; ++kt) {
         const bool live = ta_key_live(mask_row, T, kt * TA_TILE);
@@ -225,6 +258,17 @@ __global__ __launch_bounds__(TA_THREADS) void tokattn_bwd_a_kernel(const float* 
         for (int kb = 0; kb < 4; ++kb) s[kb] = dp[kb] = otp_f32x4{0.f, 0.f, 0.f, 0.f};
         ta_first<NCB>(s, Ks, qf);
         ta_first<NCB>(dp, Vs, gf);
+        if (DROP) {
+            const uint64_t pair0 = drop_row + (uint64_t)((kt * TA_TILE + 16 * g) >> 1);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int h2 = 0; h2 < 2; ++h2) {
+                    const uint32_t h = otp_attn_drop_draw(drop, pair0 + 2 * r + h2);
+                    dp[2 * h2][r] *= otp_attn_drop_factor(drop, h, 0);
+                    dp[2 * h2 + 1][r] *= otp_attn_drop_factor(drop, h, 1);
+                }
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const otp_f32x4 kb4 = *reinterpret_cast<const otp_f32x4*>(kbias + 16 * g + 4 * r);
@@ -238,14 +282,32 @@ __global__ __launch_bounds__(TA_THREADS) void tokattn_bwd_a_kernel(const float* 
     }
     ta_store<NCB>(dq + head, acc, scale, hd, T, tq);
 }
-
 template <int NCB>
-__global__ __launch_bounds__(TA_THREADS) void tokattn_bwd_b_kernel(const float* __restrict__ q, const float* __restrict__ k,
+__global__ __launch_bounds__(TA_THREADS) void tokattn_bwd_a_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                    const float* __restrict__ v, const unsigned char* __restrict__ mask,
-                                                                   const float* __restrict__ lse, const float* __restrict__ dout,
-                                                                   const float* __restrict__ dsum, float* __restrict__ dk,
-                                                                   float* __restrict__ dv, int C, int nh, int T, float scale,
+                                                                   const float* __restrict__ out, const float* __restrict__ lse,
+                                                                   const float* __restrict__ dout, float* __restrict__ dq,
+                                                                   float* __restrict__ dsum, int C, int nh, int T, float scale,
                                                                    int tiles) {
+    tokattn_bwd_a_body<NCB, false>(q, k, v, mask, out, lse, dout, dq, dsum, C, nh, T, scale, tiles, otp_attn_drop{});
+}
+template <int NCB>
+__global__ __launch_bounds__(TA_THREADS) void tokattn_bwd_a_drop_kernel(
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, const unsigned char* __restrict__ mask,
+    const float* __restrict__ out, const float* __restrict__ lse, const float* __restrict__ dout, float* __restrict__ dq,
+    float* __restrict__ dsum, int C, int nh, int T, float scale, int tiles, otp_attn_drop drop) {
+    tokattn_bwd_a_body<NCB, true>(q, k, v, mask, out, lse, dout, dq, dsum, C, nh, T, scale, tiles, drop);
+}
+
+// with DROP: the staged side is the query side, so a lane's 16 entries of a tile are 16 rows of the mask at its own key column -
+// one hash each; dv sums P m dO, dk the same dS as pass A
+template <int NCB, bool DROP>
+__device__ __forceinline__ void tokattn_bwd_b_body(const float* __restrict__ q, const float* __restrict__ k,
+                                                   const float* __restrict__ v, const unsigned char* __restrict__ mask,
+                                                   const float* __restrict__ lse, const float* __restrict__ dout,
+                                                   const float* __restrict__ dsum, float* __restrict__ dk,
+                                                   float* __restrict__ dv, int C, int nh, int T, float scale,
+                                                   int tiles, const otp_attn_drop& drop) {
     extern __shared__ __attribute__((aligned(16))) float ta_smem[];
     float* Qs = ta_smem;
     float* Gs = Qs + 16 * NCB * TA_STRIDE;
@@ -279,6 +341,9 @@ __global__ __launch_bounds__(TA_THREADS) void tokattn_bwd_b_kernel(const float* 
         for (int qb = 0; qb < 4; ++qb) s[qb] = dp[qb] = otp_f32x4{0.f, 0.f, 0.f, 0.f};
         ta_first<NCB>(s, Qs, kf);
         ta_first<NCB>(dp, Gs, vf);
+        // the pair of (first query of this lane group, own key); one row further is ceil(T / 2) pairs further
+        const uint64_t pair0 = DROP ? otp_attn_drop_row((uint64_t)bh * T + (uint64_t)(qt * TA_TILE + 16 * g), T) + (uint64_t)(tk >> 1) : 0;
+        const uint64_t row_pairs = (uint64_t)((T + 1) >> 1);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const otp_f32x4 l4 = *reinterpret_cast<const otp_f32x4*>(lse_s + 16 * g + 4 * r);
@@ -286,8 +351,14 @@ __global__ __launch_bounds__(TA_THREADS) void tokattn_bwd_b_kernel(const float* 
 #pragma unroll
             for (int qb = 0; qb < 4; ++qb) {
                 const float p = key_live ? expf(__fmul_rn(s[qb][r], scale) - l4[qb]) : 0.f;
-                s[qb][r] = p;
-                dp[qb][r] = p * (dp[qb][r] - d4[qb]);
+                if (DROP) {
+                    const float f = otp_attn_drop_factor(drop, otp_attn_drop_draw(drop, pair0 + (4 * r + qb) * row_pairs), tk);
+                    s[qb][r] = p * f;
+                    dp[qb][r] = p * (f * dp[qb][r] - d4[qb]);
+                } else {
+                    s[qb][r] = p;
+                    dp[qb][r] = p * (dp[qb][r] - d4[qb]);
+                }
             }
         }
         ta_second<NCB>(gv, Gs, s);
@@ -295,6 +366,22 @@ __global__ __launch_bounds__(TA_THREADS) void tokattn_bwd_b_kernel(const float* 
     }
     ta_store<NCB>(dk + head, gk, scale, hd, T, tk);
     ta_store<NCB>(dv + head, gv, 1.f, hd, T, tk);
+}
+template <int NCB>
+__global__ __launch_bounds__(TA_THREADS) void tokattn_bwd_b_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                   const float* __restrict__ v, const unsigned char* __restrict__ mask,
+                                                                   const float* __restrict__ lse, const float* __restrict__ dout,
+                                                                   const float* __restrict__ dsum, float* __restrict__ dk,
+                                                                   float* __restrict__ dv, int C, int nh, int T, float scale,
+                                                                   int tiles) {
+    tokattn_bwd_b_body<NCB, false>(q, k, v, mask, lse, dout, dsum, dk, dv, C, nh, T, scale, tiles, otp_attn_drop{});
+}
+template <int NCB>
+__global__ __launch_bounds__(TA_THREADS) void tokattn_bwd_b_drop_kernel(
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, const unsigned char* __restrict__ mask,
+    const float* __restrict__ lse, const float* __restrict__ dout, const float* __restrict__ dsum, float* __restrict__ dk,
+    float* __restrict__ dv, int C, int nh, int T, float scale, int tiles, otp_attn_drop drop) {
+    tokattn_bwd_b_body<NCB, true>(q, k, v, mask, lse, dout, dsum, dk, dv, C, nh, T, scale, tiles, drop);
 }
 
 template <int NCB>
@@ -412,6 +499,49 @@ extern "C" int otp_token_attn_backward(const void* q, const void* k, const void*
                   dsum, C, nh, T, scale, tiles);
         TA_LAUNCH(tokattn_bwd_b_kernel, grid, st, qf, kf, vf, mf, lf, gf, static_cast<const float*>(dsum), static_cast<float*>(dk),
                   static_cast<float*>(dv), C, nh, T, scale, tiles);
+    });
+    return otp_launch_status();
+}
+
+extern "C" int otp_token_attn_forward_dropout(const void* q, const void* k, const void* v, const void* key_mask, void* out, void* lse,
+                                              int B, int C, int nh, int T, float scale, float p, unsigned long long seed,
+                                              void* stream) {
+    if (!q || !k || !v || !out || !ta_shape_ok(B, C, nh, T) || !otp_attn_drop_rate_ok(p)) return OTP_ERR_BAD_ARG;
+    const otp_attn_drop drop = otp_attn_drop_make(p, seed);
+    if (!drop.thr) return otp_token_attn_forward(q, k, v, key_mask, out, lse, B, C, nh, T, scale, stream);
+    const int tiles = otp_ceil_div(T, TA_TILE);
+    const unsigned grid = ta_grid((size_t)B * nh, tiles);
+    if (!grid) return OTP_ERR_UNSUPPORTED;
+    auto st = static_cast<hipStream_t>(stream);
+    TA_DISPATCH(otp_ceil_div(C / nh, 16),
+                TA_LAUNCH(tokattn_fwd_drop_kernel, grid, st, static_cast<const float*>(q), static_cast<const float*>(k),
+                          static_cast<const float*>(v), static_cast<const unsigned char*>(key_mask), static_cast<float*>(out),
+                          static_cast<float*>(lse), C, nh, T, scale, tiles, drop));
+    return otp_launch_status();
+}
+
+extern "C" int otp_token_attn_backward_dropout(const void* q, const void* k, const void* v, const void* key_mask, const void* out,
+                                               const void* lse, const void* dout, void* dq, void* dk, void* dv, void* workspace,
+                                               int B, int C, int nh, int T, float scale, float p, unsigned long long seed,
+                                               void* stream) {
+    if (!q || !k || !v || !out || !lse || !dout || !dq || !dk || !dv || !workspace || !ta_shape_ok(B, C, nh, T) ||
+        !otp_attn_drop_rate_ok(p))
+        return OTP_ERR_BAD_ARG;
+    const otp_attn_drop drop = otp_attn_drop_make(p, seed);
+    if (!drop.thr) return otp_token_attn_backward(q, k, v, key_mask, out, lse, dout, dq, dk, dv, workspace, B, C, nh, T, scale, stream);
+    const int tiles = otp_ceil_div(T, TA_TILE);
+    const unsigned grid = ta_grid((size_t)B * nh, tiles);
+    if (!grid) return OTP_ERR_UNSUPPORTED;
+    auto st = static_cast<hipStream_t>(stream);
+    const float *qf = static_cast<const float*>(q), *kf = static_cast<const float*>(k), *vf = static_cast<const float*>(v),
+                *lf = static_cast<const float*>(lse), *gf = static_cast<const float*>(dout);
+    const unsigned char* mf = static_cast<const unsigned char*>(key_mask);
+    float* dsum = static_cast<float*>(workspace);
+    TA_DISPATCH(otp_ceil_div(C / nh, 16), {
+        TA_LAUNCH(tokattn_bwd_a_drop_kernel, grid, st, qf, kf, vf, mf, static_cast<const float*>(out), lf, gf,
+                  static_cast<float*>(dq), dsum, C, nh, T, scale, tiles, drop);
+        TA_LAUNCH(tokattn_bwd_b_drop_kernel, grid, st, qf, kf, vf, mf, lf, gf, static_cast<const float*>(dsum),
+                  static_cast<float*>(dk), static_cast<float*>(dv), C, nh, T, scale, tiles, drop);
     });
     return otp_launch_status();
 }

@@ -430,8 +430,11 @@ __global__ __launch_bounds__(256) void attn_scores_x3_kernel(const float* __rest
 // Phase 2: sum the slabs, scale, row softmax (one wave per row, shuffles for max / sum).
 // P (B*nh, HSP, HSP) with zero padding columns.  grid (B*nh, ceil(HSP / 4)): every wave of the chip gets a row
 // (a grid of B*nh workgroups alone left 7/8 of the CUs idle for 120 us).
-__global__ __launch_bounds__(256) void attn_softmax_kernel(const float* __restrict__ slabs, float* __restrict__ P,
-                                                            int hs, int HSP, int NS, float scale) {
+// A body with a DROP flag under two __global__ wrappers: with DROP (attention-probability dropout, csrc/common.h: otp_attn_drop, the
+// matrix is entry (g = bh, i = row, j = col) of (B nh, hs, hs)) PM receives m P for the apply step and P stays the undropped matrix.
+template <bool DROP>
+__device__ __forceinline__ void attn_softmax_body(const float* __restrict__ slabs, float* __restrict__ P, float* __restrict__ PM,
+                                                  int hs, int HSP, int NS, float scale, const otp_attn_drop& drop) {
     const int bh = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.y * 4 + wave;
     if (row >= HSP) return;
@@ -461,8 +464,24 @@ __global__ __launch_bounds__(256) void attn_softmax_kernel(const float* __restri
     float e0 = (row < hs && lane < hs) ? expf(v[0] - m) : 0.f;
     float e1 = (row < hs && lane + 64 < hs) ? expf(v[1] - m) : 0.f;
     const float den = wave_sum(e0 + e1);
-    if (lane < HSP) pb[row * HSP + lane] = row < hs ? e0 / den : 0.f;
-    if (lane + 64 < HSP) pb[row * HSP + lane + 64] = row < hs ? e1 / den : 0.f;
+    const float p0 = row < hs ? e0 / den : 0.f, p1 = row < hs ? e1 / den : 0.f;
+    if (lane < HSP) pb[row * HSP + lane] = p0;
+    if (lane + 64 < HSP) pb[row * HSP + lane + 64] = p1;
+    if (DROP) {
+        float* mb = PM + (size_t)bh * HSP * HSP;
+        const uint64_t rp = otp_attn_drop_row((uint64_t)bh * hs + row, hs);
+        if (lane < HSP) mb[row * HSP + lane] = p0 * otp_attn_drop_at(drop, rp, lane);
+        if (lane + 64 < HSP) mb[row * HSP + lane + 64] = p1 * otp_attn_drop_at(drop, rp, lane + 64);
+    }
+}
+__global__ __launch_bounds__(256) void attn_softmax_kernel(const float* __restrict__ slabs, float* __restrict__ P,
+                                                            int hs, int HSP, int NS, float scale) {
+    attn_softmax_body<false>(slabs, P, nullptr, hs, HSP, NS, scale, otp_attn_drop{});
+}
+__global__ __launch_bounds__(256) void attn_softmax_drop_kernel(const float* __restrict__ slabs, float* __restrict__ P,
+                                                                 float* __restrict__ PM, int hs, int HSP, int NS, float scale,
+                                                                 otp_attn_drop drop) {
+    attn_softmax_body<true>(slabs, P, PM, hs, HSP, NS, scale, drop);
 }
 
 // Phase 3: O^T[t, i] = sum_j v[j, t] P[i, j], stored as out[bh][t][i] (i contiguous) - exactly the memory
@@ -920,6 +939,37 @@ extern "C" int otp_chan_attn(const void* q, const void* k, const void* v, void* 
     launch_scores<otp_half_pieces>(static_cast<const float*>(q), static_cast<const float*>(k), slabs, BH, hs, T, NS, chunk, st);
     hipLaunchKernelGGL(attn_softmax_kernel, dim3(BH, otp_ceil_div(HSP, 4)), dim3(256), 0, st, slabs, P, hs, HSP, NS, scale);
     launch_apply<otp_half_pieces>(static_cast<const float*>(v), P, static_cast<float*>(out), BH, hs, T, st);
+    return otp_launch_status();
+}
+
+// the same with attention-probability dropout: the workspace holds one more matrix per (b, head), m P, behind P
+extern "C" size_t otp_chan_attn_dropout_workspace(int B, int C, int T, int n_head) {
+    const size_t base = otp_chan_attn_workspace(B, C, T, n_head);
+    if (!base) return 0;
+    const int hs = C / n_head, HSP = (hs + 15) & ~15;
+    return base + (size_t)B * n_head * HSP * HSP * sizeof(float);
+}
+
+extern "C" int otp_chan_attn_dropout(const void* q, const void* k, const void* v, void* out, void* workspace, size_t workspace_bytes,
+                                     int B, int C, int T, int n_head, float scale, float p, unsigned long long seed, void* stream) {
+    if (!q || !k || !v || !out || !workspace || B <= 0 || C <= 0 || T <= 0 || n_head <= 0 || !otp_attn_drop_rate_ok(p))
+        return OTP_ERR_BAD_ARG;
+    if (C % n_head) return OTP_ERR_BAD_ARG;
+    const otp_attn_drop drop = otp_attn_drop_make(p, seed);
+    if (!drop.thr) return otp_chan_attn(q, k, v, out, workspace, workspace_bytes, B, C, T, n_head, scale, stream);
+    const int hs = C / n_head, HSP = (hs + 15) & ~15;
+    if (HSP > 7 * 16) return OTP_ERR_UNSUPPORTED;
+    if (workspace_bytes < otp_chan_attn_dropout_workspace(B, C, T, n_head)) return OTP_ERR_WORKSPACE;
+    const int BH = B * n_head, NS = attn_splits(BH, T);
+    const int chunk = otp_ceil_div(otp_ceil_div(T, NS), ATT_TC) * ATT_TC;
+    auto st = static_cast<hipStream_t>(stream);
+    float* slabs = static_cast<float*>(workspace);
+    float* P = slabs + (size_t)BH * NS * HSP * HSP;
+    float* PM = P + (size_t)BH * HSP * HSP;
+    launch_scores<otp_half_pieces>(static_cast<const float*>(q), static_cast<const float*>(k), slabs, BH, hs, T, NS, chunk, st);
+    hipLaunchKernelGGL(attn_softmax_drop_kernel, dim3(BH, otp_ceil_div(HSP, 4)), dim3(256), 0, st, slabs, P, PM, hs, HSP, NS, scale,
+                       drop);
+    launch_apply<otp_half_pieces>(static_cast<const float*>(v), PM, static_cast<float*>(out), BH, hs, T, st);
     return otp_launch_status();
 }
 

@@ -448,22 +448,30 @@ __global__ void transpose_scale_kernel(const float* __restrict__ in, float* __re
     }
 }
 
-// dP = sum of the NS score slabs (padded HSP x HSP); dS = P o (dP - rowsum(dP o P)); also writes dS^T and P^T
-__global__ __launch_bounds__(64) void softmax_bwd_kernel(const float* __restrict__ slabs, const float* __restrict__ P,
-                                                          float* __restrict__ dS, float* __restrict__ dST,
-                                                          float* __restrict__ PT, int hs, int HSP, int NS) {
+// dP = sum of the NS score slabs (padded HSP x HSP); dS = P o (dP - rowsum(dP o P)); also writes dS^T and P^T.
+// With DROP (attention-probability dropout, csrc/common.h: otp_attn_drop, entry (g = bh, i = row, j = col) of (B nh, hs, hs)): dP is
+// multiplied by the mask m first and PT receives (m P)^T, the matrix dv is formed with.
+template <bool DROP>
+__device__ __forceinline__ void softmax_bwd_body(const float* __restrict__ slabs, const float* __restrict__ P,
+                                                 float* __restrict__ dS, float* __restrict__ dST,
+                                                 float* __restrict__ PT, int hs, int HSP, int NS, const otp_attn_drop& drop) {
     const int bh = blockIdx.x, row = blockIdx.y, lane = threadIdx.x;
     const float* sb = slabs + (size_t)bh * NS * HSP * HSP;
     const float* pb = P + (size_t)bh * HSP * HSP;
-    float dp[2], pv[2], acc = 0.f;
+    float dp[2], pv[2], mf[2], acc = 0.f;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int col = lane + 64 * h;
         dp[h] = 0.f;
         pv[h] = 0.f;
+        mf[h] = 1.f;
         if (row < hs && col < hs) {
             for (int s = 0; s < NS; ++s) dp[h] += sb[((size_t)s * HSP + row) * HSP + col];
             pv[h] = pb[row * HSP + col];
+            if (DROP) {
+                mf[h] = otp_attn_drop_at(drop, otp_attn_drop_row((uint64_t)bh * hs + row, hs), col);
+                dp[h] *= mf[h];
+            }
         }
         acc += dp[h] * pv[h];
     }
@@ -475,9 +483,19 @@ __global__ __launch_bounds__(64) void softmax_bwd_kernel(const float* __restrict
             const float v = (row < hs && col < hs) ? pv[h] * (dp[h] - acc) : 0.f;
             dS[((size_t)bh * HSP + row) * HSP + col] = v;
             dST[((size_t)bh * HSP + col) * HSP + row] = v;
-            PT[((size_t)bh * HSP + col) * HSP + row] = (row < hs && col < hs) ? pv[h] : 0.f;
+            PT[((size_t)bh * HSP + col) * HSP + row] = (row < hs && col < hs) ? (DROP ? pv[h] * mf[h] : pv[h]) : 0.f;
         }
     }
+}
+__global__ __launch_bounds__(64) void softmax_bwd_kernel(const float* __restrict__ slabs, const float* __restrict__ P,
+                                                          float* __restrict__ dS, float* __restrict__ dST,
+                                                          float* __restrict__ PT, int hs, int HSP, int NS) {
+    softmax_bwd_body<false>(slabs, P, dS, dST, PT, hs, HSP, NS, otp_attn_drop{});
+}
+__global__ __launch_bounds__(64) void softmax_bwd_drop_kernel(const float* __restrict__ slabs, const float* __restrict__ P,
+                                                               float* __restrict__ dS, float* __restrict__ dST,
+                                                               float* __restrict__ PT, int hs, int HSP, int NS, otp_attn_drop drop) {
+    softmax_bwd_body<true>(slabs, P, dS, dST, PT, hs, HSP, NS, drop);
 }
 
 }  // namespace
@@ -580,6 +598,19 @@ extern "C" int otp_softmax_backward(const void* slabs, const void* P, void* dS, 
     hipLaunchKernelGGL(softmax_bwd_kernel, dim3(BH, HSP), dim3(64), 0, static_cast<hipStream_t>(stream),
                        static_cast<const float*>(slabs), static_cast<const float*>(P), static_cast<float*>(dS),
                        static_cast<float*>(dST), static_cast<float*>(PT), hs, HSP, NS);
+    return otp_launch_status();
+}
+
+extern "C" int otp_softmax_backward_dropout(const void* slabs, const void* P, void* dS, void* dST, void* PT, int BH, int hs, int NS,
+                                            float p, unsigned long long seed, void* stream) {
+    if (!slabs || !P || !dS || !dST || !PT || BH <= 0 || hs <= 0 || NS <= 0 || !otp_attn_drop_rate_ok(p)) return OTP_ERR_BAD_ARG;
+    const otp_attn_drop drop = otp_attn_drop_make(p, seed);
+    if (!drop.thr) return otp_softmax_backward(slabs, P, dS, dST, PT, BH, hs, NS, stream);
+    const int HSP = (hs + 15) & ~15;
+    if (HSP > 128) return OTP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(softmax_bwd_drop_kernel, dim3(BH, HSP), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const float*>(slabs), static_cast<const float*>(P), static_cast<float*>(dS),
+                       static_cast<float*>(dST), static_cast<float*>(PT), hs, HSP, NS, drop);
     return otp_launch_status();
 }
 

@@ -143,14 +143,28 @@ class OTPose(nn.Module):
         # encoders with arch[0] = 0): MODEL.EMBD_LAYERS for the two temporal encoders, MODEL.FLOW_EMBD_LAYERS for the flow encoder,
         # MODEL.EMBD_KS / MODEL.EMBD_WITH_LN for all three
         ekw = self._embd_keys(get, d)
+        # extension keys, training only (the inference engines read none of them: eval is the identity): attention-probability
+        # dropout, which the reference's blocks take as attn_pdrop (blocks.py:392,572) and its OTPose.py:209-216 leaves at 0 -
+        # MODEL.ATTN_PDROP for the two temporal encoders, MODEL.FLOW_ATTN_PDROP for the flow encoder, MODEL.TOKEN_ATTN_DROPOUT
+        # for the token encoders (what OTPose.py:93 hands to nn.MultiheadAttention); all 0.0 by default
+        pdrop, flow_pdrop, token_pdrop = (self._rate_key(get, k) for k in ("ATTN_PDROP", "FLOW_ATTN_PDROP", "TOKEN_ATTN_DROPOUT"))
+        # the training graph passes a rate to the channel attention only (TrainGraph.attention): a windowed encoder with one could
+        # not take its first training step, so the pair of keys is refused here, by name
+        for key, rate, wkey, windows in (("ATTN_PDROP", pdrop, "MHA_WIN_SIZE", win), ("FLOW_ATTN_PDROP", flow_pdrop, "FLOW_MHA_WIN_SIZE", fwin)):
+            if rate > 0.0 and windows is not None:
+                raise ValueError(f"MODEL.{key} = {rate} with MODEL.{wkey} = {windows}: the training graph does not drop the "
+                                 "probabilities of the local-window attention (train_ops.local_attn takes dropout_p; "
+                                 "TrainGraph.attention does not pass it)")
         if ekw:
             self.scale_arch = (ekw.pop("layers"),) + self.scale_arch[1:]
             self.flow_scale_arch = (ekw.pop("flow_layers"),) + self.flow_scale_arch[1:]
             tkw.update(ekw)
-        self.temporal_encoder1 = ConvTransformer(d, d, n_head=2, arch=self.scale_arch, **tkw, **self._local_kw(win, rel))
-        self.temporal_encoder2 = ConvTransformer(d, d, n_head=2, arch=self.scale_arch, **tkw, **self._local_kw(win, rel))
-        self.flow_encoder = ConvTransformer(self.patch_dim, self.patch_dim, n_head=1,
-                                            arch=self.flow_scale_arch, **tkw, **self._local_kw(fwin, False))
+        self.temporal_encoder1 = ConvTransformer(d, d, n_head=2, arch=self.scale_arch, attn_pdrop=pdrop, **tkw,
+                                                 **self._local_kw(win, rel))
+        self.temporal_encoder2 = ConvTransformer(d, d, n_head=2, arch=self.scale_arch, attn_pdrop=pdrop, **tkw,
+                                                 **self._local_kw(win, rel))
+        self.flow_encoder = ConvTransformer(self.patch_dim, self.patch_dim, n_head=1, arch=self.flow_scale_arch,
+                                            attn_pdrop=flow_pdrop, **tkw, **self._local_kw(fwin, False))
 
         # extension keys: a DETR-style TransformerEncoder (OTPose.py:26-159, exported and never called by the reference) over the
         # h w heat-map tokens in front of each ConvTransformer, on exactly the tensor the ConvTransformer is handed; all off by
@@ -162,7 +176,7 @@ class OTPose(nn.Module):
                                                 ("flow_token_encoder", self.patch_dim, tk["flow_layers"], 1, tk["flow_ffn"])):
             if layers > 0:
                 layer = TransformerEncoderLayer(width, heads, ffn, dropout=0.1, activation="gelu", normalize_before=tk["pre_norm"])
-                setattr(self, name, TransformerEncoder(layer, layers))
+                setattr(self, name, TransformerEncoder(layer.set_attn_dropout(token_pdrop), layers))
         pe, flow_pe = tk["pe"], tk["pe"]
         if flow_pe == "sine" and tk["flow_layers"] > 0:
             flow_pe = "none"                   # width 17 has no sine table (d_model % 4), in the reference either
@@ -226,6 +240,12 @@ class OTPose(nn.Module):
                 check_local_length(t if self.num_patches % 2 ** i == 0 else 0, s,
                                    f"{key}[{i}]: level {i} of the {self.pe_w}x{self.pe_h} heat-map: sequence length")
         return sizes
+
+    @staticmethod
+    def _rate_key(get, key):
+        """``MODEL.<key>`` validated as a dropout rate: a float in [0, 1), 0.0 where absent."""
+        from .attn_dropout import check_rate
+        return check_rate(get(key, 0.0), f"MODEL.{key}")
 
     PRM_CHAINS = ("def_fuse", "offset_mask_combine_conv")
 

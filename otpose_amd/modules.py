@@ -503,10 +503,12 @@ class TransformerEncoderLayer(nn.Module):
     ``token_attn`` (csrc/tokattn.hip).  Residual adds, the ``pos`` add, ReLU and dropout are PyTorch element-wise operators.
 
     Deviations, each raising: a dense ``src_mask`` -> ``NotImplementedError``; ``activation`` is ``relu`` or ``gelu`` (``glu``
-    halves the width in the reference and then fails in ``linear2``) -> ``ValueError``; attention-probability dropout is not
-    built: ``dropout`` acts at the reference's three ``nn.Dropout`` places only, and the separate ``attn_dropout`` must be 0
-    (the reference hands ``dropout`` to ``nn.MultiheadAttention`` as well).  With ``return_atten_map`` the map comes from
-    ``token_attn_map`` and carries no gradient."""
+    halves the width in the reference and then fails in ``linear2``) -> ``ValueError``.  ``dropout`` acts at the reference's three
+    ``nn.Dropout`` places only, and the constructor argument ``attn_dropout`` must stay 0 (``ValueError``; the reference hands
+    ``dropout`` to ``nn.MultiheadAttention`` as well).  Attention-probability dropout is switched on for a built layer with
+    :meth:`set_attn_dropout` (what ``OTPose`` does for ``MODEL.TOKEN_ATTN_DROPOUT``): it is applied inside ``token_attn`` when the
+    layer runs stochastically, with this library's own counter-based mask (otpose_amd/attn_dropout.py), not PyTorch's.
+    With ``return_atten_map`` the map comes from ``token_attn_map``: no gradient, and the undropped probabilities."""
 
     def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1, activation="gelu", normalize_before=False,
                  return_atten_map=False, attn_dropout=0.0):
@@ -521,7 +523,9 @@ class TransformerEncoderLayer(nn.Module):
         if activation not in ("relu", "gelu"):
             raise ValueError(f"TransformerEncoderLayer: activation must be 'relu' or 'gelu', got {activation!r}")
         if attn_dropout != 0.0:
-            raise ValueError("TransformerEncoderLayer: attention-probability dropout is not built, attn_dropout must be 0")
+            raise ValueError("TransformerEncoderLayer: attn_dropout must be 0 at construction; attention-probability dropout is "
+                             "set on a built layer with set_attn_dropout(p)")
+        self.attn_dropout = 0.0
         self.self_attn = _SelfAttnParams(d_model)
         self.linear1 = nn.Linear(d_model, dim_feedforward)
         self.linear2 = nn.Linear(dim_feedforward, d_model)
@@ -529,6 +533,12 @@ class TransformerEncoderLayer(nn.Module):
         self.norm2 = nn.LayerNorm(d_model)
         self.d_model, self.nhead, self.p_drop, self.activation = d_model, nhead, float(dropout), activation
         self.normalize_before, self.return_atten_map = normalize_before, return_atten_map
+
+    def set_attn_dropout(self, p):
+        """Attention-probability dropout rate of this layer, a float in [0, 1) (``ValueError`` otherwise); returns the layer."""
+        from .attn_dropout import check_rate
+        self.attn_dropout = check_rate(p, "TransformerEncoderLayer: attn_dropout")
+        return self
 
     def _drop(self, x):
         return torch.nn.functional.dropout(x, self.p_drop, True) if self._stochastic and self.p_drop > 0 else x
@@ -546,7 +556,8 @@ class TransformerEncoderLayer(nn.Module):
         k = _pointwise(qk, w[e:2 * e], b[e:2 * e])
         v = _pointwise(value, w[2 * e:], b[2 * e:])
         scale = 1.0 / math.sqrt(e // self.nhead)
-        out = _pointwise(token_attn(q, k, v, self.nhead, scale, mask), a.out_proj.weight, a.out_proj.bias)
+        p_attn = self.attn_dropout if self._stochastic else 0.0
+        out = _pointwise(token_attn(q, k, v, self.nhead, scale, mask, dropout_p=p_attn), a.out_proj.weight, a.out_proj.bias)
         amap = token_attn_map(q.detach(), k.detach(), self.nhead, scale, mask) if self.return_atten_map else None
         return out, amap
 

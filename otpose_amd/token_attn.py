@@ -7,7 +7,9 @@ Operands are the library's own layout: ``q, k, v`` fp32 ``(B, C, T)``, contiguou
     S[i][j] = scale * sum_c q[c][i] k[c][j],   P = softmax_j(S),   O[c][i] = sum_j P[i][j] v[c][j]
 
 ``key_padding_mask`` is ``(B, T)`` bool, True = this key is padding, as in PyTorch.  A sample whose keys are all padding is
-outside the contract (PyTorch returns NaN rows there; this kernel divides by zero).  Supported: ``C % n_head == 0`` and a head
+outside the contract (PyTorch returns NaN rows there; this kernel divides by zero).  ``dropout_p`` > 0 drops attention
+probabilities inside the kernels (the mask of otpose_amd/attn_dropout.py: the softmax statistics stay undropped, only the operand
+of the P v product is masked and scaled by 1 / (1 - p)); the backward re-evaluates the same mask from the seed.  Supported: ``C % n_head == 0`` and a head
 width of at most 136; everything else raises ``ValueError`` before any launch.  CPU tensors raise ``NotImplementedError``,
 like every operator here.
 """
@@ -18,7 +20,7 @@ import math
 import torch
 from torch.autograd import Function
 
-from . import hip
+from . import attn_dropout, hip
 from .ops import require_gpu
 
 __all__ = ["token_attn", "token_attn_map", "sine_position_embedding", "check_token_attn", "MAX_HEAD_WIDTH"]
@@ -63,10 +65,15 @@ def _check(q, k, v, n_head, key_padding_mask):
     return b, c, t, mask
 
 
-def _forward(q, k, v, mask, n_head, scale, want_lse):
+def _forward(q, k, v, mask, n_head, scale, want_lse, p=0.0, seed=0):
     b, c, t = q.shape
     out = torch.empty_like(q)
     lse = torch.empty((b, n_head, t), dtype=torch.float32, device=q.device) if want_lse else None
+    if p > 0.0:
+        hip.check(hip.lib().otp_token_attn_forward_dropout(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(mask), hip.ptr(out),
+                                                           hip.ptr(lse), b, c, n_head, t, scale, p, seed, hip.stream_of(q)),
+                  "otp_token_attn_forward_dropout")
+        return out, lse
     hip.check(hip.lib().otp_token_attn_forward(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(mask), hip.ptr(out), hip.ptr(lse),
                                                b, c, n_head, t, scale, hip.stream_of(q)), "otp_token_attn_forward")
     return out, lse
@@ -74,13 +81,14 @@ def _forward(q, k, v, mask, n_head, scale, want_lse):
 
 class TokenAttnFunction(Function):
     """``token_attn`` with a backward: the forward keeps q, k, v, the output and the row log-sum-exp (B, n_head, T); the backward
-    is ``otp_token_attn_backward`` (pass A: D and dq per query tile, pass B: dk and dv per key tile; deterministic, no atomics)."""
+    is ``otp_token_attn_backward`` (pass A: D and dq per query tile, pass B: dk and dv per key tile; deterministic, no atomics).
+    With ``p`` > 0 both directions run the ``_dropout`` entry points under the same ``seed``: no mask is stored."""
 
     @staticmethod
-    def forward(ctx, q, k, v, mask, n_head, scale):
-        out, lse = _forward(q, k, v, mask, n_head, scale, True)
+    def forward(ctx, q, k, v, mask, n_head, scale, p=0.0, seed=0):
+        out, lse = _forward(q, k, v, mask, n_head, scale, True, p, seed)
         ctx.save_for_backward(q, k, v, out, lse)
-        ctx.mask, ctx.cfg = mask, (n_head, scale)
+        ctx.mask, ctx.cfg, ctx.drop = mask, (n_head, scale), (p, seed)
         return out
 
     @staticmethod
@@ -92,27 +100,44 @@ class TokenAttnFunction(Function):
         gout = gout.contiguous()
         gq, gk, gv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
         ws = torch.empty(L.otp_token_attn_workspace(b, n_head, t, c // n_head) // 4, dtype=torch.float32, device=q.device)
+        p, seed = ctx.drop
+        if p > 0.0:
+            hip.check(L.otp_token_attn_backward_dropout(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(ctx.mask), hip.ptr(out),
+                                                        hip.ptr(lse), hip.ptr(gout), hip.ptr(gq), hip.ptr(gk), hip.ptr(gv),
+                                                        hip.ptr(ws), b, c, n_head, t, scale, p, seed, hip.stream_of(q)),
+                      "otp_token_attn_backward_dropout")
+            return gq, gk, gv, None, None, None, None, None
         hip.check(L.otp_token_attn_backward(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(ctx.mask), hip.ptr(out), hip.ptr(lse),
                                             hip.ptr(gout), hip.ptr(gq), hip.ptr(gk), hip.ptr(gv), hip.ptr(ws), b, c, n_head, t,
                                             scale, hip.stream_of(q)), "otp_token_attn_backward")
-        return gq, gk, gv, None, None, None
+        return gq, gk, gv, None, None, None, None, None
 
 
-def token_attn(q, k, v, n_head, scale, key_padding_mask=None):
+def token_attn(q, k, v, n_head, scale, key_padding_mask=None, dropout_p=0.0, seed=None):
     """softmax(scale q^T k) v per head, ``(B, C, T)`` in and out.  Under ``torch.no_grad()`` or with no operand requiring a
-    gradient: one forward launch that stores no log-sum-exp; otherwise an autograd Function."""
+    gradient: one forward launch that stores no log-sum-exp; otherwise an autograd Function.
+
+    ``dropout_p`` in [0, 1) (``ValueError`` otherwise) drops attention probabilities: every P[i][j] is zeroed with probability
+    ``dropout_p`` and the survivors are scaled by 1 / (1 - dropout_p) in front of the P v product, as ``nn.MultiheadAttention``
+    does in training.  ``seed`` (an int below 2^64) fixes the mask; None draws one per call from PyTorch's CUDA generator, so
+    ``torch.manual_seed`` makes it repeat.  A rate whose 16-bit threshold is 0 (below 2^-17) is the call without dropout,
+    bit for bit, and draws nothing.  Under ``no_grad`` the dropout still applies: forward only."""
+    p = attn_dropout.check_rate(dropout_p, "token_attn: dropout_p")
     _, _, _, mask = _check(q, k, v, n_head, key_padding_mask)
     scale = float(scale)
+    p, seed = attn_dropout.seed_of(p, seed, q.device)
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        return TokenAttnFunction.apply(q, k, v, mask, n_head, scale)
-    return _forward(q, k, v, mask, n_head, scale, False)[0]
+        return TokenAttnFunction.apply(q, k, v, mask, n_head, scale, p, seed)
+    return _forward(q, k, v, mask, n_head, scale, False, p, seed)[0]
 
 
 def token_attn_map(q, k, n_head, scale, key_padding_mask=None):
     """``(B, T, T)``: the mean over heads of P, what ``nn.MultiheadAttention`` returns as its second value.  Two launches: a
     forward for the row log-sum-exp (its output is dropped), then one pass that recomputes ``exp(S - lse)``.
 
-    The map carries NO gradient (a documented deviation: in PyTorch the averaged weights are differentiable)."""
+    The map carries NO gradient (a documented deviation: in PyTorch the averaged weights are differentiable), and it is the
+    map of the UNDROPPED probabilities (a second deviation: in training ``nn.MultiheadAttention`` returns the weights after its
+    dropout; ``token_attn``'s ``dropout_p`` does not reach this function)."""
     b, c, t, mask = _check(q, k, None, n_head, key_padding_mask)
     scale = float(scale)
     q, k = q.detach(), k.detach()

@@ -374,14 +374,17 @@ class TrainGraph:
 
     def attention(self, p, q, k, v, n_head, scale):
         """The attention product of module ``p``: the local window of a LocalMaskedMHCA (blocks.py:655-833), else the channel
-        attention (blocks.py:427-447).  No dropout on the attention map: attn_pdrop is 0 in OTPose.py:209-216."""
+        attention (blocks.py:427-447).  The channel attention honours the module's ``attn_pdrop`` (blocks.py:392; 0 in
+        OTPose.py:209-216, the extension keys MODEL.ATTN_PDROP / FLOW_ATTN_PDROP set it) inside its kernels when the graph is
+        stochastic.  A window with ``attn_pdrop`` > 0 still raises: ``train_ops.local_attn`` takes ``dropout_p``, the graph does
+        not pass it yet."""
         a = self.mods[p]
         window = getattr(a, "window_size", 0)
         if window > 1:
             if self.stochastic and a.attn_pdrop > 0.0:
                 raise NotImplementedError(f"{p}: attn_pdrop = {a.attn_pdrop} > 0 is not implemented in the training graph")
             return T.local_attn(q, k, v, n_head, window, scale, self.P.get(p + ".rel_pe"))
-        return T.chan_attn(q, k, v, n_head, scale)
+        return T.chan_attn(q, k, v, n_head, scale, dropout_p=a.attn_pdrop if self.stochastic else 0.0)
 
     def dropout(self, x, rate):
         if self.stochastic and rate > 0.0:

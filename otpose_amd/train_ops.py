@@ -15,7 +15,7 @@ import os
 import torch
 from torch.autograd import Function
 
-from . import hip, ops
+from . import attn_dropout, hip, ops
 from .ops import (ACT_NONE, View, check_f32, out_hw, require_gpu, conv2d_launch, conv2d_wino_launch, conv_desc,
                   pack_conv_weight, pack_wino_weight)
 
@@ -532,22 +532,28 @@ class ChanAttnFunction(Function):
     P = softmax(S), O = P v, returned in the ``transpose(2,3).contiguous().view(B, C, T)`` memory image."""
 
     @staticmethod
-    def forward(ctx, q, k, v, n_head, scale):
+    def forward(ctx, q, k, v, n_head, scale, p=0.0, seed=0):
         require_gpu(q, k, v)
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         b, c, t = q.shape
         L = hip.lib()
-        nbytes = L.otp_chan_attn_workspace(b, c, t, n_head)
-        ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=q.device)
         out = torch.empty_like(q)
-        hip.check(L.otp_chan_attn(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(out), hip.ptr(ws), nbytes, b, c, t, n_head,
-                                  scale, hip.stream_of(q)), "otp_chan_attn")
+        if p > 0.0:                                            # m P goes to a third region of the workspace, P stays undropped
+            nbytes = L.otp_chan_attn_dropout_workspace(b, c, t, n_head)
+            ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=q.device)
+            hip.check(L.otp_chan_attn_dropout(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(out), hip.ptr(ws), nbytes, b, c, t,
+                                              n_head, scale, p, seed, hip.stream_of(q)), "otp_chan_attn_dropout")
+        else:
+            nbytes = L.otp_chan_attn_workspace(b, c, t, n_head)
+            ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=q.device)
+            hip.check(L.otp_chan_attn(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(out), hip.ptr(ws), nbytes, b, c, t, n_head,
+                                      scale, hip.stream_of(q)), "otp_chan_attn")
         bh, hs = b * n_head, c // n_head
         hsp = (hs + 15) // 16 * 16
         ns = L.otp_chan_attn_splits(bh, t)
-        p = ws[bh * ns * hsp * hsp: bh * ns * hsp * hsp + bh * hsp * hsp].clone()     # softmax matrix, zero padded
-        ctx.save_for_backward(q, k, v, p)
-        ctx.cfg = (n_head, scale)
+        probs = ws[bh * ns * hsp * hsp: bh * ns * hsp * hsp + bh * hsp * hsp].clone()    # softmax matrix (undropped), zero padded
+        ctx.save_for_backward(q, k, v, probs)
+        ctx.cfg, ctx.drop = (n_head, scale), (p, seed)
         return out
 
     @staticmethod
@@ -569,8 +575,13 @@ class ChanAttnFunction(Function):
         # (every product of the backward has a gradient operand: bfloat16 pieces - otp_bf16_pieces in csrc/transformer.hip)
         hip.check(L.otp_chan_attn_scores_bf16p(hip.ptr(d_o), hip.ptr(v), hip.ptr(slabs), bh, hs, t, st), "otp_chan_attn_scores_bf16p")
         d_s, d_st, p_t = new(bh, hsp, hsp), new(bh, hsp, hsp), new(bh, hsp, hsp)
-        hip.check(L.otp_softmax_backward(hip.ptr(slabs), hip.ptr(p), hip.ptr(d_s), hip.ptr(d_st), hip.ptr(p_t), bh, hs, ns,
-                                         st), "otp_softmax_backward")
+        drop_p, seed = ctx.drop
+        if drop_p > 0.0:
+            hip.check(L.otp_softmax_backward_dropout(hip.ptr(slabs), hip.ptr(p), hip.ptr(d_s), hip.ptr(d_st), hip.ptr(p_t), bh, hs,
+                                                     ns, drop_p, seed, st), "otp_softmax_backward_dropout")
+        else:
+            hip.check(L.otp_softmax_backward(hip.ptr(slabs), hip.ptr(p), hip.ptr(d_s), hip.ptr(d_st), hip.ptr(p_t), bh, hs, ns,
+                                             st), "otp_softmax_backward")
         tmp = new(bh, t, hs)
         grads = []
         for src, mat, sc in ((k, d_s, scale), (q, d_st, scale), (d_o, p_t, 1.0)):
@@ -578,11 +589,14 @@ class ChanAttnFunction(Function):
             g = new(b, c, t)
             hip.check(L.otp_transpose_scale(hip.ptr(tmp), hip.ptr(g), bh, t, hs, sc, st), "otp_transpose_scale")
             grads.append(g)
-        return grads[0], grads[1], grads[2], None, None
+        return grads[0], grads[1], grads[2], None, None, None, None
 
 
-def chan_attn(q, k, v, n_head, scale):
-    return ChanAttnFunction.apply(q, k, v, n_head, scale)
+def chan_attn(q, k, v, n_head, scale, dropout_p=0.0, seed=None):
+    """``dropout_p`` in [0, 1): attention-probability dropout on the hs x hs matrix between the softmax and the apply step
+    (blocks.py:392; the mask of otpose_amd/attn_dropout.py, ``seed`` None = one draw from the CUDA generator per call)."""
+    p, seed = attn_dropout.resolve(dropout_p, seed, q.device, "chan_attn: dropout_p")
+    return ChanAttnFunction.apply(q, k, v, n_head, scale, p, seed)
 
 
 class LocalAttnFunction(Function):
@@ -591,7 +605,7 @@ class LocalAttnFunction(Function):
     fixed-order fold for ``rel_pe``: deterministic, no atomics)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, rel_pe, n_head, window_size, scale):
+    def forward(ctx, q, k, v, rel_pe, n_head, window_size, scale, p=0.0, seed=0):
         require_gpu(q, k, v)
         check_f32(q, k, v)
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
@@ -600,10 +614,13 @@ class LocalAttnFunction(Function):
         rel = ops.rel_pe_table(rel_pe, n_head, window_size, q)
         out = torch.empty_like(q)
         probs = torch.empty((b * n_head, t, window_size), dtype=torch.float32, device=q.device)
-        hip.check(hip.lib().otp_local_attn(*ops.local_attn_args(q, k, v, rel, out, probs, n_head, window_size, scale),
-                                           hip.stream_of(q)), "otp_local_attn")
+        args = ops.local_attn_args(q, k, v, rel, out, probs, n_head, window_size, scale)
+        if p > 0.0:                                            # probs keeps the undropped band
+            hip.check(hip.lib().otp_local_attn_dropout(*args, p, seed, hip.stream_of(q)), "otp_local_attn_dropout")
+        else:
+            hip.check(hip.lib().otp_local_attn(*args, hip.stream_of(q)), "otp_local_attn")
         ctx.save_for_backward(q, k, v, probs)
-        ctx.cfg = (n_head, int(window_size), scale)
+        ctx.cfg, ctx.drop = (n_head, int(window_size), scale), (p, seed)
         ctx.params = (rel_pe,)
         return out
 
@@ -622,14 +639,24 @@ class LocalAttnFunction(Function):
             grel = slot if slot is not None else torch.empty(rel_pe.shape, dtype=torch.float32, device=q.device)
         nbytes = L.otp_local_attn_backward_workspace(b, c, t, n_head, window)
         ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
-        hip.check(L.otp_local_attn_backward(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(probs), hip.ptr(gout), hip.ptr(gq),
-                                            hip.ptr(gk), hip.ptr(gv), hip.ptr(grel), hip.ptr(ws), nbytes, b, c, t, n_head, window,
-                                            scale, hip.stream_of(q)), "otp_local_attn_backward")
-        return gq, gk, gv, grel, None, None, None
+        p, seed = ctx.drop
+        if p > 0.0:
+            hip.check(L.otp_local_attn_backward_dropout(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(probs), hip.ptr(gout),
+                                                        hip.ptr(gq), hip.ptr(gk), hip.ptr(gv), hip.ptr(grel), hip.ptr(ws), nbytes,
+                                                        b, c, t, n_head, window, scale, p, seed, hip.stream_of(q)),
+                      "otp_local_attn_backward_dropout")
+        else:
+            hip.check(L.otp_local_attn_backward(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(probs), hip.ptr(gout), hip.ptr(gq),
+                                                hip.ptr(gk), hip.ptr(gv), hip.ptr(grel), hip.ptr(ws), nbytes, b, c, t, n_head,
+                                                window, scale, hip.stream_of(q)), "otp_local_attn_backward")
+        return gq, gk, gv, grel, None, None, None, None, None
 
 
-def local_attn(q, k, v, n_head, window_size, scale, rel_pe=None):
-    return LocalAttnFunction.apply(q, k, v, rel_pe, n_head, window_size, scale)
+def local_attn(q, k, v, n_head, window_size, scale, rel_pe=None, dropout_p=0.0, seed=None):
+    """``dropout_p`` in [0, 1): attention-probability dropout on the band (blocks.py:572; the mask of otpose_amd/attn_dropout.py,
+    ``seed`` None = one draw from the CUDA generator per call)."""
+    p, seed = attn_dropout.resolve(dropout_p, seed, q.device, "local_attn: dropout_p")
+    return LocalAttnFunction.apply(q, k, v, rel_pe, n_head, window_size, scale, p, seed)
 
 
 CONV_EMBD_TRAIN_KS = (1, 3)           # the kernel sizes conv2d_grad_weight (otp_conv2d_wgrad) takes

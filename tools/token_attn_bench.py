@@ -3,7 +3,10 @@
 algorithmic TFLOP/s that gives and its share of the fp32-matrix peak, beside ``torch.nn.functional.scaled_dot_product_attention``
 on the same operands.
 
-    python tools/token_attn_bench.py [--iters 10] [--warmup 3] [--out profiles/token_attn_bench.txt]
+    python tools/token_attn_bench.py [--iters 10] [--warmup 3] [--dropout P] [--out profiles/token_attn_bench.txt]
+
+``--dropout P`` (0 < P < 1) adds, per shape, the times of the ``_dropout`` entry points at rate P beside the p = 0 times of the
+same run: what the in-kernel mask (8 hashes per lane and key tile forward and in backward pass A, 16 in pass B) costs.
 
 Shapes: (16, 136, 6912) with 2 heads (head width 68) and with 8 heads (head width 17).  Times are device events around ``iters``
 back-to-back calls after ``warmup`` calls of the same shape, best of three such windows.  FLOP are counted from the shapes:
@@ -50,8 +53,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dropout", type=float, default=0.0, help="also time the dropout entry points at this rate")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if not 0.0 <= a.dropout < 1.0:
+        raise SystemExit("--dropout takes a rate in [0, 1)")
     if not torch.cuda.is_available():
         raise SystemExit("token_attn_bench needs the GPU: a CPU run gives no time")
     dev = torch.device("cuda")
@@ -79,6 +85,19 @@ def main():
                                                 t, scale, st), "otp_token_attn_backward")
         t_fwd, t_both = timed(fwd, a.iters, a.warmup), timed(both, a.iters, a.warmup)
 
+        seed = 0x123456789ABCDEF
+
+        def fwd_drop(keep_lse=False):
+            hip.check(L.otp_token_attn_forward_dropout(P(q), P(k), P(v), None, P(out), P(lse) if keep_lse else None, b, c, nh, t,
+                                                       scale, a.dropout, seed, st), "otp_token_attn_forward_dropout")
+
+        def both_drop():
+            fwd_drop(True)
+            hip.check(L.otp_token_attn_backward_dropout(P(q), P(k), P(v), None, P(out), P(lse), P(go), P(gq), P(gk), P(gv), P(ws),
+                                                        b, c, nh, t, scale, a.dropout, seed, st), "otp_token_attn_backward_dropout")
+        if a.dropout > 0.0:
+            d_fwd, d_both = timed(fwd_drop, a.iters, a.warmup), timed(both_drop, a.iters, a.warmup)
+
         # the baseline in its own layout (B, heads, T, hd)
         sq, sk, sv, sgo = (x.view(b, nh, c // nh, t).transpose(2, 3).contiguous() for x in (q, k, v, go))
         e_it = max(2, a.iters // 3)
@@ -99,6 +118,9 @@ def main():
         lines.append("%-18s %8.2f %7.1f %5.1f%% | %9.2f %7.1f %5.1f%% | %9.2f %11.2f | %9.1e" % (
             f"{b},{c},{nh},{t}", t_fwd, f_fwd / t_fwd / 1e9, 100 * f_fwd / t_fwd / 1e-3 / PEAK, t_both, f_both / t_both / 1e9,
             100 * f_both / t_both / 1e-3 / PEAK, s_fwd, s_both, diff))
+        if a.dropout > 0.0:
+            lines.append("%-18s %8.2f %7s %5.2fx | %9.2f %7s %5.2fx | dropout p = %g against the p = 0 row above" % (
+                "", d_fwd, "", d_fwd / t_fwd, d_both, "", d_both / t_both, a.dropout))
         del leaves, sq, sk, sv, sgo, ref
         torch.cuda.empty_cache()
     lines.append("FLOP: forward 4 B T^2 C, forward + backward 14 B T^2 C; peak %.1f TFLOP/s (fp32 matrix)" % (PEAK / 1e12))

@@ -694,7 +694,7 @@ int otp_chan_attn_set_split(int on);
 int otp_chan_attn_splits(int BH, int T);
 int otp_chan_attn_scores(const void* a, const void* b, void* slabs, int BH, int hs, int T, void* stream);
 int otp_chan_attn_apply(const void* v, const void* M, void* out, int BH, int hs, int T, void* stream);
-/* The two products with bfloat16 operand pieces (csrc/transformer.hip on otp_bf16_pieces) for the attention backward, whose operands are
+/* The two products with bfloat16 operand pieces (csrc/chanattn.hip on otp_bf16_pieces) for the attention backward, whose operands are
  * gradients (dS = dO v^T; dq, dk, dv): same arguments, same otp_chan_attn_set_split switch. */
 int otp_chan_attn_scores_bf16p(const void* a, const void* b, void* slabs, int BH, int hs, int T, void* stream);
 int otp_chan_attn_apply_bf16p(const void* v, const void* M, void* out, int BH, int hs, int T, void* stream);

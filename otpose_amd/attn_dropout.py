@@ -1,5 +1,5 @@
 """Attention-probability dropout of the three attentions (token: csrc/tokattn.hip, local window: csrc/localattn.hip, channel:
-csrc/transformer.hip): what the callers share, and the mask as a tensor for tests and debugging.
+csrc/chanattn.hip): what the callers share, and the mask as a tensor for tests and debugging.
 
 The mask is a counter-based function of (seed, group, row, column, p) - include/otpose_hip.h states it ("attention dropout mask")
 - that the forward and the backward kernels evaluate in place; no mask tensor exists on the training path.  The 64-bit seed of a

@@ -172,7 +172,7 @@ __device__ __forceinline__ float bload(otp_rsrc r, int voff_bytes, int soff_byte
 // bf16 one and takes SUBNORMAL f16 inputs exactly (tools/micro/mfma_f16_denorm.hip), which the small `lo` pieces need.  Range:
 // operands above 65504 become infinities (BatchNorm-folded weights and heat-map activations are orders of magnitude below).
 // The piece type is a traits parameter of the kernels that exist for both (csrc/densex.hip, the attention products of
-// csrc/transformer.hip: bfloat16 pieces for the GRADIENT operands of the training backward); every other file uses the half
+// csrc/chanattn.hip: bfloat16 pieces for the GRADIENT operands of the training backward); every other file uses the half
 // aliases below.
 struct otp_half_pieces {
     typedef _Float16 elem;

@@ -1,7 +1,8 @@
-// Backward kernels of the ConvTransformer pieces (training step; forward counterparts in transformer.hip):
-// channel LayerNorm, depthwise k=3 conv (forward + both gradients), exact-erf GELU, MaxPool1d(3,2,1), linear
-// up-sampling, and the helpers the channel-attention backward is assembled from (layout transpose, slab sum,
-// softmax backward).  Reference: model/blocks.py:95-110, 234-254, 359-381, 400-453; ConvVideoTransformer.py:108.
+// Backward kernels of the ConvTransformer encoder's passes (training step; forward counterparts in transformer.hip):
+// channel LayerNorm, MaxPool1d(3,2,1), linear up-sampling, and the two forward / backward pairs the training step
+// has no other home for: depthwise k=3 conv (forward + both gradients) and exact-erf GELU.  The helpers of the
+// channel-attention backward are in csrc/chanattn.hip.
+// Reference: model/blocks.py:95-110, 234-254, 359-381, 400-415; ConvVideoTransformer.py:108.
 // All tensors (B, C, T) fp32 with T contiguous; a thread owns one time step, so wave accesses are 256-byte rows.
 #include "common.h"
 
@@ -430,74 +431,6 @@ __global__ void upsample_linear_bwd_kernel(const float* __restrict__ dy, float* 
     dx[((size_t)b * C + c) * T + i] = s;
 }
 
-// ---- attention backward helpers ------------------------------------------------------------------------
-// per (b, head): in (R, Cc) row-major -> out (Cc, R) row-major, scaled (the O <-> out.transpose(2,3).contiguous() image)
-__global__ void transpose_scale_kernel(const float* __restrict__ in, float* __restrict__ out, int R, int Cc, float scale) {
-    __shared__ float tile[32][33];
-    const float* ib = in + (size_t)blockIdx.z * R * Cc;
-    float* ob = out + (size_t)blockIdx.z * R * Cc;
-    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-    for (int j = threadIdx.y; j < 32; j += 8) {
-        const int r = r0 + j, c = c0 + threadIdx.x;
-        tile[j][threadIdx.x] = (r < R && c < Cc) ? ib[(size_t)r * Cc + c] : 0.f;
-    }
-    __syncthreads();
-    for (int j = threadIdx.y; j < 32; j += 8) {
-        const int c = c0 + j, r = r0 + threadIdx.x;
-        if (c < Cc && r < R) ob[(size_t)c * R + r] = tile[threadIdx.x][j] * scale;
-    }
-}
-
-// dP = sum of the NS score slabs (padded HSP x HSP); dS = P o (dP - rowsum(dP o P)); also writes dS^T and P^T.
-// With DROP (attention-probability dropout, csrc/common.h: otp_attn_drop, entry (g = bh, i = row, j = col) of (B nh, hs, hs)): dP is
-// multiplied by the mask m first and PT receives (m P)^T, the matrix dv is formed with.
-template <bool DROP>
-__device__ __forceinline__ void softmax_bwd_body(const float* __restrict__ slabs, const float* __restrict__ P,
-                                                 float* __restrict__ dS, float* __restrict__ dST,
-                                                 float* __restrict__ PT, int hs, int HSP, int NS, const otp_attn_drop& drop) {
-    const int bh = blockIdx.x, row = blockIdx.y, lane = threadIdx.x;
-    const float* sb = slabs + (size_t)bh * NS * HSP * HSP;
-    const float* pb = P + (size_t)bh * HSP * HSP;
-    float dp[2], pv[2], mf[2], acc = 0.f;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int col = lane + 64 * h;
-        dp[h] = 0.f;
-        pv[h] = 0.f;
-        mf[h] = 1.f;
-        if (row < hs && col < hs) {
-            for (int s = 0; s < NS; ++s) dp[h] += sb[((size_t)s * HSP + row) * HSP + col];
-            pv[h] = pb[row * HSP + col];
-            if (DROP) {
-                mf[h] = otp_attn_drop_at(drop, otp_attn_drop_row((uint64_t)bh * hs + row, hs), col);
-                dp[h] *= mf[h];
-            }
-        }
-        acc += dp[h] * pv[h];
-    }
-    acc = wave_sum(acc);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int col = lane + 64 * h;
-        if (col < HSP) {
-            const float v = (row < hs && col < hs) ? pv[h] * (dp[h] - acc) : 0.f;
-            dS[((size_t)bh * HSP + row) * HSP + col] = v;
-            dST[((size_t)bh * HSP + col) * HSP + row] = v;
-            PT[((size_t)bh * HSP + col) * HSP + row] = (row < hs && col < hs) ? (DROP ? pv[h] * mf[h] : pv[h]) : 0.f;
-        }
-    }
-}
-__global__ __launch_bounds__(64) void softmax_bwd_kernel(const float* __restrict__ slabs, const float* __restrict__ P,
-                                                          float* __restrict__ dS, float* __restrict__ dST,
-                                                          float* __restrict__ PT, int hs, int HSP, int NS) {
-    softmax_bwd_body<false>(slabs, P, dS, dST, PT, hs, HSP, NS, otp_attn_drop{});
-}
-__global__ __launch_bounds__(64) void softmax_bwd_drop_kernel(const float* __restrict__ slabs, const float* __restrict__ P,
-                                                               float* __restrict__ dS, float* __restrict__ dST,
-                                                               float* __restrict__ PT, int hs, int HSP, int NS, otp_attn_drop drop) {
-    softmax_bwd_body<true>(slabs, P, dS, dST, PT, hs, HSP, NS, drop);
-}
-
 }  // namespace
 
 extern "C" int otp_ln_channel_backward(const void* x, const void* grad_y, const void* gamma, void* grad_x, void* dy_xhat,
@@ -580,37 +513,6 @@ extern "C" int otp_upsample_linear_backward(const void* grad_out, void* grad_x, 
     hipLaunchKernelGGL(upsample_linear_bwd_kernel, dim3(otp_ceil_div(T, 256), B * C), dim3(256), 0,
                        static_cast<hipStream_t>(stream), static_cast<const float*>(grad_out), static_cast<float*>(grad_x), C, T,
                        f, out_ctot, out_coff);
-    return otp_launch_status();
-}
-
-extern "C" int otp_transpose_scale(const void* in, void* out, int batches, int R, int Cc, float scale, void* stream) {
-    if (!in || !out || batches <= 0 || R <= 0 || Cc <= 0) return OTP_ERR_BAD_ARG;
-    hipLaunchKernelGGL(transpose_scale_kernel, dim3(otp_ceil_div(Cc, 32), otp_ceil_div(R, 32), batches), dim3(32, 8), 0,
-                       static_cast<hipStream_t>(stream), static_cast<const float*>(in), static_cast<float*>(out), R, Cc, scale);
-    return otp_launch_status();
-}
-
-extern "C" int otp_softmax_backward(const void* slabs, const void* P, void* dS, void* dST, void* PT, int BH, int hs, int NS,
-                                    void* stream) {
-    if (!slabs || !P || !dS || !dST || !PT || BH <= 0 || hs <= 0 || NS <= 0) return OTP_ERR_BAD_ARG;
-    const int HSP = (hs + 15) & ~15;
-    if (HSP > 128) return OTP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(softmax_bwd_kernel, dim3(BH, HSP), dim3(64), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const float*>(slabs), static_cast<const float*>(P), static_cast<float*>(dS),
-                       static_cast<float*>(dST), static_cast<float*>(PT), hs, HSP, NS);
-    return otp_launch_status();
-}
-
-extern "C" int otp_softmax_backward_dropout(const void* slabs, const void* P, void* dS, void* dST, void* PT, int BH, int hs, int NS,
-                                            float p, unsigned long long seed, void* stream) {
-    if (!slabs || !P || !dS || !dST || !PT || BH <= 0 || hs <= 0 || NS <= 0 || !otp_attn_drop_rate_ok(p)) return OTP_ERR_BAD_ARG;
-    const otp_attn_drop drop = otp_attn_drop_make(p, seed);
-    if (!drop.thr) return otp_softmax_backward(slabs, P, dS, dST, PT, BH, hs, NS, stream);
-    const int HSP = (hs + 15) & ~15;
-    if (HSP > 128) return OTP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(softmax_bwd_drop_kernel, dim3(BH, HSP), dim3(64), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const float*>(slabs), static_cast<const float*>(P), static_cast<float*>(dS),
-                       static_cast<float*>(dST), static_cast<float*>(PT), hs, HSP, NS, drop);
     return otp_launch_status();
 }
 

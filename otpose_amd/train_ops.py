@@ -551,6 +551,7 @@ class ChanAttnFunction(Function):
         bh, hs = b * n_head, c // n_head
         hsp = (hs + 15) // 16 * 16
         ns = L.otp_chan_attn_splits(bh, t)
+        # the workspace is slabs (bh ns matrices) | P | m P: attn_workspace in csrc/chanattn.hip states the layout
         probs = ws[bh * ns * hsp * hsp: bh * ns * hsp * hsp + bh * hsp * hsp].clone()    # softmax matrix (undropped), zero padded
         ctx.save_for_backward(q, k, v, probs)
         ctx.cfg, ctx.drop = (n_head, scale), (p, seed)
@@ -572,7 +573,7 @@ class ChanAttnFunction(Function):
         hip.check(L.otp_transpose_scale(hip.ptr(gout), hip.ptr(d_o), bh, t, hs, 1.0, st), "otp_transpose_scale")
         ns = L.otp_chan_attn_splits(bh, t)
         slabs = new(bh * ns * hsp * hsp)
-        # (every product of the backward has a gradient operand: bfloat16 pieces - otp_bf16_pieces in csrc/transformer.hip)
+        # (every product of the backward has a gradient operand: bfloat16 pieces - otp_bf16_pieces in csrc/chanattn.hip)
         hip.check(L.otp_chan_attn_scores_bf16p(hip.ptr(d_o), hip.ptr(v), hip.ptr(slabs), bh, hs, t, st), "otp_chan_attn_scores_bf16p")
         d_s, d_st, p_t = new(bh, hsp, hsp), new(bh, hsp, hsp), new(bh, hsp, hsp)
         drop_p, seed = ctx.drop

@@ -2,7 +2,7 @@
 tests/test_gpu_encoder_bwd.py (the kernels).  No GPU import.
 
 Every case carries the name of the branch it exists for; the ``*_branch`` functions below restate the host-side rules and the
-in-kernel loops of csrc/transformer_bwd.hip, csrc/transformer.hip and csrc/glue.hip from the case's numbers, and the host test
+in-kernel loops of csrc/transformer_bwd.hip, csrc/chanattn.hip and csrc/glue.hip from the case's numbers, and the host test
 asserts that name and numbers agree, so an edit of a list cannot silently drop a branch.
 
 Bounds are tests/reductions_cases.bound: 4 x the error of torch's fp32 CPU autograd on the same operands against float64, at
@@ -149,7 +149,7 @@ ATT_TC = 64
 
 
 def attn_splits(bh, t):
-    """csrc/transformer.hip: slices of T the score kernels work on (the library's otp_chan_attn_splits)."""
+    """csrc/chanattn.hip: slices of T the score kernels work on (the library's otp_chan_attn_splits)."""
     ns = 1
     while bh * ns < 768 and t // (ns * 2) >= 2 * ATT_TC:
         ns *= 2

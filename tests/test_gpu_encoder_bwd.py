@@ -1,5 +1,5 @@
 """The small backward kernels of the temporal encoders (csrc/transformer_bwd.hip, csrc/glue.hip, the attention
-products of csrc/transformer.hip on bfloat16 pieces)
+products and backward helpers of csrc/chanattn.hip, the products on bfloat16 pieces)
 against float64 (tests/encoder_bwd_ref.py) at the smallest sizes that reach every host-side branch rule and every loop of theirs
 (tests/encoder_bwd_cases.py names the branch of each case; tests/test_encoder_bwd_host.py derives it again from the numbers):
 the depthwise conv's dW in and around its paired float4 loop, into a zero and into a pre-filled destination, and on views that are

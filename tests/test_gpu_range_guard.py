@@ -180,7 +180,7 @@ def test_the_range_limit_travels_with_the_piece_type_projection():
 
 
 def test_the_range_limit_travels_with_the_piece_type_attention():
-    """csrc/transformer.hip on both piece types: one 1e5 element of v flags the forward's apply (OTP_RANGE_ATTN); the same v
+    """csrc/chanattn.hip on both piece types: one 1e5 element of v flags the forward's apply (OTP_RANGE_ATTN); the same v
     through the bfloat16-piece apply of the training backward does not."""
     B, C, NH, T = 1, 34, 2, 70
     hs, hsp = C // NH, 32

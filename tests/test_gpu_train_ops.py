@@ -297,7 +297,7 @@ def test_scale_residual_matches_autograd(b, c, t, masked):
 @pytest.mark.parametrize("mag", [1.0, 1e-5, 1e-8])
 def test_gradient_operands_of_any_magnitude_keep_their_precision(mag):
     """The backward sends GRADIENTS through the projection and the attention products.  Their magnitude is whatever the loss
-    makes it; the split products of those calls therefore use bfloat16 pieces (otp_bf16_pieces in csrc/densex.hip, transformer.hip:
+    makes it; the split products of those calls therefore use bfloat16 pieces (otp_bf16_pieces in csrc/densex.hip, chanattn.hip:
     16-17 bits at any magnitude), not the IEEE-half pieces of the forward, which flush 1e-8 to zero and hold 1e-5 to 8 bits."""
     from otpose_amd import ops
     from otpose_amd import train_ops as T

@@ -474,6 +474,24 @@ int otp_token_attn_forward_dropout(const void* q, const void* k, const void* v, 
 int otp_token_attn_backward_dropout(const void* q, const void* k, const void* v, const void* key_mask, const void* out,
                                     const void* lse, const void* dout, void* dq, void* dk, void* dv, void* workspace, int B, int C,
                                     int nh, int T, float scale, float p, unsigned long long seed, void* stream);
+/* token attention with IEEE-half products (csrc/tokattn_h.hip): the operands, masking, lse, workspace size and determinism of
+ * otp_token_attn_forward / _backward above, but scale q, k, v, dout and the probabilities P / dS are rounded to half (nearest
+ * even) on their way into v_mfma_f32_16x16x16_f16; sums (D = sum_c h(dout) h(out) is one of them, so that dS = P (dP - D) cancels),
+ * the online softmax and lse stay fp32, nothing is converted in HBM.
+ * p, seed: attention-probability dropout as in the _dropout entry points (p = 0: none), applied to P before its conversion.
+ * Range: |scale q|, |k|, |v|, |dout| must stay below 65504; a violation stores code 12 into the guard word - range_word, or the
+ * library's sticky word (otp_range_flag_read / otp_range_poison) when range_word is NULL.
+ * Gradients: dout is scaled per 64-query tile by the power of two that brings its largest magnitude into [1, 2) before the
+ * conversion (a gradient behind a mean-reduced loss lies in a half's subnormal range), dq, dk, dv are scaled back at their stores.
+ * otp_token_attn_h1_supported has the truth table of otp_token_attn_supported; otp_token_attn_h1_workspace is 4 B nh (T +
+ * ceil(T / 64)) bytes: D per query and that exponent per query tile. */
+int otp_token_attn_h1_supported(int C, int nh, int T);
+size_t otp_token_attn_h1_workspace(int B, int nh, int T, int hd);
+int otp_token_attn_forward_h1(const void* q, const void* k, const void* v, const void* key_mask, void* out, void* lse, int B, int C,
+                              int nh, int T, float scale, float p, unsigned long long seed, void* range_word, void* stream);
+int otp_token_attn_backward_h1(const void* q, const void* k, const void* v, const void* key_mask, const void* out, const void* lse,
+                               const void* dout, void* dq, void* dk, void* dv, void* workspace, int B, int C, int nh, int T,
+                               float scale, float p, unsigned long long seed, void* range_word, void* stream);
 int otp_local_attn_dropout(const void* q, const void* k, const void* v, const void* rel_pe, void* out, void* probs, int B, int C,
                            int T, int n_head, int window, float scale, float p, unsigned long long seed, void* stream);
 int otp_local_attn_backward_dropout(const void* q, const void* k, const void* v, const void* probs, const void* gout, void* gq,

@@ -26,7 +26,8 @@ The token encoders (reference model/OTPose.py:26-159, the DETR-style ``Transform
 (``flow_token_encoder``, width J, one head, FFN 2 J); ``MODEL.TOKEN_HEADS`` (2; divides the width, heads of at most 136 channels),
 ``MODEL.TOKEN_FFN`` (2 x the width), ``MODEL.TOKEN_PRE_NORM`` (False), ``MODEL.TOKEN_PE`` (``"sine"``, ``"learnable"`` or
 ``"none"``: the tables ``temporal_pos_embedding`` / ``flow_pos_embedding`` of OTPose.py:259-279; with ``"sine"`` the flow encoder
-runs without a table, width J = 17 has none).  A malformed value raises ``ValueError`` also when no layer is asked for.
+runs without a table, width J = 17 has none), ``MODEL.TOKEN_PRODUCTS`` (``"f32"`` or ``"half"``: the attention products of all
+three token encoders in exact fp32, or with IEEE-half operands and fp32 accumulation, csrc/tokattn_h.hip).  A malformed value raises ``ValueError`` also when no layer is asked for.
 Attention-probability dropout, training only (reference model/blocks.py:392,572 and the ``dropout`` OTPose.py:93 hands to
 ``nn.MultiheadAttention``; its OTPose.py:209-216 leaves the rate at 0): ``MODEL.ATTN_PDROP`` (0.0) for the two temporal encoders,
 ``MODEL.FLOW_ATTN_PDROP`` (0.0) for the flow encoder, ``MODEL.TOKEN_ATTN_DROPOUT`` (0.0) for the token encoders; floats in [0, 1).

@@ -214,7 +214,8 @@ __device__ __forceinline__ otp_f32x2 otp_x3_widen(uint32_t pair) { return otp_ha
 // include/otpose_hip.h: otp_range_flag_read / otp_range_poison.
 enum {
     OTP_RANGE_CONVX = 1, OTP_RANGE_CONVS = 2, OTP_RANGE_CONVS2 = 3, OTP_RANGE_POINTX = 4, OTP_RANGE_STEM = 5, OTP_RANGE_S8PASS = 6,
-    OTP_RANGE_MLPX = 7, OTP_RANGE_DENSEX = 8, OTP_RANGE_ATTN = 9, OTP_RANGE_DCNF = 10, OTP_RANGE_H16 = 11
+    OTP_RANGE_MLPX = 7, OTP_RANGE_DENSEX = 8, OTP_RANGE_ATTN = 9, OTP_RANGE_DCNF = 10, OTP_RANGE_H16 = 11,
+    OTP_RANGE_TOKATTN_H = 12
 };
 unsigned* otp_range_word();                                        // host side: the word's address (NULL without a GPU)
 template <typename P>                                              // P: the piece traits above, whose range_limit is the bound

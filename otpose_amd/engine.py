@@ -1107,8 +1107,15 @@ class InferenceEngine:
                 self.conv(self.v3(src), w[lo:lo + E].reshape(E, E, 1, 1), self.v3(out), bias=b[lo:lo + E],
                           res=None if res is None else self.v3(res))
             self.conv(self.v3(x), w[2 * E:].reshape(E, E, 1, 1), self.v3(v), bias=b[2 * E:])
-            self.call(self.lib.otp_token_attn_forward, "otp_token_attn_forward", hip.ptr(q), hip.ptr(k), hip.ptr(v), None,
-                      hip.ptr(att), None, B, C, layer.nhead, T, 1.0 / math.sqrt(E // layer.nhead))
+            if getattr(layer, "products", "f32") == "half":
+                # MODEL.TOKEN_PRODUCTS = "half": the same launch slot on the 16-bit matrix cores (csrc/tokattn_h.hip); no dropout
+                # in eval, and the guard word is the library's sticky one, which :meth:`_finish` / :meth:`run` read
+                self._half_tokens = True
+                self.call(self.lib.otp_token_attn_forward_h1, "otp_token_attn_forward_h1", hip.ptr(q), hip.ptr(k), hip.ptr(v), None,
+                          hip.ptr(att), None, B, C, layer.nhead, T, 1.0 / math.sqrt(E // layer.nhead), 0.0, 0, None)
+            else:
+                self.call(self.lib.otp_token_attn_forward, "otp_token_attn_forward", hip.ptr(q), hip.ptr(k), hip.ptr(v), None,
+                          hip.ptr(att), None, B, C, layer.nhead, T, 1.0 / math.sqrt(E // layer.nhead))
             self.conv(self.v3(att), a.out_proj.weight.reshape(E, E, 1, 1), self.v3(y), bias=a.out_proj.bias, res=self.v3(x))
             act = ACT_GELU if layer.activation == "gelu" else ACT_RELU
             F = layer.linear1.out_features
@@ -1334,7 +1341,7 @@ class InferenceEngine:
         process saw a value beyond a half's range, the heat-maps leave as NaN instead of as finite numbers computed from an
         overflowed operand (the host side raises: :meth:`run`, :meth:`check_range`)."""
         B, J, h, w = self.B, self.J, self.h, self.w
-        if self.use_x3 or self.h16:
+        if self.use_x3 or self.h16 or getattr(self, "_half_tokens", False):
             self.call(self.lib.otp_range_poison, "otp_range_poison", hip.ptr(out), out.numel())
         self.outputs = (out, rough, inter, prev_b, ctx.view(B, J, h, w), squeezed, total)
         torch.cuda.synchronize(self.dev)
@@ -1342,7 +1349,8 @@ class InferenceEngine:
     _RANGE_KERNELS = {1: "convx (3x3 / 1x1 convolutions from fp32 NCHW)", 2: "convs (BasicBlock convolutions on S8 records)",
                       3: "convs2 (stride-2 convolutions on S8 records)", 4: "pointx (1x1 convolutions)", 5: "stem convolution",
                       6: "S8 conversion / fuse passes", 7: "mlpx (TransformerBlock MLP)", 8: "densex (q / k / v / proj projections)",
-                      9: "channel attention", 10: "dcn_fused (warping head)", 11: "fp16 engine kernels"}
+                      9: "channel attention", 10: "dcn_fused (warping head)", 11: "fp16 engine kernels",
+                      12: "token attention with half products (MODEL.TOKEN_PRODUCTS)"}
 
     def _raise_range(self, code):
         raise FloatingPointError(

@@ -176,7 +176,8 @@ class OTPose(nn.Module):
                                                 ("flow_token_encoder", self.patch_dim, tk["flow_layers"], 1, tk["flow_ffn"])):
             if layers > 0:
                 layer = TransformerEncoderLayer(width, heads, ffn, dropout=0.1, activation="gelu", normalize_before=tk["pre_norm"])
-                setattr(self, name, TransformerEncoder(layer.set_attn_dropout(token_pdrop), layers))
+                # MODEL.TOKEN_PRODUCTS: "half" puts the attention products of all three encoders on the 16-bit matrix cores
+                setattr(self, name, TransformerEncoder(layer.set_attn_dropout(token_pdrop).set_products(tk["products"]), layers))
         pe, flow_pe = tk["pe"], tk["pe"]
         if flow_pe == "sine" and tk["flow_layers"] > 0:
             flow_pe = "none"                   # width 17 has no sine table (d_model % 4), in the reference either
@@ -283,8 +284,12 @@ class OTPose(nn.Module):
             raise ValueError(f"MODEL.TOKEN_PE must be one of {self.TOKEN_PE_KINDS}, got {pe!r}")
         if pe == "sine" and layers > 0 and d % 4:
             raise ValueError(f"MODEL.TOKEN_PE = 'sine' needs a token width that is a multiple of 4, got {d}")
+        from .token_attn import PRODUCTS
+        products = get("TOKEN_PRODUCTS", "f32")
+        if not isinstance(products, str) or products not in PRODUCTS:
+            raise ValueError(f"MODEL.TOKEN_PRODUCTS must be one of {PRODUCTS}, got {products!r}")
         return {"layers": layers, "flow_layers": flow_layers, "heads": heads, "ffn": ffn, "flow_ffn": flow_ffn, "pre_norm": pre,
-                "pe": pe}
+                "pe": pe, "products": products}
 
     def _embd_keys(self, get, d):
         """The conv embedding keys of the cfg, validated: {} at the defaults (no layer anywhere), else the layer counts and the

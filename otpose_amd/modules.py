@@ -508,7 +508,9 @@ class TransformerEncoderLayer(nn.Module):
     ``dropout`` to ``nn.MultiheadAttention`` as well).  Attention-probability dropout is switched on for a built layer with
     :meth:`set_attn_dropout` (what ``OTPose`` does for ``MODEL.TOKEN_ATTN_DROPOUT``): it is applied inside ``token_attn`` when the
     layer runs stochastically, with this library's own counter-based mask (otpose_amd/attn_dropout.py), not PyTorch's.
-    With ``return_atten_map`` the map comes from ``token_attn_map``: no gradient, and the undropped probabilities."""
+    With ``return_atten_map`` the map comes from ``token_attn_map``: no gradient, and the undropped probabilities.
+    :meth:`set_products` (``"f32"``, the default, or ``"half"``; ``OTPose``: ``MODEL.TOKEN_PRODUCTS``) chooses the arithmetic of the
+    attention products, ``token_attn``'s ``products``; the attribute ``products`` is no parameter and adds no ``state_dict`` key."""
 
     def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1, activation="gelu", normalize_before=False,
                  return_atten_map=False, attn_dropout=0.0):
@@ -526,6 +528,7 @@ class TransformerEncoderLayer(nn.Module):
             raise ValueError("TransformerEncoderLayer: attn_dropout must be 0 at construction; attention-probability dropout is "
                              "set on a built layer with set_attn_dropout(p)")
         self.attn_dropout = 0.0
+        self.products = "f32"
         self.self_attn = _SelfAttnParams(d_model)
         self.linear1 = nn.Linear(d_model, dim_feedforward)
         self.linear2 = nn.Linear(dim_feedforward, d_model)
@@ -538,6 +541,13 @@ class TransformerEncoderLayer(nn.Module):
         """Attention-probability dropout rate of this layer, a float in [0, 1) (``ValueError`` otherwise); returns the layer."""
         from .attn_dropout import check_rate
         self.attn_dropout = check_rate(p, "TransformerEncoderLayer: attn_dropout")
+        return self
+
+    def set_products(self, mode):
+        """Arithmetic of this layer's attention products: ``"f32"`` (default, exact) or ``"half"`` (``token_attn``'s
+        ``products``; what ``OTPose`` does for ``MODEL.TOKEN_PRODUCTS``); ``ValueError`` otherwise; returns the layer."""
+        from .token_attn import check_products
+        self.products = check_products(mode, "TransformerEncoderLayer: products")
         return self
 
     def _drop(self, x):
@@ -557,7 +567,8 @@ class TransformerEncoderLayer(nn.Module):
         v = _pointwise(value, w[2 * e:], b[2 * e:])
         scale = 1.0 / math.sqrt(e // self.nhead)
         p_attn = self.attn_dropout if self._stochastic else 0.0
-        out = _pointwise(token_attn(q, k, v, self.nhead, scale, mask, dropout_p=p_attn), a.out_proj.weight, a.out_proj.bias)
+        out = _pointwise(token_attn(q, k, v, self.nhead, scale, mask, dropout_p=p_attn, products=getattr(self, "products", "f32")),
+                         a.out_proj.weight, a.out_proj.bias)
         amap = token_attn_map(q.detach(), k.detach(), self.nhead, scale, mask) if self.return_atten_map else None
         return out, amap
 

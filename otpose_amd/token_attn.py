@@ -12,6 +12,10 @@ probabilities inside the kernels (the mask of otpose_amd/attn_dropout.py: the so
 of the P v product is masked and scaled by 1 / (1 - p)); the backward re-evaluates the same mask from the seed.  Supported: ``C % n_head == 0`` and a head
 width of at most 136; everything else raises ``ValueError`` before any launch.  CPU tensors raise ``NotImplementedError``,
 like every operator here.
+
+``products="half"`` (``token_attn`` only) runs the half-operand kernels of csrc/tokattn_h.hip: ``scale q``, ``k``, ``v``, the
+incoming gradient and the probabilities are rounded to IEEE half on their way into the 16-bit matrix cores, every sum, the softmax
+and every tensor in memory stay fp32.  Its operands must stay below 65504 in magnitude (:func:`check_range`).
 """
 from __future__ import annotations
 
@@ -23,9 +27,18 @@ from torch.autograd import Function
 from . import attn_dropout, hip
 from .ops import require_gpu
 
-__all__ = ["token_attn", "token_attn_map", "sine_position_embedding", "check_token_attn", "MAX_HEAD_WIDTH"]
+__all__ = ["token_attn", "token_attn_map", "sine_position_embedding", "check_token_attn", "check_products", "check_range",
+           "MAX_HEAD_WIDTH", "PRODUCTS"]
 
 MAX_HEAD_WIDTH = 136
+PRODUCTS = ("f32", "half")
+
+
+def check_products(products, what="token_attn: products"):
+    """Raise ``ValueError`` unless ``products`` names an arithmetic mode of the token attention; returns it."""
+    if not isinstance(products, str) or products not in PRODUCTS:
+        raise ValueError(f"{what} must be one of {PRODUCTS}, got {products!r}")
+    return products
 
 
 def check_token_attn(c, n_head, t):
@@ -113,7 +126,70 @@ class TokenAttnFunction(Function):
         return gq, gk, gv, None, None, None, None, None
 
 
-def token_attn(q, k, v, n_head, scale, key_padding_mask=None, dropout_p=0.0, seed=None):
+def check_range(device=None):
+    """The host side of the half kernels' range guard (csrc/range.hip): synchronise ``device`` and raise ``FloatingPointError`` if
+    a 16-bit-operand kernel of this process has seen a value beyond a half's range since the last check; the sticky word is
+    cleared.  ``token_attn(products="half")`` calls it after every eager launch; under a stream capture it cannot (the tensors
+    of a violating launch are NaN-filled on the device all the same) and the owner of the graph calls it after a replay."""
+    torch.cuda.synchronize(device)
+    code = hip.lib().otp_range_flag_read(1)
+    if code:
+        raise FloatingPointError(
+            f"otpose_amd.token_attn: a value left the range of an IEEE half (|x| >= 65504, or a non-finite sum; kernel family "
+            f"{code}, 12 = token attention with half products); the tensors of that launch were NaN-filled on the device.  "
+            "Rescale the operands or use products='f32'.")
+
+
+def _guard(device, *outs):
+    """Behind a launch of the half kernels: NaN into ``outs`` on the device if the guard word is set, then the host check."""
+    for t in outs:
+        if t is not None:
+            hip.check(hip.lib().otp_range_poison(hip.ptr(t), t.numel(), hip.stream_of(t)), "otp_range_poison")
+    if not torch.cuda.is_current_stream_capturing():
+        check_range(device)
+
+
+def _forward_half(q, k, v, mask, n_head, scale, want_lse, p=0.0, seed=0):
+    b, c, t = q.shape
+    out = torch.empty_like(q)
+    lse = torch.empty((b, n_head, t), dtype=torch.float32, device=q.device) if want_lse else None
+    hip.check(hip.lib().otp_token_attn_forward_h1(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(mask), hip.ptr(out), hip.ptr(lse),
+                                                  b, c, n_head, t, scale, p, seed, None, hip.stream_of(q)),
+              "otp_token_attn_forward_h1")
+    _guard(q.device, out)
+    return out, lse
+
+
+class TokenAttnHalfFunction(Function):
+    """``token_attn(products="half")`` with a backward: ``otp_token_attn_forward_h1`` / ``otp_token_attn_backward_h1``, which keep
+    what :class:`TokenAttnFunction` keeps.  The gradient is that of the rounded forward with the roundings passed straight
+    through; the backward rounds its own operands (``dout``, dS) to half as well."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, n_head, scale, p=0.0, seed=0):
+        out, lse = _forward_half(q, k, v, mask, n_head, scale, True, p, seed)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.mask, ctx.cfg, ctx.drop = mask, (n_head, scale), (p, seed)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        q, k, v, out, lse = ctx.saved_tensors
+        n_head, scale = ctx.cfg
+        b, c, t = q.shape
+        L = hip.lib()
+        gout = gout.contiguous()
+        gq, gk, gv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+        ws = torch.empty(L.otp_token_attn_h1_workspace(b, n_head, t, c // n_head) // 4, dtype=torch.float32, device=q.device)
+        p, seed = ctx.drop
+        hip.check(L.otp_token_attn_backward_h1(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(ctx.mask), hip.ptr(out), hip.ptr(lse),
+                                               hip.ptr(gout), hip.ptr(gq), hip.ptr(gk), hip.ptr(gv), hip.ptr(ws), b, c, n_head, t,
+                                               scale, p, seed, None, hip.stream_of(q)), "otp_token_attn_backward_h1")
+        _guard(q.device, gq, gk, gv)
+        return gq, gk, gv, None, None, None, None, None
+
+
+def token_attn(q, k, v, n_head, scale, key_padding_mask=None, dropout_p=0.0, seed=None, products="f32"):
     """softmax(scale q^T k) v per head, ``(B, C, T)`` in and out.  Under ``torch.no_grad()`` or with no operand requiring a
     gradient: one forward launch that stores no log-sum-exp; otherwise an autograd Function.
 
@@ -121,14 +197,22 @@ def token_attn(q, k, v, n_head, scale, key_padding_mask=None, dropout_p=0.0, see
     ``dropout_p`` and the survivors are scaled by 1 / (1 - dropout_p) in front of the P v product, as ``nn.MultiheadAttention``
     does in training.  ``seed`` (an int below 2^64) fixes the mask; None draws one per call from PyTorch's CUDA generator, so
     ``torch.manual_seed`` makes it repeat.  A rate whose 16-bit threshold is 0 (below 2^-17) is the call without dropout,
-    bit for bit, and draws nothing.  Under ``no_grad`` the dropout still applies: forward only."""
+    bit for bit, and draws nothing.  Under ``no_grad`` the dropout still applies: forward only.
+
+    ``products``: ``"f32"`` (default) multiplies on the exact-fp32 matrix instruction; ``"half"`` rounds ``scale q``, ``k``,
+    ``v``, the incoming gradient and the probabilities to IEEE half in front of the 16-bit matrix cores and accumulates in fp32
+    (csrc/tokattn_h.hip) - same operands, same mask and dropout semantics, outputs and gradients to about 2^-11 of their range.
+    There an operand of magnitude 65504 or more raises ``FloatingPointError`` and leaves the result NaN-filled
+    (:func:`check_range`; eager calls synchronise for it).  Anything else raises ``ValueError`` before any launch."""
+    check_products(products)
     p = attn_dropout.check_rate(dropout_p, "token_attn: dropout_p")
     _, _, _, mask = _check(q, k, v, n_head, key_padding_mask)
     scale = float(scale)
     p, seed = attn_dropout.seed_of(p, seed, q.device)
+    half = products == "half"
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        return TokenAttnFunction.apply(q, k, v, mask, n_head, scale, p, seed)
-    return _forward(q, k, v, mask, n_head, scale, False, p, seed)[0]
+        return (TokenAttnHalfFunction if half else TokenAttnFunction).apply(q, k, v, mask, n_head, scale, p, seed)
+    return (_forward_half if half else _forward)(q, k, v, mask, n_head, scale, False, p, seed)[0]
 
 
 def token_attn_map(q, k, n_head, scale, key_padding_mask=None):

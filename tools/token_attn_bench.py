@@ -3,7 +3,10 @@
 algorithmic TFLOP/s that gives and its share of the fp32-matrix peak, beside ``torch.nn.functional.scaled_dot_product_attention``
 on the same operands.
 
-    python tools/token_attn_bench.py [--iters 10] [--warmup 3] [--dropout P] [--out profiles/token_attn_bench.txt]
+    python tools/token_attn_bench.py [--iters 10] [--warmup 3] [--dropout P] [--products half] [--out profiles/token_attn_bench.txt]
+
+``--products half`` adds, per shape, a row for the half-operand kernels (csrc/tokattn_h.hip): their times, the ratio of the fp32
+kernels' time to theirs, the ratio of SDPA's time to theirs, and their largest difference from SDPA's output.
 
 ``--dropout P`` (0 < P < 1) adds, per shape, the times of the ``_dropout`` entry points at rate P beside the p = 0 times of the
 same run: what the in-kernel mask (8 hashes per lane and key tile forward and in backward pass A, 16 in pass B) costs.
@@ -54,6 +57,8 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--dropout", type=float, default=0.0, help="also time the dropout entry points at this rate")
+    ap.add_argument("--products", choices=("f32", "half"), default="f32",
+                    help="half: add a row per shape with the half-operand kernels beside the fp32 and SDPA columns")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not 0.0 <= a.dropout < 1.0:
@@ -98,6 +103,22 @@ def main():
         if a.dropout > 0.0:
             d_fwd, d_both = timed(fwd_drop, a.iters, a.warmup), timed(both_drop, a.iters, a.warmup)
 
+        # --products half: the half-operand kernels (csrc/tokattn_h.hip) on the same operands, the same timing method
+        def fwd_half(keep_lse=False):
+            hip.check(L.otp_token_attn_forward_h1(P(q), P(k), P(v), None, P(out), P(lse) if keep_lse else None, b, c, nh, t, scale,
+                                                  0.0, 0, None, st), "otp_token_attn_forward_h1")
+
+        ws_h = torch.empty(L.otp_token_attn_h1_workspace(b, nh, t, c // nh) // 4, device=dev)
+
+        def both_half():
+            fwd_half(True)
+            hip.check(L.otp_token_attn_backward_h1(P(q), P(k), P(v), None, P(out), P(lse), P(go), P(gq), P(gk), P(gv), P(ws_h), b, c,
+                                                   nh, t, scale, 0.0, 0, None, st), "otp_token_attn_backward_h1")
+        if a.products == "half":
+            h_fwd, h_both = timed(fwd_half, a.iters, a.warmup), timed(both_half, a.iters, a.warmup)
+            fwd_half()
+            h_out = out.clone()
+
         # the baseline in its own layout (B, heads, T, hd)
         sq, sk, sv, sgo = (x.view(b, nh, c // nh, t).transpose(2, 3).contiguous() for x in (q, k, v, go))
         e_it = max(2, a.iters // 3)
@@ -121,6 +142,13 @@ def main():
         if a.dropout > 0.0:
             lines.append("%-18s %8.2f %7s %5.2fx | %9.2f %7s %5.2fx | dropout p = %g against the p = 0 row above" % (
                 "", d_fwd, "", d_fwd / t_fwd, d_both, "", d_both / t_both, a.dropout))
+        if a.products == "half":
+            h_diff = float((h_out - ref).abs().max())
+            assert h_diff < 1e-2, h_diff
+            lines.append("%-18s %8.2f %7.1f %5.2fx | %9.2f %7.1f %5.2fx | %9.2f %11.2f | %9.1e  half products: x = f32 time / half "
+                         "time, then sdpa time / half time" % ("  products=half", h_fwd, f_fwd / h_fwd / 1e9, t_fwd / h_fwd, h_both,
+                                                               f_both / h_both / 1e9, t_both / h_both, s_fwd / h_fwd,
+                                                               s_both / h_both, h_diff))
         del leaves, sq, sk, sv, sgo, ref
         torch.cuda.empty_cache()
     lines.append("FLOP: forward 4 B T^2 C, forward + backward 14 B T^2 C; peak %.1f TFLOP/s (fp32 matrix)" % (PEAK / 1e12))
